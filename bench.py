@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: AnemoiModelEncProcDec forward (BASELINE.json configurations).
 
-    python bench.py --gpus N --steps K --warmup W [--config o96|o96-res6|n320|gnn]
+    python bench.py --gpus N --steps K --warmup W [--config o96|o96-res6|n320|gnn] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full forward (encoder -> processor layers -> decoder) over one synthetic ERA5-shaped input that is already
@@ -10,9 +10,12 @@ resident in HBM.  metric = forward nodes*channels / s = N_data * num_channels / 
 hidden mesh is sharded across the ranks (halo all-to-all per processor layer, needed-rows exchange in the decoder): the
 total work is fixed -> "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  Extra objects: "roofline" (dominant kernel family, measured live with HIP events on the launch
-stream), "kernel_families" (algorithmic flops AND bytes per family), at N = 1 "cpu_baseline" (the oracle timed on the host
-cores on a bounded sample) and "kernels"; at N > 1 "rccl" (what the exchange carries).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; at N > 1 it carries "rccl" (what
+the exchange carries).  ``--full`` adds the measurements that take runs of their own: "roofline" (dominant kernel family,
+measured live with HIP events on the launch stream), "kernel_families" (algorithmic flops AND bytes per family), "components",
+at N = 1 "kernels", "gpu_eager_baseline" and "cpu_baseline" (the oracle timed on the host cores on a bounded sample), at N > 1
+the same forward timed over the RCCL chain beside the hipIpc wire.  ``--dump-outputs DIR`` writes what the last timed step
+computed as DIR/<name>.npy (float32; the inputs are seeded, so two builds can be compared output for output).
 
 Configurations (BASELINE.json `configs`): o96 = config 2 (the headline; default), o96-res6 = its stated res-6 variant,
 n320 = config 4 (mapper stress), gnn = config 5 (GraphConv processor on O96).
@@ -63,7 +66,13 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--kernels-only", action="store_true", help="developer aid: only the per-kernel table of one processor layer")
+    ap.add_argument("--full", action="store_true", help="also the extra measurements: per-kernel table, roofline, components, GPU-eager and "
+                    "CPU baselines (N = 1), the RCCL comparison leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, under 64 MB: a seeded sample of grid points beyond)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     for k, v in CONFIGS[args.config].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -518,6 +527,16 @@ def physical_cores() -> int:
         return os.cpu_count() or 1
 
 
+def usable_cpus() -> int:
+    """The CPUs this process may use: its affinity mask, capped by OMP_NUM_THREADS where that is set (a share of a larger host)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
 def cpu_baseline(model_fp32_params, cfg, g, x, budget_s: float = 150.0):
     """The oracle (CPU restatement of the reference, parity-pinned) on the host cores, fp32, same graph / inputs / weights:
     FULL forwards (encoder + all processor layers + decoder), 3 warm-up + 10 timed, median.  The thread
@@ -527,6 +546,7 @@ def cpu_baseline(model_fp32_params, cfg, g, x, budget_s: float = 150.0):
     from oracle import gt_oracle as O
 
     ncpu, ncore = os.cpu_count() or 1, physical_cores()
+    usable = usable_cpus()  # more threads than CPUs to run them on only oversubscribe
     p = model_fp32_params
     H, L, gt = cfg["num_heads"], cfg["num_layers"], cfg["kind"] == "gt"
     with torch.no_grad():
@@ -542,7 +562,7 @@ def cpu_baseline(model_fp32_params, cfg, g, x, budget_s: float = 150.0):
 
         e1 = layer(0, h0, proc_ea)[1] if not gt else proc_ea  # GNN layers >= 1 take the embedded edges
         best = None
-        for th in sorted({c for c in (8, 16, 32, 64, ncore, ncpu) if c <= ncpu}):
+        for th in sorted({c for c in (8, 16, 32, 64, ncore, ncpu, usable) if c <= min(ncpu, usable)}):
             torch.set_num_threads(th)
             t0 = time.perf_counter()
             layer(1 if L > 1 else 0, h0, e1 if L > 1 else proc_ea)
@@ -570,7 +590,7 @@ def cpu_baseline(model_fp32_params, cfg, g, x, budget_s: float = 150.0):
         runs = sorted(forward() for _ in range(reps))
         # beside the fastest thread count: ALL physical cores (BASELINE.md section 3 words the CPU line that way) - one warm-up, two timed
         all_cores = None
-        if ncore != cores and first * 3 <= 120:
+        if ncore != cores and ncore <= usable and first * 3 <= 120:
             torch.set_num_threads(ncore)
             forward()
             ac = sorted(forward() for _ in range(2))
@@ -581,6 +601,7 @@ def cpu_baseline(model_fp32_params, cfg, g, x, budget_s: float = 150.0):
     if all_cores is not None:
         all_cores["value"] = N * cfg["num_channels"] / all_cores["seconds_forward"]
     return {"value": N * cfg["num_channels"] / t_full, "unit": "nodes*channels/s", "cores": cores, "physical_cores": ncore, "logical_cpus": ncpu,
+            "usable_cpus": usable,
             "all_physical_cores": all_cores, "kind": "port",
             "sample": f"oracle fp32, FULL forward (encoder + {L} processor layers + decoder) on {cores} threads of {ncore} physical cores / {ncpu} "
                       f"logical CPUs (fastest thread count of a sweep over one processor layer): {warm} warm-up + {reps} timed forwards, "
@@ -654,6 +675,27 @@ def latest_traffic(tag: str):
     return json.load(open(files[-1])), os.path.basename(files[-1])
 
 
+DUMP_LIMIT_BYTES = 60_000_000  # all files together stay under 64 MB
+
+
+def dump_outputs(outputs: dict, out_dir: str) -> None:
+    """DIR/<name>.npy in float32.  An output above DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its grid points (the
+    second-to-last dimension, all variables of each), kept in grid order: the same rows for the same arguments in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        t = t.float()
+        if t.numel() * 4 > budget:
+            rows = t.shape[-2]
+            keep = max(1, budget // (4 * t.numel() // rows))
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(t.dim() - 2, idx)
+            print(f"[bench] {name}: {rows} grid points, wrote a seeded sample of {keep}", file=sys.stderr)
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.contiguous().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -707,7 +749,7 @@ def main():
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}[args.dtype]
 
     g, model, x = build(args, device)
-    params_fp32 = {k: v.detach().clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    params_fp32 = {k: v.detach().clone() for k, v in model.state_dict().items()} if rank == 0 and args.full else None
     model = model.to(device).to(dtype)
     x_dev = x.to(device).to(dtype)
     inp = {"data": x_dev}
@@ -849,9 +891,11 @@ def main():
             torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            run()
+            last = run()
         sync_all()
         elapsed = time.perf_counter() - t0
+        # what a caller of the timed path receives from its last step (a hipGraph replay leaves it in the captured output)
+        outputs = {"data": (last if last is not None else out).float().cpu()} if args.dump_outputs and rank == 0 else None
         if sentinel:
             torch.cuda._sleep(100)
             torch.cuda.synchronize()
@@ -893,7 +937,7 @@ def main():
             peer.uninstall()
             wire_was, wire = "ok" if int(flag.item()) else "a wait timed out during the timed region", None
             rccl_leg = {"ms_per_step_ipc": elapsed / args.steps * 1e3, "graph_segments_ipc": ipc_segments, "ipc_status": wire_was, "peer_channels": n_channels}
-            if transport != "ipc" or os.environ.get("ANEMOI_BENCH_RCCL_LEG", "1") == "1":
+            if args.full and (transport != "ipc" or os.environ.get("ANEMOI_BENCH_RCCL_LEG", "1") == "1"):
                 try:
                     with torch.inference_mode():
                         for _ in range(2):
@@ -962,7 +1006,9 @@ def main():
                 res["rccl"]["wire_note"] = wire_note
             if host_transport:
                 res["rccl"]["note"] = f"ANEMOI_BENCH_TRANSPORT={transport}: all ranks on ONE GPU (gloo control plane) - a code-path check, not a scaling number"
-        if world == 1 and not args.no_kernel_timing:
+        if outputs is not None:
+            dump_outputs(outputs, args.dump_outputs)
+        if world == 1 and args.full and not args.no_kernel_timing:
             host_ms = max(12.0, 4.0 * ms)
             with torch.inference_mode():
                 fam = profile_forward(step, dtype, host_ms)
@@ -1028,7 +1074,7 @@ def main():
                 if gs == "gnn_node_chain_kernel" and "scatter_sum_error" in res["roofline"]["gather_scatter"]:
                     res["roofline"]["gather_scatter"]["note"] = ("GraphConv's scatter-sum inside the node MLP launch: a GEMM chain whose panel load is "
                                                                   "the segmented sum; the HBM figure prices the whole launch against its bytes")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cfg = {"num_heads": args.heads, "num_layers": args.layers, "num_channels": args.channels, "kind": args.kind}
             try:
                 res["gpu_eager_baseline"] = gpu_eager_baseline(params_fp32, cfg, g, x, device)

@@ -177,7 +177,8 @@ def test_bench_entry_point_eight_ranks_on_one_gpu(wire):
     env = dict(os.environ, ANEMOI_BENCH_TRANSPORT=wire, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--layers", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--layers", "2", "--no-cpu-baseline",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=repo)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

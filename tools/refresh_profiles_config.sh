@@ -21,5 +21,5 @@ ANEMOI_BENCH_SENTINEL=1 timeout 280 rocprofv3 --kernel-trace --stats -d /tmp/p_$
 d=$(find /tmp/p_$c -name "*.db" | head -1)
 if [ -n "$d" ]; then python $R/tools/rocprof_summary.py $d --timed > $OUT/kernel_trace_summary_$c.txt 2>&1 < /dev/null; cp $OUT/kernel_trace_summary_$c.txt $R/profiles/${ROUND}_kernel_trace_summary_$c.txt; fi
 cd $R
-timeout 600 python bench.py --config $c --steps 10 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err < /dev/null
+timeout 600 python bench.py --config $c --steps 10 --warmup 3 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err < /dev/null
 head -c 1500 $OUT/bench_$c.json; echo; head -12 $OUT/kernel_trace_summary_$c.txt | cut -c1-70,108-170

@@ -5,8 +5,8 @@ set -x
 R=$PWD
 OUT=$R/gpurun_out/r02p
 mkdir -p $OUT
-python bench.py > $OUT/bench_o96.json 2> $OUT/bench_o96.err
-for c in o96-res6 n320 gnn; do python bench.py --config $c --steps 10 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
+python bench.py --full > $OUT/bench_o96.json 2> $OUT/bench_o96.err
+for c in o96-res6 n320 gnn; do python bench.py --config $c --steps 10 --warmup 3 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
 cd /tmp; export TMPDIR=/tmp
 for c in o96 o96-res6 n320 gnn; do
   rm -rf /tmp/p_$c

@@ -17,8 +17,8 @@ for c in o96 o96-res6 n320 gnn; do
   cp $OUT/pmc_traffic${s}_detail.json $R/profiles/r03_pmc_traffic${s}_detail.json
 done
 cd $R
-python bench.py > $OUT/bench_o96.json 2> $OUT/bench_o96.err
-for c in o96-res6 n320 gnn; do python bench.py --config $c --steps 10 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
+python bench.py --full > $OUT/bench_o96.json 2> $OUT/bench_o96.err
+for c in o96-res6 n320 gnn; do python bench.py --config $c --steps 10 --warmup 3 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err; done
 cd /tmp
 for c in o96 o96-res6 n320 gnn; do
   rm -rf /tmp/p_$c
@@ -37,5 +37,5 @@ timeout 600 python tools/rank_floor.py --world 8 --hidden-res 6 --wire ipc 2> $O
 timeout 300 python tools/peer_latency.py --loopback 2>&1 | grep peer_latency > $OUT/peer_latency.txt
 timeout 300 python tools/peer_latency.py --loopback --rows 512 2>&1 | grep peer_latency >> $OUT/peer_latency.txt
 timeout 300 python tools/peer_latency.py --world 2 2>&1 | grep peer_latency >> $OUT/peer_latency.txt
-ANEMOI_BENCH_TRANSPORT=ipc timeout 600 python bench.py --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_8ranks_one_gpu_ipc.json 2> $OUT/bench_8ranks_one_gpu_ipc.err
+ANEMOI_BENCH_TRANSPORT=ipc timeout 600 python bench.py --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline --full > $OUT/bench_8ranks_one_gpu_ipc.json 2> $OUT/bench_8ranks_one_gpu_ipc.err
 head -c 400 $OUT/bench_o96.json; cat $OUT/floor_w*_r*.json $OUT/peer_latency.txt
