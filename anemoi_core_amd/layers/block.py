@@ -10,6 +10,7 @@ instead of the reference's ~25 eager ops with [M, H, C] temporaries.
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Optional, Union
 
 import torch
@@ -23,6 +24,7 @@ from ..distributed.shapes import BipartiteGraphShardInfo, GraphShardInfo, comm_r
 from .conv import DeferredAggregate, GraphConv, mlp_chain_ok, node_mlp_chain
 from . import conv as _conv
 from .graphcache import get_csc, get_edge_features, get_reverse_csr
+from .handoff import Carrier, Handoff, inference_in, plain_layer_norm
 from .kernels import PaddedLinear
 from .normalization import ConditionalLayerNorm, apply_layer_norm
 from .mlp import MLP
@@ -78,70 +80,65 @@ def _identity_index(x: Tensor) -> Tensor:
 
 
 class _FusedWeights:
-    """Concatenated projection weights ([Wq;Wk;Wv;Ws] ...) rebuilt only when a parameter changes."""
+    """Weights derived from a block's parameters (concatenations [Wq;Wk;Wv;Ws] ..., LayerNorm folds, fragment-major images), rebuilt only
+    when one of those parameters changes."""
 
     def __init__(self):
         self._cache = {}
 
-    def get(self, tag: str, linears: list) -> tuple[Tensor, Tensor]:
-        ps = [p for lin in linears for p in (lin.weight, lin.bias) if p is not None]
-        sig = tuple((p.data_ptr(), version(p), p.dtype, str(p.device)) for p in ps)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in ps):  # training: gradients flow through the cat
-            return (torch.cat([lin.weight for lin in linears], dim=0),
-                    torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features) for lin in linears]))
-        hit = self._cache.get(tag)
-        if hit is not None and hit[0] == sig:
-            return hit[1], hit[2]
-        with torch.no_grad():
-            w = torch.cat([lin.weight for lin in linears], dim=0).contiguous()
-            b = torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features) for lin in linears]).contiguous()
-        self._cache[tag] = (sig, w, b)
-        return w, b
-
-    def ln_folded(self, tag: str, linears: list, ln) -> tuple[Tensor, Tensor, Tensor]:
-        """(W diag(gamma) in the model dtype, c = its fp32 row sums, d = W beta + b in fp32) for a LayerNorm folded into the
-        GEMM that follows it (ops.linear_ln_folded); rebuilt only when a parameter changes."""
-        ps = [p for lin in linears for p in (lin.weight, lin.bias) if p is not None] + [p for p in (ln.weight, ln.bias) if p is not None]
-        sig = tuple((p.data_ptr(), version(p), p.dtype, str(p.device)) for p in ps)
-        hit = self._cache.get("ln:" + tag)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        with torch.no_grad():
-            w = torch.cat([lin.weight for lin in linears], dim=0).float()
-            b = torch.cat([lin.bias.float() if lin.bias is not None else w.new_zeros(lin.out_features) for lin in linears])
-            ws = (w * ln.weight.float()).to(linears[0].weight.dtype).contiguous()
-            c = ws.float().sum(1).contiguous()
-            d = (b if ln.bias is None else w @ ln.bias.float() + b).contiguous()
-        self._cache["ln:" + tag] = (sig, (ws, c, d))
-        return ws, c, d
-
     def derived(self, tag: str, params: list, builder):
-        """``builder()`` cached until one of ``params`` changes (fragment-major images of weight slices / stacks)."""
-        ps = [p for p in params if p is not None]
-        sig = tuple((p.data_ptr(), version(p), p.dtype, str(p.device)) for p in ps)
-        hit = self._cache.get("der:" + tag)
+        """``builder()`` cached under ``tag`` until one of ``params`` changes."""
+        sig = tuple((p.data_ptr(), version(p), p.dtype, str(p.device)) for p in params if p is not None)
+        hit = self._cache.get(tag)
         if hit is not None and hit[0] == sig:
             return hit[1]
         with torch.no_grad():
             val = builder()
-        self._cache["der:" + tag] = (sig, val)
+        self._cache[tag] = (sig, val)
         return val
 
+    def get(self, tag: str, linears: list) -> tuple[Tensor, Tensor]:
+        """(W, b) of ``linears`` concatenated; in training a fresh concatenation through which the gradients flow."""
+        ps = [p for lin in linears for p in (lin.weight, lin.bias) if p is not None]
+
+        def cat():
+            return (torch.cat([lin.weight for lin in linears], dim=0).contiguous(),
+                    torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features) for lin in linears]).contiguous())
+        return cat() if torch.is_grad_enabled() and any(p.requires_grad for p in ps) else self.derived("cat:" + tag, ps, cat)
+
+    def ln_folded(self, tag: str, linears: list, ln) -> tuple[Tensor, Tensor, Tensor]:
+        """(W diag(gamma) in the model dtype, c = its fp32 row sums, d = W beta + b in fp32) for a LayerNorm folded into the
+        GEMM that follows it (ops.linear_ln_folded)."""
+        def build():
+            w = torch.cat([lin.weight for lin in linears], dim=0).float()
+            b = torch.cat([lin.bias.float() if lin.bias is not None else w.new_zeros(lin.out_features) for lin in linears])
+            ws = (w * ln.weight.float()).to(linears[0].weight.dtype).contiguous()
+            return ws, ws.float().sum(1).contiguous(), (b if ln.bias is None else w @ ln.bias.float() + b).contiguous()
+        return self.derived("ln:" + tag, [p for m in (*linears, ln) for p in (m.weight, m.bias)], build)
+
     def packed_edge(self, lin_edge) -> Tensor:
-        """fp32 [D, fe_pad] image of lin_edge for the fused attention, rebuilt only when the parameters change."""
-        ps = [p for p in (lin_edge.weight, lin_edge.bias) if p is not None]
-        sig = tuple((p.data_ptr(), version(p), p.dtype, str(p.device)) for p in ps)
-        hit = self._cache.get("edge")
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        with torch.no_grad():
-            w = ops.pack_edge_weights(lin_edge.weight.contiguous(), lin_edge.bias)
-        self._cache["edge"] = (sig, w)
-        return w
+        """fp32 [D, fe_pad] image of lin_edge for the fused attention."""
+        return self.derived("edge", [lin_edge.weight, lin_edge.bias], lambda: ops.pack_edge_weights(lin_edge.weight.contiguous(), lin_edge.bias))
 
 
 class BaseBlock(nn.Module):
     """Base class for network blocks."""
+
+
+@dataclass
+class TailRoute:
+    """How a GraphTransformer block tail runs (``GraphTransformerBaseBlock._tail_route``)."""
+    kind: str                               # "chain2" | "cluster" | "lnfold" | "plain"
+    next_block: Optional[nn.Module] = None  # the consumer the launch leaves something for (its projection; lnfold: row statistics)
+    projs: tuple = ()                       # the trailing projection's Linears, in the order the kernel writes their columns
+    lnq: Optional[nn.Module] = None         # the LayerNorm in front of them
+    tail_width: int = 0                     # the decoder's extractor as the trailing projection: its width padded to 128 columns
+    halo: bool = False                      # k|v of the local rows into the head of the next halo exchange's buffer
+
+    @property
+    def weights_tag(self) -> str:
+        """Cache key of the chain launch's weight images: the trailing projections, in their order."""
+        return "chain2:" + ":".join(str(id(lin)) for lin in self.projs)
 
 
 # ============================================================================================ GraphTransformer blocks
@@ -337,173 +334,160 @@ class GraphTransformerBaseBlock(BaseBlock):
 
     def _ln_fold_ok(self, ln, x: Tensor) -> bool:
         """The LayerNorm-fold path: inference, 16-bit, plain affine LayerNorm (see include/anemoi_hip.h)."""
-        return (_LN_FOLD and x.shape[0] >= _LN_FOLD_MIN_ROWS and type(ln).__name__ in ("LayerNorm", "AutocastLayerNorm")
-                and x.dtype != torch.float32 and x.is_cuda
-                and not (torch.is_grad_enabled() and (x.requires_grad or ln.weight.requires_grad)))
+        return (_LN_FOLD and x.shape[0] >= _LN_FOLD_MIN_ROWS and plain_layer_norm(ln) and x.dtype != torch.float32 and x.is_cuda
+                and not ops._needs_grad(x, ln.weight))
 
     def _chain_ok(self, ln, x: Tensor, cluster: bool = False) -> bool:
         """The row-resident chain kernel takes this block's projection / LayerNorm / MLP: inference, 16-bit, 512 channels, plain
         affine LayerNorm, Linear-GELU-Linear MLP with a hidden width that is a multiple of 512.  ``cluster``: the same question for the
         cluster chain, which takes the row counts BELOW the chain's gate (and a hidden width of 2048)."""
-        mlp = self.node_dst_mlp
-        if cluster and not (_CLUSTER_CHAIN and 0 < x.shape[0] < _LAYER_CHAIN_MIN_ROWS and mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3
-                            and mlp.mlp[0].weight.shape[0] == 4 * ops.CHAIN_CHANNELS):
+        mlp, C = self.node_dst_mlp, ops.CHAIN_CHANNELS
+        if not (_LAYER_CHAIN and x.is_cuda and x.dtype != torch.float32 and plain_layer_norm(ln)
+                and mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None):
             return False
-        return (_LAYER_CHAIN and x.is_cuda and x.dtype != torch.float32
-                and (cluster or x.shape[0] >= _LAYER_CHAIN_MIN_ROWS)
-                and type(ln).__name__ in ("LayerNorm", "AutocastLayerNorm") and ln.weight is not None
-                and mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None
-                and self.projection.weight.shape == (ops.CHAIN_CHANNELS, ops.CHAIN_CHANNELS) and self.projection.bias is not None
-                and mlp.mlp[0].weight.shape[1] == ops.CHAIN_CHANNELS and mlp.mlp[0].weight.shape[0] % ops.CHAIN_CHANNELS == 0
-                and mlp.mlp[2].weight.shape[0] == ops.CHAIN_CHANNELS and mlp.mlp[0].bias is not None and mlp.mlp[2].bias is not None
-                # (mixed layouts - an fp32-kept LayerNorm or weights next to 16-bit activations - take the GEMM launches; the chain ops raise on them)
-                and all(p is None or p.dtype == x.dtype for p in (ln.weight, ln.bias, self.projection.weight, self.projection.bias,
-                                                                   mlp.mlp[0].weight, mlp.mlp[0].bias, mlp.mlp[2].weight, mlp.mlp[2].bias))
-                # (the chain ops build no autograd graph: ANY trainable parameter of the tail keeps the differentiable path)
-                and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in (ln, self.projection, mlp) for p in m.parameters()))))
+        lin1, lin2 = mlp.mlp[0], mlp.mlp[2]
+        rows = (_CLUSTER_CHAIN and 0 < x.shape[0] < _LAYER_CHAIN_MIN_ROWS and lin1.weight.shape[0] == 4 * C) if cluster else x.shape[0] >= _LAYER_CHAIN_MIN_ROWS
+        return (rows and self.projection.weight.shape == (C, C) and self.projection.bias is not None
+                and lin1.weight.shape[1] == C and lin1.weight.shape[0] % C == 0 and lin2.weight.shape[0] == C
+                and lin1.bias is not None and lin2.bias is not None and inference_in(x, ln, self.projection, mlp))
 
-    def _qkvs_chain_ok(self, x: Tensor) -> bool:
-        """This block's layer_norm_attention + fused [q|k|v|self] projection can ride at the end of the PREVIOUS block's chain launch."""
-        ln = self.layer_norm_attention
-        A = self.attn_channels
-        return (type(ln).__name__ in ("LayerNorm", "AutocastLayerNorm") and ln.weight is not None and not self.qk_norm
-                and x.shape[1] == ops.CHAIN_CHANNELS and (4 * A) % ops.CHAIN_CHANNELS == 0 and self.lin_query.weight.shape[1] == ops.CHAIN_CHANNELS
-                and all(p is None or p.dtype == x.dtype for m in (ln, self.lin_query, self.lin_key, self.lin_value, self.lin_self) for p in m.parameters())
-                and not (torch.is_grad_enabled() and any(p.requires_grad for m in (ln, self.lin_query, self.lin_key, self.lin_value, self.lin_self)
-                                                         for p in m.parameters())))
+    def _chain_projections(self, halo: bool = False) -> tuple:
+        """(LayerNorm, Linears) of this block's fused projection of its input rows in the order a chain launch writes their columns:
+        q|k|v|self, or q|self|k|v where k|v go to the halo buffer."""
+        return self.layer_norm_attention, ([self.lin_query, self.lin_self, self.lin_key, self.lin_value] if halo else
+                                           [self.lin_query, self.lin_key, self.lin_value, self.lin_self])
 
-    def _kv_chain_ok(self, x: Tensor) -> bool:
-        """(mapper blocks) layer_norm_attention_src + fused [k|v] projection of the SOURCE rows can ride at the end of the chain launch that produces
-        those rows - the last processor block's, behind the latent skip."""
-        ln = getattr(self, "layer_norm_attention_src", None)
-        A = self.attn_channels
-        mods = (ln, self.lin_key, self.lin_value)
-        return (ln is not None and type(ln).__name__ in ("LayerNorm", "AutocastLayerNorm") and ln.weight is not None and not self.qk_norm
-                and x.shape[1] == ops.CHAIN_CHANNELS and (2 * A) % ops.CHAIN_CHANNELS == 0 and self.lin_key.weight.shape[1] == ops.CHAIN_CHANNELS
-                and all(p is None or p.dtype == x.dtype for m in mods for p in m.parameters())
-                and not (torch.is_grad_enabled() and any(p.requires_grad for m in mods for p in m.parameters())))
+    def _projections_chain_ok(self, x: Tensor) -> bool:
+        """This block's attention LayerNorm + fused projection (``_chain_projections``) can ride at the end of the chain launch that
+        produces its input rows ``x``."""
+        ln, projs = self._chain_projections()
+        return (plain_layer_norm(ln) and not self.qk_norm and x.shape[1] == ops.CHAIN_CHANNELS
+                and sum(p.out_features for p in projs) % ops.CHAIN_CHANNELS == 0 and projs[0].weight.shape[1] == ops.CHAIN_CHANNELS
+                and inference_in(x, ln, *projs))
 
-    def _post_attention(self, attn_plus_self: Tensor, x_skip: Tensor, cond: Optional[Tensor] = None, chain: Optional[dict] = None,
-                        extra: Optional[Tensor] = None, next_block=None, halo=None) -> Tensor:
-        """projection + residual, LayerNorm, MLP + residual.  Inference: the projection GEMM also emits the row statistics of
-        its output and the MLP's first GEMM applies the LayerNorm from them (no LayerNorm launch); with ``chain`` the last
-        GEMM does the same for the NEXT block's first LayerNorm.  ``extra`` (last block of a processor): the model's latent
-        skip (encoder_processor_decoder.py:295-296), added by the last GEMM's epilogue as a second residual."""
-        # ``halo`` (a sharded processor block at inference: (HaloPlan, group)): where the cluster chain takes the tail it also computes the NEXT
-        # block's LayerNorm + projections of the LOCAL rows - q | self into a buffer of their own, k | v straight into the head of the
-        # [local + halo, 2A] buffer whose tail the halo exchange fills.  The next block then starts with that exchange (``chain["halo_pre"]``):
-        # what crosses the wire are the owners' k | v rows (2 KiB per row instead of the 1-KiB LayerNorm'd row the reference exchanges,
-        # layers/block.py:1159-1172 - the exchange is latency-bound, SURVEY 8e) and no rank projects a halo row again.
-        if extra is not None and (ops._needs_grad(attn_plus_self, x_skip, extra, self.projection.weight) or extra.shape != x_skip.shape):
-            return self._post_attention(attn_plus_self, x_skip, cond, chain) + extra
+    def _ready_projection(self, h: Optional[Handoff], x: Tensor, ln, tag: str, lins: list) -> Optional[Tensor]:
+        """The projection of ``x`` a producer handed over: computed already, or from raw rows with the row statistics it left (LayerNorm fold)."""
+        if h is not None and h.proj is None and h.stats is not None and self._ln_fold_ok(ln, x):
+            ws, c, d = self._fused.ln_folded(tag, lins, ln)
+            return ops.linear_ln_folded(x, ws, c, d, h.stats, ln.eps)
+        return None if h is None else h.proj
+
+    def _tail_route(self, attn: Tensor, x_skip: Tensor, cond: Optional[Tensor], carrier: Optional[Carrier], extra: Optional[Tensor] = None,
+                    shares: Optional[tuple] = None) -> TailRoute:
+        """Every gate of a block tail, evaluated here and nowhere else.  ``shares`` (a sharded block at inference): the row counts of ALL ranks -
+        the halo payload of the next exchange must be the same on every rank."""
         ln, mlp = self.layer_norm_mlp_dst, self.node_dst_mlp
-        plain_mlp = mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None
-        cluster = cond is None and self._chain_ok(ln, attn_plus_self, cluster=True)
-        if (cond is None and (cluster or self._chain_ok(ln, attn_plus_self)) and attn_plus_self.shape == x_skip.shape
+        nxt = None if carrier is None else carrier.next_block
+        cluster = cond is None and self._chain_ok(ln, attn, cluster=True)
+        if (cond is None and (cluster or self._chain_ok(ln, attn)) and attn.shape == x_skip.shape
                 and (extra is None or extra.shape == x_skip.shape)):
-            # the NEXT consumer of this tail's output whose LayerNorm + projection ride at the end of the launch: the next processor block
-            # (q|k|v|self), or - behind the LAST processor block and the latent skip - the decoder's block (k|v of its source rows)
-            to_mapper = isinstance(next_block, GraphTransformerMapperBlock)
-            nb = None
-            if next_block is not None and chain is not None:
-                if to_mapper:
-                    nb = next_block if (not cluster and halo is None and next_block._kv_chain_ok(x_skip)) else None
-                elif extra is None and next_block._qkvs_chain_ok(x_skip):
-                    nb = next_block
-            if halo is not None and not (_CLUSTER_HALO and cluster and nb is not None and getattr(nb, "shard_strategy", None) == "edges"):
-                nb = None  # (a sharded block's k | v need the halo rows: only the cluster chain has the LayerNorm'd rows as an output)
-            hidden = mlp.mlp[0].weight.shape[0]
-            # a decoder's node_data_extractor (LayerNorm + Linear(512, out), layers/mapper.py:688-704) as the chain launch's NARROW trailing
-            # projection: the 40 320-row output of the tail is then neither written nor read back, and two launches disappear
-            tail = None
-            if chain is not None and nb is None and extra is None and not cluster and chain.get("tail_proj") is not None:
-                ln_t, lin_t = chain["tail_proj"]
-                o_pad = (lin_t.out_features + 127) // 128 * 128
-                if (o_pad < ops.CHAIN_CHANNELS and lin_t.in_features == ops.CHAIN_CHANNELS and type(ln_t).__name__ in ("LayerNorm", "AutocastLayerNorm")
-                        and ln_t.weight is not None and ops.gt_layer_chain2_supported(attn_plus_self, hidden, o_pad)
-                        and all(q_ is None or q_.dtype == attn_plus_self.dtype for m_ in (ln_t, lin_t) for q_ in m_.parameters())
-                        and not (torch.is_grad_enabled() and any(q_.requires_grad for m_ in (ln_t, lin_t) for q_ in m_.parameters()))):
-                    tail = (ln_t, lin_t, o_pad)
+            kind, hidden = "cluster" if cluster else "chain2", mlp.mlp[0].weight.shape[0]
             supported = ops.gt_cluster_chain_supported if cluster else ops.gt_layer_chain2_supported
-            if nb is not None and not supported(attn_plus_self, hidden, 4 * nb.attn_channels):
-                nb = None  # the per-column vectors of tail + trailing projection do not fit the kernel's LDS region: the tail alone
-            if supported(attn_plus_self, hidden, 0 if nb is None else 4 * nb.attn_channels):
-                lin1, lin2 = mlp.mlp[0], mlp.mlp[2]
-                qlins = [] if nb is None else ([nb.lin_key, nb.lin_value] if to_mapper else
-                                              [nb.lin_query, nb.lin_self, nb.lin_key, nb.lin_value] if halo is not None else
-                                              [nb.lin_query, nb.lin_key, nb.lin_value, nb.lin_self])
-                q_out = sum(lin.out_features for lin in qlins)
-                lnq = None if nb is None else (nb.layer_norm_attention_src if to_mapper else nb.layer_norm_attention)
-                params = [self.projection.weight, self.projection.bias, ln.weight, ln.bias, lin1.weight, lin1.bias, lin2.weight, lin2.bias]
-                params += [q for lin in qlins for q in (lin.weight, lin.bias)] + ([] if lnq is None else [lnq.weight, lnq.bias])
-                if tail is not None:
-                    params += [tail[0].weight, tail[0].bias, tail[1].weight, tail[1].bias]
+            halo = shares is not None
+            # the NEXT consumer of this tail's output whose LayerNorm + projections ride at the end of the launch: the next processor block
+            # (q|k|v|self), or - behind the LAST processor block and the latent skip - the decoder's block (k|v of its source rows).  A sharded
+            # block's k|v need the halo rows: only the cluster chain, on every rank, hands them over
+            to_mapper = isinstance(nxt, GraphTransformerMapperBlock)
+            nb = nxt if nxt is not None and (not cluster and not halo if to_mapper else extra is None) and nxt._projections_chain_ok(x_skip) else None
+            if halo and not (_CLUSTER_HALO and cluster and getattr(nb, "shard_strategy", None) == "edges" and shares
+                             and all(0 < n < _LAYER_CHAIN_MIN_ROWS for n in shares)):
+                nb = None
+            if nb is not None:
+                lnq, projs = nb._chain_projections(halo)
+                if supported(attn, hidden, sum(p.out_features for p in projs)):
+                    return TailRoute(kind, nb, tuple(projs), lnq, halo=halo)
+            # a decoder's node_data_extractor (LayerNorm + Linear(512, out), layers/mapper.py) as the chain launch's NARROW trailing projection:
+            # the tail's output rows are then neither written nor read back, and two launches disappear
+            if nb is None and carrier is not None and carrier.tail_proj is not None and extra is None and not cluster:
+                ln_t, lin_t = carrier.tail_proj
+                o_pad = (lin_t.out_features + 127) // 128 * 128
+                if (o_pad < ops.CHAIN_CHANNELS and lin_t.in_features == ops.CHAIN_CHANNELS and plain_layer_norm(ln_t)
+                        and supported(attn, hidden, o_pad) and inference_in(attn, ln_t, lin_t)):
+                    return TailRoute(kind, projs=(lin_t,), lnq=ln_t, tail_width=o_pad)
+            if supported(attn, hidden, 0):
+                return TailRoute(kind)
+            # (a hidden width whose vectors do not fit the kernel's LDS region: the GEMM launches)
+        if mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None and self._ln_fold_ok(ln, attn):
+            # the last GEMM leaves row statistics only for a reader: the next processor block, unsharded
+            reader = isinstance(nxt, GraphTransformerProcessorBlock) and shares is None and extra is None
+            return TailRoute("lnfold", nxt if reader else None)
+        return TailRoute("plain")
 
-                def build():
-                    w1g, d1 = ops.fold_layer_norm(lin1.weight, lin1.bias, ln.weight, ln.bias)
-                    parts = [self.projection.bias.float(), d1, lin2.bias.float()]
-                    wqg = None
-                    if nb is not None:
-                        wq = torch.cat([lin.weight for lin in qlins], dim=0)
-                        bq = torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features) for lin in qlins])
-                        wq, dq = ops.fold_layer_norm(wq, bq, lnq.weight, lnq.bias)
-                        wqg = ops.pack_weight_frag(wq)
-                        parts.append(dq)
-                    elif tail is not None:
-                        ln_t, lin_t, o_pad = tail
-                        pad = o_pad - lin_t.out_features
-                        wt = torch.nn.functional.pad(lin_t.weight, (0, 0, 0, pad))  # zero rows: the padded output columns are zeros
-                        bt = torch.nn.functional.pad(lin_t.bias if lin_t.bias is not None else lin_t.weight.new_zeros(lin_t.out_features), (0, pad))
-                        wt, dq = ops.fold_layer_norm(wt, bt, ln_t.weight, ln_t.bias)
-                        wqg = ops.pack_weight_frag(wt)
-                        parts.append(dq)
-                    return (ops.pack_weight_frag(self.projection.weight), ops.pack_weight_frag(w1g), ops.pack_weight_frag(lin2.weight),
-                            torch.cat(parts).to(lin1.weight.dtype).contiguous(), wqg)
-
-                wp, w1g, w2, vec, wqg = self._fused.derived(("chain2:tail" if tail is not None else "chain2") if nb is None else f"chain2:{id(nb)}:{len(qlins)}",
-                                                            params, build)
-                if tail is not None:
-                    _, q_t = ops.gt_layer_chain2(attn_plus_self, x_skip, wp, w1g, w2, vec, hidden, ln.eps, wqg=wqg, q_out_features=tail[2],
-                                                 lnq_eps=tail[0].eps, want_x_out=False)
-                    chain["tail_out"] = q_t[:, :tail[1].out_features]  # (a strided [N, out] view, as the mapper's own GEMM returns)
-                    return q_t
-                kw = {}
-                if halo is not None and nb is not None:
-                    plan, group = halo
-                    nl = x_skip.shape[0]
-                    buf = comm.recv_buffer(nl, plan.send_counts, plan.recv_counts, 2 * nb.attn_channels, x_skip.dtype, x_skip.device, group)
-                    kw["q_out2"], kw["q_split"] = buf[:nl], 2 * nb.attn_channels // ops.CHAIN_CHANNELS
-                res = (ops.gt_cluster_chain if cluster else ops.gt_layer_chain2)(
-                    attn_plus_self, x_skip, wp, w1g, w2, vec, hidden, ln.eps, extra=extra, wqg=wqg,
-                    q_out_features=q_out, lnq_eps=1e-5 if lnq is None else lnq.eps, **kw)
-                if kw:
-                    chain["halo_pre"] = {"x": res[0], "buf": buf, "qs": res[1]}
-                    return res[0]
-                if nb is not None:
-                    chain["qkvs_x"], chain["qkvs"] = res
-                    return res[0]
-                return res
-            # (a hidden width whose vectors do not fit the kernel's LDS region: the GEMM launches below)
-        if plain_mlp and self._ln_fold_ok(ln, attn_plus_self):
-            r = ops.linear_with_row_stats(attn_plus_self, self.projection.weight, self.projection.bias, x_skip)
-            if r is not None:
-                out, stats = r
-                lin1, lin2 = mlp.mlp[0], mlp.mlp[2]
-                ws, c, d = self._fused.ln_folded("mlp1", [lin1], ln)
-                h = ops.linear_ln_folded(out, ws, c, d, stats, ln.eps, act="gelu")
-                if h is None:
-                    h = ops.linear(ops.layer_norm(out, ln.weight, ln.bias, ln.eps), lin1.weight, lin1.bias, act="gelu")
-                if extra is not None:  # second residual = the gather-add epilogue with the identity index
-                    return ops.linear(h, lin2.weight, lin2.bias, residual=out, g1=extra, idx1=_identity_index(extra))
-                r2 = ops.linear_with_row_stats(h, lin2.weight, lin2.bias, out) if chain is not None else None
-                if r2 is not None:
-                    chain["x"], chain["stats"] = r2
-                    return r2[0]
-                return ops.linear(h, lin2.weight, lin2.bias, residual=out)
+    def _post_attention(self, attn_plus_self: Tensor, x_skip: Tensor, cond: Optional[Tensor] = None, carrier: Optional[Carrier] = None,
+                        extra: Optional[Tensor] = None, halo=None) -> Tensor:
+        """projection + residual, LayerNorm, MLP + residual on the route ``_tail_route`` picks.  ``extra`` (last block of a processor): the model's
+        latent skip (encoder_processor_decoder.py:295-296), a second residual.  ``halo`` (sharded block at inference: (HaloPlan, group)): where the
+        cluster chain takes every rank's tail it also writes the NEXT block's q | self of the local rows and their k | v into the head of the
+        [local + halo, 2A] buffer of the next exchange: the owners' k | v rows cross the wire (2 KiB per row instead of the 1-KiB LayerNorm'd row
+        of the reference, layers/block.py:1159-1172 - the exchange is latency-bound) and no rank projects a halo row again."""
+        if extra is not None and (ops._needs_grad(attn_plus_self, x_skip, extra, self.projection.weight) or extra.shape != x_skip.shape):
+            return self._post_attention(attn_plus_self, x_skip, cond) + extra
+        r = self._tail_route(attn_plus_self, x_skip, cond, carrier, extra, None if halo is None else halo[0].shares)
+        if r.kind in ("chain2", "cluster"):
+            return self._tail_chain(r, attn_plus_self, x_skip, carrier, extra, halo)
+        y = self._tail_lnfold(r, attn_plus_self, x_skip, carrier, extra) if r.kind == "lnfold" else None
+        if y is not None:
+            return y
         out = ops.linear(attn_plus_self, self.projection.weight, self.projection.bias, residual=x_skip)
-        h = apply_layer_norm(ln, out, cond)
-        y = self.node_dst_mlp(h, residual=out)
+        y = self.node_dst_mlp(apply_layer_norm(self.layer_norm_mlp_dst, out, cond), residual=out)
         return y if extra is None else y + extra
+
+    def _tail_chain(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor], halo) -> Tensor:
+        """The tail as ONE chain launch (the LayerNorms' affine parts folded into weight images built once per parameter version), with the
+        route's trailing projection."""
+        ln, lin1, lin2 = self.layer_norm_mlp_dst, self.node_dst_mlp.mlp[0], self.node_dst_mlp.mlp[2]
+        hidden, lnq = lin1.weight.shape[0], r.lnq
+        q_out = r.tail_width or sum(lin.out_features for lin in r.projs)
+        params = [self.projection.weight, self.projection.bias, ln.weight, ln.bias, lin1.weight, lin1.bias, lin2.weight, lin2.bias]
+        params += [q for lin in r.projs for q in (lin.weight, lin.bias)] + ([] if lnq is None else [lnq.weight, lnq.bias])
+
+        def build():
+            w1g, d1 = ops.fold_layer_norm(lin1.weight, lin1.bias, ln.weight, ln.bias)
+            parts, wqg = [self.projection.bias.float(), d1, lin2.bias.float()], None
+            if r.projs:  # (a narrow extractor: zero rows up to its padded width - the padded output columns are zeros)
+                pad = q_out - sum(lin.out_features for lin in r.projs)
+                wq = torch.nn.functional.pad(torch.cat([lin.weight for lin in r.projs], dim=0), (0, 0, 0, pad))
+                bq = torch.nn.functional.pad(torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features)
+                                                        for lin in r.projs]), (0, pad))
+                wq, dq = ops.fold_layer_norm(wq, bq, lnq.weight, lnq.bias)
+                wqg = ops.pack_weight_frag(wq)
+                parts.append(dq)
+            return (ops.pack_weight_frag(self.projection.weight), ops.pack_weight_frag(w1g), ops.pack_weight_frag(lin2.weight),
+                    torch.cat(parts).to(lin1.weight.dtype).contiguous(), wqg)
+
+        wp, w1g, w2, vec, wqg = self._fused.derived(r.weights_tag, params, build)
+        kw = dict(extra=extra, wqg=wqg, q_out_features=q_out, lnq_eps=1e-5 if lnq is None else lnq.eps)
+        if r.tail_width:
+            _, q_t = ops.gt_layer_chain2(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, want_x_out=False, **kw)
+            carrier.tail_out = q_t[:, :r.projs[0].out_features]  # (a strided [N, out] view, as the mapper's own GEMM returns)
+            return q_t
+        buf = None
+        if r.halo:
+            plan, group = halo
+            nl, width = x_skip.shape[0], 2 * r.next_block.attn_channels
+            buf = comm.recv_buffer(nl, plan.send_counts, plan.recv_counts, width, x_skip.dtype, x_skip.device, group)
+            kw.update(q_out2=buf[:nl], q_split=width // ops.CHAIN_CHANNELS)
+        res = (ops.gt_cluster_chain if r.kind == "cluster" else ops.gt_layer_chain2)(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, **kw)
+        return res if r.next_block is None else carrier.put(res[0], proj=res[1], kv=buf)
+
+    def _tail_lnfold(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor]) -> Optional[Tensor]:
+        """The tail as GEMM launches with the LayerNorm folded into the MLP's first: the projection GEMM emits the row statistics of its output.
+        None where the shapes are not eligible."""
+        ln, lin1, lin2 = self.layer_norm_mlp_dst, self.node_dst_mlp.mlp[0], self.node_dst_mlp.mlp[2]
+        first = ops.linear_with_row_stats(attn, self.projection.weight, self.projection.bias, x_skip)
+        if first is None:
+            return None
+        out, stats = first
+        ws, c, d = self._fused.ln_folded("mlp1", [lin1], ln)
+        h = ops.linear_ln_folded(out, ws, c, d, stats, ln.eps, act="gelu")
+        if h is None:
+            h = ops.linear(ops.layer_norm(out, ln.weight, ln.bias, ln.eps), lin1.weight, lin1.bias, act="gelu")
+        if extra is not None:  # second residual = the gather-add epilogue with the identity index
+            return ops.linear(h, lin2.weight, lin2.bias, residual=out, g1=extra, idx1=_identity_index(extra))
+        last = ops.linear_with_row_stats(h, lin2.weight, lin2.bias, out) if r.next_block is not None else None
+        if last is not None:  # the next block's first LayerNorm folds these statistics
+            return carrier.put(last[0], stats=last[1])
+        return ops.linear(h, lin2.weight, lin2.bias, residual=out)
 
 
 class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
@@ -532,6 +516,10 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
             raise ValueError(f"Invalid shard strategy '{shard_strategy}'")
         self.shard_strategy = shard_strategy
 
+    def _chain_projections(self, halo: bool = False) -> tuple:
+        """(the chain launch that produces this block's SOURCE rows: the last processor block's) LayerNorm_src + k|v."""
+        return self.layer_norm_attention_src, [self.lin_key, self.lin_value]
+
     def forward(self, x, edge_attr: Tensor, edge_index: Tensor, shard_info: BipartiteGraphShardInfo, batch_size: int,
                 size, model_comm_group=None, cond=None, edges_are_dst_sorted: bool = True, **layer_kwargs):
         x_src, x_dst = x
@@ -545,22 +533,13 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         A = self.attn_channels
         ln_s, ln_d = self.layer_norm_attention_src, self.layer_norm_attention_dest
         cond_src, cond_dst = cond if cond is not None else (None, None)  # block.py:979-980
-        # LayerNorm + projection per side; with the row statistics left by the mapper's embedding (``ln_stats``, inference) the
-        # LayerNorm is applied inside the projection GEMM from raw rows
-        st = layer_kwargs.get("ln_stats") or {}
-        # (the mapper's row chain launches computed a side's projection together with its embedding: layers/mapper.py)
-        qs, kv = st.get("proj:dst"), st.get("proj:src")
-        if cond is not None:
-            qs = kv = None
-        if cond is None:
-            e = st.get("dst")
-            if qs is None and e is not None and e[0] is x_dst and self._ln_fold_ok(ln_d, x_dst):
-                ws, c, d = self._fused.ln_folded("qs", [self.lin_query, self.lin_self], ln_d)
-                qs = ops.linear_ln_folded(x_dst, ws, c, d, e[1], ln_d.eps)
-            e = st.get("src")
-            if kv is None and e is not None and e[0] is x_src and self._ln_fold_ok(ln_s, x_src):
-                ws, c, d = self._fused.ln_folded("kv", [self.lin_key, self.lin_value], ln_s)
-                kv = ops.linear_ln_folded(x_src, ws, c, d, e[1], ln_s.eps)
+        # LayerNorm + projection per side, unless the launch that produced a side's rows handed it over (the mapper's row chain, the last
+        # processor block's chain launch) or left the row statistics that let the projection GEMM apply the LayerNorm (inference)
+        carrier = layer_kwargs.get("carrier")
+        qs = kv = None
+        if cond is None and carrier is not None:
+            qs = self._ready_projection(carrier.take(x_dst), x_dst, ln_d, "qs", [self.lin_query, self.lin_self])
+            kv = self._ready_projection(carrier.take(x_src), x_src, ln_s, "kv", [self.lin_key, self.lin_value])
         if qs is None:
             w_qs, b_qs = self._fused.get("qs", [self.lin_query, self.lin_self])
             qs = ops.linear(apply_layer_norm(ln_d, x_dst, cond_dst), w_qs, b_qs)
@@ -574,8 +553,7 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
         else:
             out = self._attention(qs[:, :A], kv[:, :A], kv[:, A:], qs[:, A:], edge_attr, csc,
                                   fused=dict(bufs=(qs, kv), q=(0, 0), s=(0, A), k=(1, 0), v=(1, A)))
-        ch = layer_kwargs.get("ln_chain")  # chain: statistics (or the ready projections) for the processor's first block
-        nodes_new_dst = self._post_attention(out, x_dst, cond_dst, ch, next_block=None if ch is None else ch.pop("next_block", None))
+        nodes_new_dst = self._post_attention(out, x_dst, cond_dst, carrier)
         if self.update_src_nodes:
             ln = self.layer_norm_mlp_src
             nodes_new_src = self.node_src_mlp(apply_layer_norm(ln, x_src, cond_src), residual=x_src)
@@ -613,7 +591,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
         assert shard_info.edges_are_sharded(), "Halo strategy requires edges to be sharded"
         bip = BipartiteGraphShardInfo(src_nodes=shard_info.nodes, dst_nodes=shard_info.nodes, edges=shard_info.edges)
         partition = build_graph_partition_from_shard_info(edge_index, (x, x), bip, group)
-        plan = HaloPlan(build_halo_info(partition, edge_index, comm_rank(group), edges_are_local=True, debug=ANEMOI_DEBUG_SHARDING))
+        plan = HaloPlan(build_halo_info(partition, edge_index, comm_rank(group), edges_are_local=True, debug=ANEMOI_DEBUG_SHARDING), shard_info.nodes)
         self._cached_halo = (specs, plan)
         if shared is not None:
             shared["specs"], shared["plan"] = specs, plan
@@ -624,38 +602,31 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
                 **kwargs):
         A = self.attn_channels
         ln = self.layer_norm_attention
-        chain = kwargs.get("ln_chain")
-        nxt = None if chain is None else chain.pop("next_block", None)
-        if (not model_is_distributed(model_comm_group) and chain is not None and cond is None
-                and (self._ln_fold_ok(ln, x) or chain.get("qkvs_x") is x or self._chain_ok(self.layer_norm_mlp_dst, x))):
-            qkvs = None
-            if chain.get("qkvs_x") is x:  # the previous block's chain launch computed this block's projections already
-                qkvs = chain["qkvs"]
-            elif chain.get("x") is x and self._ln_fold_ok(ln, x):  # the previous block's last GEMM left the row statistics of x
-                ws, c, d = self._fused.ln_folded("qkvs", [self.lin_query, self.lin_key, self.lin_value, self.lin_self], ln)
-                qkvs = ops.linear_ln_folded(x, ws, c, d, chain["stats"], ln.eps)
+        carrier, extra = kwargs.get("carrier"), kwargs.get("extra_residual")
+        h = None if carrier is None else carrier.take(x)  # what the launch that produced x left for this block
+        if (not model_is_distributed(model_comm_group) and carrier is not None and cond is None
+                and ((h is not None and h.proj is not None) or self._ln_fold_ok(ln, x) or self._chain_ok(self.layer_norm_mlp_dst, x))):
+            qkvs = self._ready_projection(h, x, ln, "qkvs", [self.lin_query, self.lin_key, self.lin_value, self.lin_self])
             if qkvs is None:
                 w, b = self._fused.get("qkvs", [self.lin_query, self.lin_key, self.lin_value, self.lin_self])
                 qkvs = ops.linear(ops.layer_norm(x, ln.weight, ln.bias, ln.eps), w, b)
-            chain.clear()
             q, k, v, x_r = qkvs[:, :A], qkvs[:, A:2 * A], qkvs[:, 2 * A:3 * A], qkvs[:, 3 * A:]
             csc = get_csc(edge_index, (x.shape[0], x.shape[0]), edges_are_dst_sorted)
             out = self._attention(q, k, v, x_r, edge_attr, csc)
-            return self._post_attention(out, x, cond, chain, kwargs.get("extra_residual"), next_block=nxt), edge_attr
+            return self._post_attention(out, x, cond, carrier, extra), edge_attr
         sharded = model_is_distributed(model_comm_group) and self.shard_strategy != "heads"
         x_plus_halo = None
-        pre = chain.pop("halo_pre", None) if chain is not None else None
-        if (pre is not None and pre["x"] is x and sharded and cond is None and not ops._needs_grad(x, ln.weight, self.lin_key.weight)):
+        if (h is not None and h.kv is not None and sharded and cond is None and not ops._needs_grad(x, ln.weight, self.lin_key.weight)):
             # the previous block's cluster-chain launch left this block's q | self projection and, in the head of the [local + halo, 2A]
             # buffer, the k | v rows of its own nodes: the exchange brings the halo nodes' k | v rows from their owners, then attention, tail
             plan = self._halo_plan(x, edge_index, shard_info, batch_size, model_comm_group, halo_cache)
             nl = x.shape[0]
-            kv, qs = pre["buf"], pre["qs"]
+            kv, qs = h.kv, h.proj
             comm.halo_exchange_into(kv, nl, plan.send_index, plan.send_counts, plan.recv_counts, model_comm_group, ops.gather_rows)
             csc = get_csc(plan.edge_index_local, (plan.info.total_nodes, plan.info.num_local_nodes), True)
             out = self._attention(qs[:, :A], kv[:, :A], kv[:, A:], qs[:, A:], edge_attr, csc,
                                   fused=dict(bufs=(qs, kv), q=(0, 0), s=(0, A), k=(1, 0), v=(1, A)), edge_prep=kwargs.get("edge_prep"))
-            return self._post_attention(out, x, cond, chain, kwargs.get("extra_residual"), next_block=nxt, halo=(plan, model_comm_group)), edge_attr
+            return self._post_attention(out, x, cond, carrier, extra, halo=(plan, model_comm_group)), edge_attr
         if (sharded and cond is None and not isinstance(ln, ConditionalLayerNorm) and not ops._needs_grad(x, ln.weight)):
             # inference on a shard: LayerNorm writes the head of the [local + halo] buffer, the all-to-all receives into its tail
             plan = self._halo_plan(x, edge_index, shard_info, batch_size, model_comm_group, halo_cache)
@@ -667,7 +638,7 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
             xn = apply_layer_norm(ln, x, cond)
         if model_is_distributed(model_comm_group) and self.shard_strategy == "heads":
             return self._forward_heads(x, xn, edge_attr, edge_index, shard_info, batch_size, model_comm_group, cond, halo_cache,
-                                       extra=kwargs.get("extra_residual")), edge_attr
+                                       extra=extra), edge_attr
         if model_is_distributed(model_comm_group):
             plan = self._halo_plan(x, edge_index, shard_info, batch_size, model_comm_group, halo_cache)
             if x_plus_halo is None:
@@ -697,9 +668,9 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
             fused = dict(bufs=(qkvs,), q=(0, 0), k=(0, A), v=(0, 2 * A), s=(0, 3 * A))
             csc = get_csc(edge_index, (n, n), edges_are_dst_sorted)
         out = self._attention(q, k, v, x_r, edge_attr, csc, fused=fused, edge_prep=kwargs.get("edge_prep"))
-        if x_plus_halo is not None and sharded and chain is not None:  # inference on a shard: the tail may prepare the next block's exchange
-            return self._post_attention(out, x, cond, chain, kwargs.get("extra_residual"), next_block=nxt, halo=(plan, model_comm_group)), edge_attr
-        return self._post_attention(out, x, cond, extra=kwargs.get("extra_residual")), edge_attr
+        if x_plus_halo is not None and carrier is not None:  # inference on a shard: the tail may prepare the next block's exchange
+            return self._post_attention(out, x, cond, carrier, extra, halo=(plan, model_comm_group)), edge_attr
+        return self._post_attention(out, x, cond, extra=extra), edge_attr
 
 
     def _forward_heads(self, x, xn, edge_attr, edge_index, shard_info, batch_size, group, cond, cache: Optional[dict], extra=None):
@@ -720,8 +691,9 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
 class HaloPlan:
     """HaloInfo + the device-side buffers the exchange needs (built once, reused by every layer and step)."""
 
-    def __init__(self, info: HaloInfo):
+    def __init__(self, info: HaloInfo, shares: Optional[tuple] = None):
         self.info = info
+        self.shares = tuple(shares or ())  # every rank's row count: what decides the payload of the exchange (GraphTransformerBaseBlock._tail_route)
         dev = info.edge_index_local.device
         idx = torch.cat(list(info.send_indices)) if len(info.send_indices) else torch.zeros(0, dtype=torch.long, device=dev)
         self.send_index = idx.to(torch.int32).contiguous()
@@ -757,8 +729,8 @@ class GraphConvProcessorBlock(GraphConvBaseBlock):
                 size=None, **layer_kwargs):
         if self.emb_edges is not None:
             edge_attr = self.emb_edges(edge_attr)
-        chain = layer_kwargs.get("gnn_chain")
-        nxt = None if chain is None else chain.pop("next_block", None)
+        carrier = layer_kwargs.get("carrier")
+        h = None if carrier is None else carrier.take(x)
         if model_is_distributed(model_comm_group):  # block.py:375: all node rows are needed as sources
             x_in = comm.gather_tensor(x, 0, shard_info.nodes, model_comm_group, reduce_in_backward=True)
             n_loc = x.shape[0]
@@ -768,20 +740,16 @@ class GraphConvProcessorBlock(GraphConvBaseBlock):
             assert out.shape[0] == n_loc
         else:
             # inference on the chain kernels: the previous block's node chain may have left this block's stacked node-level terms
-            p = chain["p"] if (chain is not None and chain.get("p_x") is x and self.conv.chain_ok(x, edge_attr)) else None
-            if chain is not None:
-                chain.clear()
+            p = h.proj if (h is not None and self.conv.chain_ok(x, edge_attr)) else None
             out, edges_new = self.conv(x, edge_attr, edge_index, size=size, p=p, defer_sum=mlp_chain_ok(self.node_mlp, 2 * ops.CHAIN_CHANNELS, x))
         if mlp_chain_ok(self.node_mlp, 2 * ops.CHAIN_CHANNELS, x) and out.dtype == x.dtype:
             kw = {}
-            if (chain is not None and not model_is_distributed(model_comm_group) and isinstance(nxt, GraphConvProcessorBlock)
+            nxt = None if carrier is None else carrier.next_block
+            if (not model_is_distributed(model_comm_group) and isinstance(nxt, GraphConvProcessorBlock)
                     and nxt.emb_edges is None and nxt.conv.chain_ok(x, edges_new)):
                 kw = dict(wt=nxt.conv.stacked_frag(), t_out_features=2 * ops.CHAIN_CHANNELS)
             res = node_mlp_chain(self.node_mlp, x, out, **kw)
-            if kw:
-                chain["p_x"], chain["p"] = res
-                return res[0], edges_new
-            return res, edges_new
+            return (carrier.put(res[0], proj=res[1]) if kw else res), edges_new
         if isinstance(out, DeferredAggregate):
             out = out.materialize()
         nodes_new = self.node_mlp(x, x2=out, residual=x)

@@ -11,6 +11,7 @@ import os
 
 from .. import ops
 from .graphcache import get_csc, get_reverse_csr
+from .handoff import inference_in, plain_layer_norm
 from .mlp import MLP
 from ..utils.tensors import version
 
@@ -57,12 +58,9 @@ def mlp_chain_ok(m: MLP, k_in: int, x: Tensor) -> bool:
     a plain affine LayerNorm (mlp_extra_layers = 0, mlp_implementation = "mlp")."""
     D = ops.CHAIN_CHANNELS
     return (_GNN_CHAIN and x.is_cuda and x.dtype != torch.float32 and x.shape[-1] == D
-            and m.mlp_implementation == "mlp" and len(m.mlp) == 5 and m.layer_norm is not None
-            and type(m.layer_norm).__name__ in ("LayerNorm", "AutocastLayerNorm") and m.layer_norm.weight is not None
+            and m.mlp_implementation == "mlp" and len(m.mlp) == 5 and m.layer_norm is not None and plain_layer_norm(m.layer_norm)
             and m.mlp[0].weight.shape == (D, k_in) and m.mlp[2].weight.shape == (D, D) and m.mlp[4].weight.shape == (D, D)
-            and m.mlp[0].weight.dtype == x.dtype and all(m.mlp[i].bias is not None for i in (0, 2, 4))
-            # (the chain ops build no autograd graph: ANY trainable parameter of the MLP keeps the differentiable path)
-            and not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in m.parameters()))))
+            and all(m.mlp[i].bias is not None for i in (0, 2, 4)) and inference_in(x, m))
 
 
 def node_mlp_chain(m: MLP, x: Tensor, agg: Tensor, *, wt: Optional[Tensor] = None, t_out_features: int = 0):
@@ -127,13 +125,7 @@ class GraphConv(nn.Module):
                             n_extra_layers=mlp_extra_layers + 1, mlp_implementation=mlp_implementation)
 
     def _stacked_node_weight(self, w: Tensor, D: int) -> Tensor:
-        sig = (w.data_ptr(), version(w), w.dtype, str(w.device))
-        hit = self.__dict__.get("_stacked")
-        if hit is None or hit[0] != sig:
-            with torch.no_grad():
-                hit = (sig, torch.cat([w[:, :D], w[:, D:2 * D]], dim=0).contiguous())
-            self.__dict__["_stacked"] = hit
-        return hit[1]
+        return _derived(self, "stacked", [w], lambda: torch.cat([w[:, :D], w[:, D:2 * D]], dim=0).contiguous())
 
     def stacked_frag(self) -> Tensor:
         """fragment-major image of [W_i; W_j] (the node-level halves of the edge MLP's first Linear): what the PREVIOUS block's node

@@ -29,6 +29,7 @@ from ..distributed.partition import (
 )
 from ..distributed.shapes import BipartiteGraphShardInfo, comm_rank, comm_size, get_shard_sizes, model_is_distributed
 from .block import GraphConvMapperBlock, GraphTransformerMapperBlock
+from .handoff import Carrier, inference_in, plain_layer_norm
 from .kernels import PaddedLinear
 from .mlp import MLP
 from .utils import compute_mlp_hidden_dim, load_layer_kernels
@@ -150,17 +151,11 @@ class GraphTransformerBaseMapper(BaseMapper):
     def _row_chain_ok(self, x: Tensor, lin, ln, projs: list) -> bool:
         """The embedding -> LayerNorm -> projection chain launch (ops.gt_row_chain) takes this side: inference, 16-bit, 512 channels, a
         plain affine LayerNorm, rows whose width is a multiple of 8 (the model pads its inputs), enough rows to fill the chip."""
-        if not (_ROW_CHAIN and x.is_cuda and x.dim() == 2 and x.dtype != torch.float32 and x.shape[0] >= _ROW_CHAIN_MIN_ROWS
+        return (_ROW_CHAIN and x.is_cuda and x.dim() == 2 and x.dtype != torch.float32 and x.shape[0] >= _ROW_CHAIN_MIN_ROWS
                 and not (_ROW_CHAIN_GEMM_BAND[0] < x.shape[0] < _ROW_CHAIN_GEMM_BAND[1])
-                and self.hidden_dim == ops.CHAIN_CHANNELS and type(ln).__name__ in ("LayerNorm", "AutocastLayerNorm") and ln.weight is not None):
-            return False
-        q_out = sum(p.out_features for p in projs)
-        mods = [lin, ln, *projs]
-        if not (lin.in_features <= x.shape[1] and lin.bias is not None and ops.gt_row_chain_supported(x, q_out)
-                and all(p.in_features == ops.CHAIN_CHANNELS for p in projs)
-                and all(q is None or q.dtype == x.dtype for m in mods for q in m.parameters())):
-            return False
-        return not (torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for m in mods for q in m.parameters())))
+                and self.hidden_dim == ops.CHAIN_CHANNELS and plain_layer_norm(ln) and lin.in_features <= x.shape[1] and lin.bias is not None
+                and ops.gt_row_chain_supported(x, sum(p.out_features for p in projs)) and all(p.in_features == ops.CHAIN_CHANNELS for p in projs)
+                and inference_in(x, lin, ln, *projs))
 
     def _row_chain(self, x: Tensor, lin, side: str, want_x: bool):
         """(embedded rows or None, the block's fused projection of that side) in one launch, or None if the shapes do not fit."""
@@ -182,25 +177,21 @@ class GraphTransformerBaseMapper(BaseMapper):
         we, wqg, vec, q_out = blk._fused.derived(f"rowchain:{side}:{K}", params, build)
         return ops.gt_row_chain(x, we, wqg, vec, q_out, ln.eps, want_x_out=want_x)
 
-    def _embed(self, padded: PaddedLinear, x: Tensor, lin, side: str, ln_stats: Optional[dict]) -> Tensor:
-        """The node embedding.  With ``ln_stats`` (inference): where the shapes fit, embedding, the block's LayerNorm on that side and its
-        fused projection run as ONE row-resident launch (``ln_stats["proj:" + side]`` = the projection; the embedded SOURCE rows are not
-        even written unless the block updates them) - else the embedding leaves the row statistics of its output there when the block's
+    def _embed(self, padded: PaddedLinear, x: Tensor, lin, side: str, carrier: Optional[Carrier]) -> Tensor:
+        """The node embedding.  With a ``carrier`` (inference): where the shapes fit, embedding, the block's LayerNorm on that side and its
+        fused projection run as ONE row-resident launch that hands the projection to the block (the embedded SOURCE rows are not even
+        written unless the block updates them) - else the embedding hands over the row statistics of its output when the block's
         LayerNorm on that side can be folded into the GEMM behind it."""
         ln = self.proc.layer_norm_attention_src if side == "src" else self.proc.layer_norm_attention_dest
-        if ln_stats is not None:
-            want_x = side == "dst" or self.proc.update_src_nodes
-            r = self._row_chain(x, lin, side, want_x)
+        if carrier is not None:
+            r = self._row_chain(x, lin, side, want_x=side == "dst" or self.proc.update_src_nodes)
             if r is not None:
                 y, proj = r
-                ln_stats["proj:" + side] = proj
                 # (source rows nobody reads: an empty [N, 0] stand-in keeps the row count the block's graph plumbing looks at)
-                return y if y is not None else x.new_empty((x.shape[0], 0))
-        if ln_stats is not None and x.is_cuda and x.dtype != torch.float32 and self.proc._ln_fold_ok(ln, x):
-            y, stats = padded.with_row_stats(x, lin)
-            if stats is not None:
-                ln_stats[side] = (y, stats)
-            return y
+                return carrier.put(y if y is not None else x.new_empty((x.shape[0], 0)), proj=proj)
+            if self.proc._ln_fold_ok(ln, x):
+                y, stats = padded.with_row_stats(x, lin)
+                return y if stats is None else carrier.put(y, stats=stats)
         return padded(x, lin)
 
     # subclasses: pre_process(x_src_compact, x_dst) -> embedded pair, post_process(x_dst)
@@ -237,19 +228,17 @@ class GraphTransformerBaseMapper(BaseMapper):
             elif not g["all_connected"]:
                 c_src = ops.gather_rows(c_src, g["src_ids32"])
             kwargs["cond"] = (c_src, c_dst)
-        # inference: the embeddings also emit the row statistics of their outputs, and the block folds LayerNorm_src / _dst into
-        # the k|v and q|self GEMMs (no LayerNorm launches on the 40 320-row side)
-        ln_stats = {} if cond is None else None
-        src_proj = kwargs.pop("src_proj", None)  # model glue: (source rows, their k|v projection) computed by the launch that produced the rows
-        xs, xd = self.pre_process((x_src_c, x_dst), ln_stats=ln_stats)
-        if src_proj is not None and ln_stats is not None and src_proj[0] is x_src and xs is x_src:
-            ln_stats["proj:src"] = src_proj[1]
-        tail = self._tail_projection() if (cond is None and "ln_chain" not in kwargs) else None
-        if tail is not None:  # the block's chain launch may run post_process as its trailing projection (layers/block.py)
-            kwargs["ln_chain"] = {"tail_proj": tail}
+        # inference: the embeddings hand the block its projections (or the row statistics of their outputs, and the block folds LayerNorm_src /
+        # _dst into the k|v and q|self GEMMs: no LayerNorm launches on the 40 320-row side); the model glue's carrier may also hold the k|v
+        # projection of the source rows, computed by the launch that produced them, and the block's tail may run post_process
+        carrier = kwargs.pop("carrier", None)
+        if cond is None:
+            carrier = Carrier() if carrier is None else carrier
+            carrier.tail_proj = self._tail_projection()
+        xs, xd = self.pre_process((x_src_c, x_dst), carrier=carrier if cond is None else None)
         (_, x_dst_out), _ = self.proc((xs, xd), g["edge_attr"], g["edge_index"], shard_info, batch_size,
-                                      (xs.shape[0], xd.shape[0]), model_comm_group, edges_are_dst_sorted=True, ln_stats=ln_stats, **kwargs)
-        out_dst = kwargs["ln_chain"].get("tail_out") if tail is not None else None
+                                      (xs.shape[0], xd.shape[0]), model_comm_group, edges_are_dst_sorted=True, carrier=carrier, **kwargs)
+        out_dst = None if carrier is None else carrier.tail_out
         if out_dst is None:
             out_dst = self.post_process(x_dst_out)
         if sharded and not keep_x_dst_sharded:
@@ -304,10 +293,10 @@ class GraphTransformerForwardMapper(GraphTransformerBaseMapper):
         super().__init__(out_channels_dst=None, **kwargs)
         self.emb_nodes_src = self.layer_factory.Linear(self.in_channels_src, self.hidden_dim)
 
-    def pre_process(self, x, ln_stats: Optional[dict] = None):
+    def pre_process(self, x, carrier: Optional[Carrier] = None):
         x_src, x_dst = x
-        return (self._embed(self._emb_src, x_src, self.emb_nodes_src, "src", ln_stats),
-                self._embed(self._emb_dst, x_dst, self.emb_nodes_dst, "dst", ln_stats))
+        return (self._embed(self._emb_src, x_src, self.emb_nodes_src, "src", carrier),
+                self._embed(self._emb_dst, x_dst, self.emb_nodes_dst, "dst", carrier))
 
     def post_process(self, x_dst, **kwargs):
         return x_dst
@@ -332,9 +321,9 @@ class GraphTransformerBackwardMapper(GraphTransformerBaseMapper):
                     if module.bias is not None:
                         nn.init.constant_(module.bias, 0.0)
 
-    def pre_process(self, x, ln_stats: Optional[dict] = None):
+    def pre_process(self, x, carrier: Optional[Carrier] = None):
         x_src, x_dst = x
-        return x_src, self._embed(self._emb_dst, x_dst, self.emb_nodes_dst, "dst", ln_stats)
+        return x_src, self._embed(self._emb_dst, x_dst, self.emb_nodes_dst, "dst", carrier)
 
     def _tail_projection(self):
         if not _TAIL_PROJ or torch.is_grad_enabled():

@@ -13,6 +13,7 @@ from ..distributed.partition import edge_shard_plan, ensure_edges_are_dst_sorted
 from ..distributed.primitives import gather_tensor, scoped_forward
 from ..distributed.shapes import GraphShardInfo
 from .block import GraphConvProcessorBlock, GraphTransformerProcessorBlock
+from .handoff import Carrier
 from .utils import compute_mlp_hidden_dim, load_layer_kernels
 from ..utils.tensors import version
 
@@ -37,15 +38,15 @@ class BaseProcessor(nn.Module):
         self.proc = nn.ModuleList([layer_class(*layer_args, **layer_kwargs) for _ in range(self.num_layers)])
 
     def run_layers(self, data: tuple, *args, last_layer_kwargs: Optional[dict] = None, **kwargs) -> tuple:
-        chain = kwargs.get("ln_chain")
-        if chain is None:
-            chain = kwargs.get("gnn_chain")
+        carrier = kwargs.get("carrier")
         after_last = kwargs.pop("after_last_block", None)  # model glue: the decoder's block, whose source-side projection may ride on the last tail
         for i, layer in enumerate(self.proc):
             extra = last_layer_kwargs if (last_layer_kwargs and i == len(self.proc) - 1) else {}
-            if chain is not None:  # a block's chain launch may compute the NEXT block's LayerNorm + projections (layers/block.py)
-                chain["next_block"] = self.proc[i + 1] if i + 1 < len(self.proc) else after_last
+            if carrier is not None:  # a block's chain launch may compute the NEXT block's LayerNorm + projections (layers/block.py)
+                carrier.next_block = self.proc[i + 1] if i + 1 < len(self.proc) else after_last
             data = layer(*data, *args, **kwargs, **extra)
+        if carrier is not None:
+            carrier.next_block = None
         return data
 
 
@@ -82,7 +83,7 @@ class GraphTransformerProcessor(BaseProcessor):
     def forward(self, x: Tensor, batch_size: int, shard_info: GraphShardInfo, edge_attr: Tensor, edge_index: Tensor,
                 model_comm_group=None, edges_are_dst_sorted: bool = True, *args, **kwargs) -> Tensor:
         size = sum(shard_info.nodes) if shard_info.nodes_are_sharded() else x.shape[0]
-        ln_chain = kwargs.pop("ln_chain", None)  # the encoder's last GEMM may have left the row statistics of x (model glue)
+        carrier = kwargs.pop("carrier", None)  # model glue: the encoder's tail may have left this processor's first projection of x
         latent_skip = kwargs.pop("latent_skip", None)  # model glue: x_latent, added by the LAST block's last GEMM (returns x + skip)
         edge_attr, edge_index = ensure_edges_are_dst_sorted(
             edge_attr, edge_index, edges_are_sharded=shard_info.edges_are_sharded(), model_comm_group=model_comm_group,
@@ -98,7 +99,7 @@ class GraphTransformerProcessor(BaseProcessor):
         x, _ = self.run_layers(
             (x, edge_attr), edge_index=edge_index, shard_info=shard_info, batch_size=batch_size, size=size,
             model_comm_group=model_comm_group, edges_are_dst_sorted=True, halo_cache=self._halo_cache, edge_prep={},
-            ln_chain={} if ln_chain is None else ln_chain,  # row statistics handed from a block's last GEMM to the next block's first (LayerNorm fold)
+            carrier=Carrier() if carrier is None else carrier,
             last_layer_kwargs=None if latent_skip is None else {"extra_residual": latent_skip},
             **kwargs,
         )
@@ -134,5 +135,5 @@ class GNNProcessor(BaseProcessor):
             perm, rows, edge_index, edge_shard_sizes = self._shard_cache[1]
             edge_attr = take_edge_rows(edge_attr, perm, rows)
             shard_info = GraphShardInfo(nodes=shard_info.nodes, edges=edge_shard_sizes)
-        x, _ = self.run_layers((x, edge_attr), edge_index, shard_info, model_comm_group, local_edge_cache=self._local_edge_cache, gnn_chain={}, **kwargs)
+        x, _ = self.run_layers((x, edge_attr), edge_index, shard_info, model_comm_group, local_edge_cache=self._local_edge_cache, carrier=Carrier(), **kwargs)
         return x

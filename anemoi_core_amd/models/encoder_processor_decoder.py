@@ -271,15 +271,16 @@ class AnemoiModelEncProcDec(nn.Module):
         shard_sizes_hidden = get_shard_sizes(x_hidden_latent, 0, model_comm_group)
         x_hidden_latent = shard_tensor(x_hidden_latent, 0, shard_sizes_hidden, model_comm_group)
         latents, skips, data_latents, data_shards = {}, {}, {}, {}
-        # LayerNorm fold across the encoder / processor boundary (inference, one dataset, GraphTransformer on both sides): the
-        # encoder's last GEMM leaves the row statistics the processor's first LayerNorm needs
-        from ..layers.mapper import GraphTransformerForwardMapper
+        # one dataset, GraphTransformer on both sides: one carrier for the forward, so that the encoder's tail can hand the processor's first
+        # block its projection (unsharded) and the last processor block's tail the decoder's block its k|v (layers/handoff.py)
+        from ..layers.handoff import Carrier
+        from ..layers.mapper import GraphTransformerBackwardMapper, GraphTransformerForwardMapper
         from ..layers.processor import GraphTransformerProcessor
 
-        chain_kw = ({"ln_chain": {"next_block": self.processor.proc[0]}} if len(names) == 1 and isinstance(self.encoder[names[0]], GraphTransformerForwardMapper)
-                    and isinstance(self.processor, GraphTransformerProcessor) and model_comm_group is None else
-                    ({"ln_chain": {}} if len(names) == 1 and isinstance(self.encoder[names[0]], GraphTransformerForwardMapper)
-                     and isinstance(self.processor, GraphTransformerProcessor) else {}))
+        carrier = None
+        if len(names) == 1 and isinstance(self.encoder[names[0]], GraphTransformerForwardMapper) and isinstance(self.processor, GraphTransformerProcessor):
+            carrier = Carrier(next_block=self.processor.proc[0] if model_comm_group is None else None)
+        chain_kw = {} if carrier is None else {"carrier": carrier}
         for ds in names:
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
             norm_in, norm_out = (_fused_norm or {}).get(ds, (None, None))
@@ -295,19 +296,14 @@ class AnemoiModelEncProcDec(nn.Module):
         ea, ei, es = self.processor_graph_provider.get_edges(batch_size=batch_size, model_comm_group=model_comm_group)
         # the latent skip (:295-296) rides in the last processor block's last GEMM (GraphTransformer processor), else one add
         fuse_skip = self.latent_skip and isinstance(self.processor, GraphTransformerProcessor)
-        # (one dataset, GraphTransformer decoder, unsharded inference: the decoder block's layer_norm_attention_src + k|v projection of the hidden
-        # rows ride at the end of the last processor block's chain launch, behind the latent skip)
-        from ..layers.mapper import GraphTransformerBackwardMapper
-
+        # (GraphTransformer decoder, unsharded inference: the decoder block's layer_norm_attention_src + k|v projection of the hidden rows ride
+        # at the end of the last processor block's chain launch, behind the latent skip)
         dec0 = self.decoder[names[0]]
-        hand_kv = (_TAIL_KV and fuse_skip and len(names) == 1 and model_comm_group is None and "ln_chain" in chain_kw and isinstance(dec0, GraphTransformerBackwardMapper)
+        hand_kv = (_TAIL_KV and fuse_skip and carrier is not None and model_comm_group is None and isinstance(dec0, GraphTransformerBackwardMapper)
                    and not torch.is_grad_enabled())
         x_latent_proc = self.processor(x=x_latent, batch_size=batch_size, shard_info=GraphShardInfo(nodes=shard_sizes_hidden, edges=es),
                                        edge_attr=ea, edge_index=ei, model_comm_group=model_comm_group, **chain_kw,
                                        **({"latent_skip": x_latent} if fuse_skip else {}), **({"after_last_block": dec0.proc} if hand_kv else {}))
-        src_proj = None
-        if hand_kv and chain_kw["ln_chain"].get("qkvs_x") is x_latent_proc:
-            src_proj = (x_latent_proc, chain_kw["ln_chain"]["qkvs"])
         if self.latent_skip and not fuse_skip:
             if (x_latent_proc.is_cuda and x_latent_proc.dim() == 2 and x_latent_proc.shape == x_latent.shape and x_latent_proc.dtype == x_latent.dtype
                     and not (torch.is_grad_enabled() and (x_latent_proc.requires_grad or x_latent.requires_grad))):
@@ -321,8 +317,7 @@ class AnemoiModelEncProcDec(nn.Module):
             ea, ei, es = self.decoder_graph_provider[ds].get_edges(batch_size=batch_size, model_comm_group=model_comm_group)
             info = BipartiteGraphShardInfo(src_nodes=shard_sizes_hidden, dst_nodes=data_shards[ds], edges=es)
             x_out = self.decoder[ds]((x_latent_proc, data_latents[ds]), batch_size=batch_size, shard_info=info, edge_attr=ea,
-                                     edge_index=ei, model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds],
-                                     **({"src_proj": src_proj} if src_proj is not None else {}))
+                                     edge_index=ei, model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds], **chain_kw)
             x_skip, raw, norm_in, norm_out = skips[ds]
             out[ds] = self._assemble_output(x_out, x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=norm_in, skip_is_raw=raw,
                                             denorm=norm_out)
