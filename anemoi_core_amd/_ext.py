@@ -79,3 +79,7 @@ def _register_fakes() -> None:
     @fake("anemoi_hip::linear_ln_folded")
     def _(x, w_scaled, c, d, stats, eps, act):
         return x.new_empty((x.shape[0], w_scaled.shape[0]))
+
+    @fake("anemoi_hip::window_attention")
+    def _(q, k, v, num_heads, window, scale, softcap, alibi_slopes, batch_size, return_lse):
+        return q.new_empty(q.shape), q.new_empty((q.shape[0] if return_lse else 0, num_heads), dtype=torch.float32)

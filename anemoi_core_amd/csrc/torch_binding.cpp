@@ -231,6 +231,35 @@ Tensor linear_ln_folded(const Tensor& x, const Tensor& w_scaled, const Tensor& c
   return y;
 }
 
+// sliding-window multi-head self-attention over (batch seq) rows                          (anemoi_window_attention_fwd)
+std::tuple<Tensor, Tensor> window_attention(const Tensor& q, const Tensor& k, const Tensor& v, int64_t num_heads, int64_t window, double scale,
+                                            double softcap, const OptTensor& alibi_slopes, int64_t batch_size, bool return_lse) {
+  on_current_device(q);
+  const auto dt = q.scalar_type();
+  const auto dev = q.device();
+  TORCH_CHECK_VALUE(q.dim() == 2 && k.dim() == 2 && v.dim() == 2, "q, k and v must be 2-D [rows, A]");
+  const int64_t rows_ = q.size(0), A = q.size(1);
+  TORCH_CHECK_VALUE(num_heads > 0 && A % num_heads == 0, "channels ", A, " not divisible by heads ", num_heads);
+  const int64_t d = A / num_heads;
+  TORCH_CHECK_VALUE(d == 32 || d == 64 || d == 128, "window_attention: head dimension ", d, " not supported; supported: {32, 64, 128}");
+  TORCH_CHECK_VALUE(k.sizes() == q.sizes() && v.sizes() == q.sizes(), "k and v must have q's shape [", rows_, ", ", A, "]");
+  TORCH_CHECK_VALUE(batch_size > 0 && rows_ % batch_size == 0, "rows ", rows_, " not divisible by batch_size ", batch_size);
+  Tensor out = at::empty({rows_, A}, q.options());
+  Tensor lse = at::empty({return_lse ? rows_ : 0, num_heads}, q.options().dtype(at::kFloat));
+  const Rows rq = rows(q, "q", dt, dev), rk = rows(k, "k", dt, dev), rv = rows(v, "v", dt, dev);
+  const void* slopes = nullptr;
+  if (alibi_slopes.has_value() && alibi_slopes->defined()) {
+    TORCH_CHECK_VALUE(alibi_slopes->device() == dev, "alibi_slopes must be on q's device");
+    slopes = vec(alibi_slopes, "alibi_slopes", num_heads, at::kFloat);
+  }
+  check(anemoi_window_attention_fwd(rq.p, rq.ld, rk.p, rk.ld, rv.p, rv.ld, out.data_ptr(), A, return_lse ? lse.data_ptr<float>() : nullptr,
+                                    (int32_t)batch_size, (int32_t)(rows_ / batch_size), (int32_t)num_heads, (int32_t)d,
+                                    (int32_t)(window < 0 ? -1 : std::min<int64_t>(window, INT32_MAX)), (float)scale, (float)softcap,
+                                    static_cast<const float*>(slopes), dt_of(q), cur_stream()),
+        "window_attention_fwd");
+  return {out, lse};
+}
+
 [[noreturn]] void no_cpu() {
   TORCH_CHECK(false, "anemoi_core_amd kernels run on an MI355X (ROCm) device only; got a CPU tensor. There is no CPU fallback in the product path.");
 }
@@ -247,6 +276,8 @@ TORCH_LIBRARY(anemoi_hip, m) {
         "int n_src, int num_heads, Tensor? addend, bool return_lse) -> (Tensor, Tensor)");
   m.def("linear_with_row_stats(Tensor x, Tensor weight, Tensor? bias, Tensor? residual) -> (Tensor, Tensor)");
   m.def("linear_ln_folded(Tensor x, Tensor w_scaled, Tensor c, Tensor d, Tensor stats, float eps, int act) -> Tensor");
+  m.def("window_attention(Tensor q, Tensor k, Tensor v, int num_heads, int window, float scale, float softcap, Tensor? alibi_slopes, "
+        "int batch_size, bool return_lse) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(anemoi_hip, CUDA, m) {  // the ROCm build of PyTorch dispatches HIP tensors under the CUDA key
@@ -257,10 +288,13 @@ TORCH_LIBRARY_IMPL(anemoi_hip, CUDA, m) {  // the ROCm build of PyTorch dispatch
   m.impl("gt_attention_fused_edge", &gt_attention_fused_edge);
   m.impl("linear_with_row_stats", &linear_with_row_stats);
   m.impl("linear_ln_folded", &linear_ln_folded);
+  m.impl("window_attention", &window_attention);
 }
 
 TORCH_LIBRARY_IMPL(anemoi_hip, CPU, m) {  // fail loudly, like the ctypes path
   m.impl("linear", [](const Tensor&, const Tensor&, const OptTensor&, int64_t, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&,
                       const OptTensor&, const OptTensor&) -> Tensor { no_cpu(); });
   m.impl("layer_norm", [](const Tensor&, const Tensor&, const OptTensor&, double, const OptTensor&) -> Tensor { no_cpu(); });
+  m.impl("window_attention", [](const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, double, double, const OptTensor&, int64_t,
+                                bool) -> std::tuple<Tensor, Tensor> { no_cpu(); });
 }

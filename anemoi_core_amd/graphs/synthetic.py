@@ -25,6 +25,8 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+from typing import Optional
+
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -197,10 +199,10 @@ class SyntheticGraph:
     data_latlon: np.ndarray
     hidden_latlon: np.ndarray
     enc_edge_index: np.ndarray  # data -> hidden
-    proc_edge_index: np.ndarray  # hidden -> hidden
+    proc_edge_index: Optional[np.ndarray]  # hidden -> hidden (None: a graph without processor edges, e.g. for a TransformerProcessor)
     dec_edge_index: np.ndarray  # hidden -> data
     enc_edge_attr: np.ndarray
-    proc_edge_attr: np.ndarray
+    proc_edge_attr: Optional[np.ndarray]
     dec_edge_attr: np.ndarray
     meta: dict = field(default_factory=dict)
 
@@ -214,8 +216,9 @@ class SyntheticGraph:
 
 
 def build_synthetic_graph(data_grid: str = "o96", hidden_resolution: int = 5, *, cutoff_factor: float = 0.6,
-                          max_neighbours: int = 64, decoder_k: int = 3) -> SyntheticGraph:
-    """``data_grid``: "o<n>" (octahedral), "fib<n>" (Fibonacci with n points) or "n320"."""
+                          max_neighbours: int = 64, decoder_k: int = 3, processor_edges: bool = True) -> SyntheticGraph:
+    """``data_grid``: "o<n>" (octahedral), "fib<n>" (Fibonacci with n points) or "n320".  ``processor_edges=False``: no hidden -> hidden
+    edges (the model then gives its processor a NoOpGraphProvider, as a graph without that edge type does in the reference)."""
     g = data_grid.lower()
     if g == "n320":
         data = fibonacci_grid(542080)
@@ -227,7 +230,7 @@ def build_synthetic_graph(data_grid: str = "o96", hidden_resolution: int = 5, *,
         raise ValueError(f"unknown data grid '{data_grid}'")
     hidden, _ = icosphere_latlon(hidden_resolution)
     enc = cutoff_edges(data, hidden, cutoff_factor, max_neighbours)
-    proc = multiscale_edges(hidden_resolution)
+    proc = multiscale_edges(hidden_resolution) if processor_edges else None
     dec = knn_edges(hidden, data, decoder_k)
     return SyntheticGraph(
         data_latlon=data.astype(np.float32),
@@ -236,7 +239,7 @@ def build_synthetic_graph(data_grid: str = "o96", hidden_resolution: int = 5, *,
         proc_edge_index=proc,
         dec_edge_index=dec,
         enc_edge_attr=edge_attributes(data, hidden, enc),
-        proc_edge_attr=edge_attributes(hidden, hidden, proc),
+        proc_edge_attr=None if proc is None else edge_attributes(hidden, hidden, proc),
         dec_edge_attr=edge_attributes(hidden, data, dec),
         meta={"data_grid": data_grid, "hidden_resolution": hidden_resolution},
     )

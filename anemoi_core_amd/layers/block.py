@@ -141,8 +141,161 @@ class TailRoute:
         return "chain2:" + ":".join(str(id(lin)) for lin in self.projs)
 
 
+# ============================================================================================ block tails
+class BlockTail:
+    """The row-local tail of a block - ``x + projection(attn)``, LayerNorm, ``+ MLP`` - on the route ``_tail_route`` picks, shared by the
+    GraphTransformer and Transformer blocks.  A block provides the module handles ``_tail_projection``, ``_tail_ln``, ``_tail_mlp`` and a
+    ``_fused`` weight cache.  The consumers are duck-typed: a next block that takes a ready projection of its input rows has
+    ``_projections_chain_ok`` / ``_chain_projections``; one that folds row statistics into its LayerNorm has ``folds_row_stats``."""
+
+    def _ln_fold_ok(self, ln, x: Tensor) -> bool:
+        """The LayerNorm-fold path: inference, 16-bit, plain affine LayerNorm (see include/anemoi_hip.h)."""
+        return (_LN_FOLD and x.shape[0] >= _LN_FOLD_MIN_ROWS and plain_layer_norm(ln) and x.dtype != torch.float32 and x.is_cuda
+                and not ops._needs_grad(x, ln.weight))
+
+    def _chain_ok(self, ln, x: Tensor, cluster: bool = False) -> bool:
+        """The row-resident chain kernel takes this block's projection / LayerNorm / MLP: inference, 16-bit, 512 channels, plain
+        affine LayerNorm, Linear-GELU-Linear MLP with a hidden width that is a multiple of 512.  ``cluster``: the same question for the
+        cluster chain, which takes the row counts BELOW the chain's gate (and a hidden width of 2048)."""
+        mlp, C = self._tail_mlp, ops.CHAIN_CHANNELS
+        if not (_LAYER_CHAIN and x.is_cuda and x.dtype != torch.float32 and plain_layer_norm(ln)
+                and mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None):
+            return False
+        lin1, lin2 = mlp.mlp[0], mlp.mlp[2]
+        rows = (_CLUSTER_CHAIN and 0 < x.shape[0] < _LAYER_CHAIN_MIN_ROWS and lin1.weight.shape[0] == 4 * C) if cluster else x.shape[0] >= _LAYER_CHAIN_MIN_ROWS
+        return (rows and self._tail_projection.weight.shape == (C, C) and self._tail_projection.bias is not None
+                and lin1.weight.shape[1] == C and lin1.weight.shape[0] % C == 0 and lin2.weight.shape[0] == C
+                and lin1.bias is not None and lin2.bias is not None and inference_in(x, ln, self._tail_projection, mlp))
+
+    def _ready_projection(self, h: Optional[Handoff], x: Tensor, ln, tag: str, lins: list) -> Optional[Tensor]:
+        """The projection of ``x`` a producer handed over: computed already, or from raw rows with the row statistics it left (LayerNorm fold)."""
+        if h is not None and h.proj is None and h.stats is not None and self._ln_fold_ok(ln, x):
+            ws, c, d = self._fused.ln_folded(tag, lins, ln)
+            return ops.linear_ln_folded(x, ws, c, d, h.stats, ln.eps)
+        return None if h is None else h.proj
+
+    def _tail_route(self, attn: Tensor, x_skip: Tensor, cond: Optional[Tensor], carrier: Optional[Carrier], extra: Optional[Tensor] = None,
+                    shares: Optional[tuple] = None) -> TailRoute:
+        """Every gate of a block tail, evaluated here and nowhere else.  ``shares`` (a sharded block at inference): the row counts of ALL ranks -
+        the halo payload of the next exchange must be the same on every rank."""
+        ln, mlp = self._tail_ln, self._tail_mlp
+        nxt = None if carrier is None else carrier.next_block
+        cluster = cond is None and self._chain_ok(ln, attn, cluster=True)
+        if (cond is None and (cluster or self._chain_ok(ln, attn)) and attn.shape == x_skip.shape
+                and (extra is None or extra.shape == x_skip.shape)):
+            kind, hidden = "cluster" if cluster else "chain2", mlp.mlp[0].weight.shape[0]
+            supported = ops.gt_cluster_chain_supported if cluster else ops.gt_layer_chain2_supported
+            halo = shares is not None
+            # the NEXT consumer of this tail's output whose LayerNorm + projections ride at the end of the launch: the next processor block
+            # (q|k|v|self), or - behind the LAST processor block and the latent skip - the decoder's block (k|v of its source rows).  A sharded
+            # block's k|v need the halo rows: only the cluster chain, on every rank, hands them over
+            to_mapper = isinstance(nxt, GraphTransformerMapperBlock)
+            nb = nxt if (nxt is not None and (not cluster and not halo if to_mapper else extra is None) and hasattr(nxt, "_projections_chain_ok")
+                         and nxt._projections_chain_ok(x_skip)) else None
+            if halo and not (_CLUSTER_HALO and cluster and getattr(nb, "shard_strategy", None) == "edges" and shares
+                             and all(0 < n < _LAYER_CHAIN_MIN_ROWS for n in shares)):
+                nb = None
+            if nb is not None:
+                lnq, projs = nb._chain_projections(halo)
+                if supported(attn, hidden, sum(p.out_features for p in projs)):
+                    return TailRoute(kind, nb, tuple(projs), lnq, halo=halo)
+            # a decoder's node_data_extractor (LayerNorm + Linear(512, out), layers/mapper.py) as the chain launch's NARROW trailing projection:
+            # the tail's output rows are then neither written nor read back, and two launches disappear
+            if nb is None and carrier is not None and carrier.tail_proj is not None and extra is None and not cluster:
+                ln_t, lin_t = carrier.tail_proj
+                o_pad = (lin_t.out_features + 127) // 128 * 128
+                if (o_pad < ops.CHAIN_CHANNELS and lin_t.in_features == ops.CHAIN_CHANNELS and plain_layer_norm(ln_t)
+                        and supported(attn, hidden, o_pad) and inference_in(attn, ln_t, lin_t)):
+                    return TailRoute(kind, projs=(lin_t,), lnq=ln_t, tail_width=o_pad)
+            if supported(attn, hidden, 0):
+                return TailRoute(kind)
+            # (a hidden width whose vectors do not fit the kernel's LDS region: the GEMM launches)
+        if mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None and self._ln_fold_ok(ln, attn):
+            # the last GEMM leaves row statistics only for a reader: the next processor block, unsharded
+            reader = getattr(nxt, "folds_row_stats", False) and shares is None and extra is None
+            return TailRoute("lnfold", nxt if reader else None)
+        return TailRoute("plain")
+
+    def _post_attention(self, attn_plus_self: Tensor, x_skip: Tensor, cond: Optional[Tensor] = None, carrier: Optional[Carrier] = None,
+                        extra: Optional[Tensor] = None, halo=None) -> Tensor:
+        """projection + residual, LayerNorm, MLP + residual on the route ``_tail_route`` picks.  ``extra`` (last block of a processor): the model's
+        latent skip (encoder_processor_decoder.py:295-296), a second residual.  ``halo`` (sharded block at inference: (HaloPlan, group)): where the
+        cluster chain takes every rank's tail it also writes the NEXT block's q | self of the local rows and their k | v into the head of the
+        [local + halo, 2A] buffer of the next exchange: the owners' k | v rows cross the wire (2 KiB per row instead of the 1-KiB LayerNorm'd row
+        of the reference, layers/block.py:1159-1172 - the exchange is latency-bound, SURVEY 8e) and no rank projects a halo row again."""
+        if extra is not None and (ops._needs_grad(attn_plus_self, x_skip, extra, self._tail_projection.weight) or extra.shape != x_skip.shape):
+            return self._post_attention(attn_plus_self, x_skip, cond) + extra
+        r = self._tail_route(attn_plus_self, x_skip, cond, carrier, extra, None if halo is None else halo[0].shares)
+        if r.kind in ("chain2", "cluster"):
+            return self._tail_chain(r, attn_plus_self, x_skip, carrier, extra, halo)
+        y = self._tail_lnfold(r, attn_plus_self, x_skip, carrier, extra) if r.kind == "lnfold" else None
+        if y is not None:
+            return y
+        out = ops.linear(attn_plus_self, self._tail_projection.weight, self._tail_projection.bias, residual=x_skip)
+        y = self._tail_mlp(apply_layer_norm(self._tail_ln, out, cond), residual=out)
+        return y if extra is None else y + extra
+
+    def _tail_chain(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor], halo) -> Tensor:
+        """The tail as ONE chain launch (the LayerNorms' affine parts folded into weight images built once per parameter version), with the
+        route's trailing projection."""
+        ln, lin1, lin2 = self._tail_ln, self._tail_mlp.mlp[0], self._tail_mlp.mlp[2]
+        hidden, lnq = lin1.weight.shape[0], r.lnq
+        q_out = r.tail_width or sum(lin.out_features for lin in r.projs)
+        params = [self._tail_projection.weight, self._tail_projection.bias, ln.weight, ln.bias, lin1.weight, lin1.bias, lin2.weight, lin2.bias]
+        params += [q for lin in r.projs for q in (lin.weight, lin.bias)] + ([] if lnq is None else [lnq.weight, lnq.bias])
+
+        def build():
+            w1g, d1 = ops.fold_layer_norm(lin1.weight, lin1.bias, ln.weight, ln.bias)
+            parts, wqg = [self._tail_projection.bias.float(), d1, lin2.bias.float()], None
+            if r.projs:  # (a narrow extractor: zero rows up to its padded width - the padded output columns are zeros)
+                pad = q_out - sum(lin.out_features for lin in r.projs)
+                wq = torch.nn.functional.pad(torch.cat([lin.weight for lin in r.projs], dim=0), (0, 0, 0, pad))
+                bq = torch.nn.functional.pad(torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features)
+                                                        for lin in r.projs]), (0, pad))
+                wq, dq = ops.fold_layer_norm(wq, bq, lnq.weight, lnq.bias)
+                wqg = ops.pack_weight_frag(wq)
+                parts.append(dq)
+            return (ops.pack_weight_frag(self._tail_projection.weight), ops.pack_weight_frag(w1g), ops.pack_weight_frag(lin2.weight),
+                    torch.cat(parts).to(lin1.weight.dtype).contiguous(), wqg)
+
+        wp, w1g, w2, vec, wqg = self._fused.derived(r.weights_tag, params, build)
+        kw = dict(extra=extra, wqg=wqg, q_out_features=q_out, lnq_eps=1e-5 if lnq is None else lnq.eps)
+        if r.tail_width:
+            _, q_t = ops.gt_layer_chain2(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, want_x_out=False, **kw)
+            carrier.tail_out = q_t[:, :r.projs[0].out_features]  # (a strided [N, out] view, as the mapper's own GEMM returns)
+            return q_t
+        buf = None
+        if r.halo:
+            plan, group = halo
+            nl, width = x_skip.shape[0], 2 * r.next_block.attn_channels
+            buf = comm.recv_buffer(nl, plan.send_counts, plan.recv_counts, width, x_skip.dtype, x_skip.device, group)
+            kw.update(q_out2=buf[:nl], q_split=width // ops.CHAIN_CHANNELS)
+        res = (ops.gt_cluster_chain if r.kind == "cluster" else ops.gt_layer_chain2)(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, **kw)
+        return res if r.next_block is None else carrier.put(res[0], proj=res[1], kv=buf)
+
+    def _tail_lnfold(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor]) -> Optional[Tensor]:
+        """The tail as GEMM launches with the LayerNorm folded into the MLP's first: the projection GEMM emits the row statistics of its output.
+        None where the shapes are not eligible."""
+        ln, lin1, lin2 = self._tail_ln, self._tail_mlp.mlp[0], self._tail_mlp.mlp[2]
+        first = ops.linear_with_row_stats(attn, self._tail_projection.weight, self._tail_projection.bias, x_skip)
+        if first is None:
+            return None
+        out, stats = first
+        ws, c, d = self._fused.ln_folded("mlp1", [lin1], ln)
+        h = ops.linear_ln_folded(out, ws, c, d, stats, ln.eps, act="gelu")
+        if h is None:
+            h = ops.linear(ops.layer_norm(out, ln.weight, ln.bias, ln.eps), lin1.weight, lin1.bias, act="gelu")
+        if extra is not None:  # second residual = the gather-add epilogue with the identity index
+            return ops.linear(h, lin2.weight, lin2.bias, residual=out, g1=extra, idx1=_identity_index(extra))
+        last = ops.linear_with_row_stats(h, lin2.weight, lin2.bias, out) if r.next_block is not None else None
+        if last is not None:  # the next block's first LayerNorm folds these statistics
+            return carrier.put(last[0], stats=last[1])
+        return ops.linear(h, lin2.weight, lin2.bias, residual=out)
+
+
+
 # ============================================================================================ GraphTransformer blocks
-class GraphTransformerBaseBlock(BaseBlock):
+class GraphTransformerBaseBlock(BlockTail, BaseBlock):
     def __init__(self, *, in_channels: int, hidden_dim: int, out_channels: int, num_heads: int, edge_dim: int,
                  bias: bool = True, qk_norm: bool = False, mlp_implementation: str = "mlp", update_src_nodes: bool = False,
                  layer_kernels, attn_channels: Optional[int] = None, graph_attention_backend: str = "hip",
@@ -332,24 +485,17 @@ class GraphTransformerBaseBlock(BaseBlock):
         back = comm.all_to_all_rows(o, dst_sizes, [n_loc] * P, group)  # [P*n_loc, Hl*C]: block r = heads of rank r
         return back.reshape(P, n_loc, Hl * C).permute(1, 0, 2).reshape(n_loc, A)
 
-    def _ln_fold_ok(self, ln, x: Tensor) -> bool:
-        """The LayerNorm-fold path: inference, 16-bit, plain affine LayerNorm (see include/anemoi_hip.h)."""
-        return (_LN_FOLD and x.shape[0] >= _LN_FOLD_MIN_ROWS and plain_layer_norm(ln) and x.dtype != torch.float32 and x.is_cuda
-                and not ops._needs_grad(x, ln.weight))
+    @property
+    def _tail_projection(self):
+        return self.projection
 
-    def _chain_ok(self, ln, x: Tensor, cluster: bool = False) -> bool:
-        """The row-resident chain kernel takes this block's projection / LayerNorm / MLP: inference, 16-bit, 512 channels, plain
-        affine LayerNorm, Linear-GELU-Linear MLP with a hidden width that is a multiple of 512.  ``cluster``: the same question for the
-        cluster chain, which takes the row counts BELOW the chain's gate (and a hidden width of 2048)."""
-        mlp, C = self.node_dst_mlp, ops.CHAIN_CHANNELS
-        if not (_LAYER_CHAIN and x.is_cuda and x.dtype != torch.float32 and plain_layer_norm(ln)
-                and mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None):
-            return False
-        lin1, lin2 = mlp.mlp[0], mlp.mlp[2]
-        rows = (_CLUSTER_CHAIN and 0 < x.shape[0] < _LAYER_CHAIN_MIN_ROWS and lin1.weight.shape[0] == 4 * C) if cluster else x.shape[0] >= _LAYER_CHAIN_MIN_ROWS
-        return (rows and self.projection.weight.shape == (C, C) and self.projection.bias is not None
-                and lin1.weight.shape[1] == C and lin1.weight.shape[0] % C == 0 and lin2.weight.shape[0] == C
-                and lin1.bias is not None and lin2.bias is not None and inference_in(x, ln, self.projection, mlp))
+    @property
+    def _tail_ln(self):
+        return self.layer_norm_mlp_dst
+
+    @property
+    def _tail_mlp(self):
+        return self.node_dst_mlp
 
     def _chain_projections(self, halo: bool = False) -> tuple:
         """(LayerNorm, Linears) of this block's fused projection of its input rows in the order a chain launch writes their columns:
@@ -364,130 +510,6 @@ class GraphTransformerBaseBlock(BaseBlock):
         return (plain_layer_norm(ln) and not self.qk_norm and x.shape[1] == ops.CHAIN_CHANNELS
                 and sum(p.out_features for p in projs) % ops.CHAIN_CHANNELS == 0 and projs[0].weight.shape[1] == ops.CHAIN_CHANNELS
                 and inference_in(x, ln, *projs))
-
-    def _ready_projection(self, h: Optional[Handoff], x: Tensor, ln, tag: str, lins: list) -> Optional[Tensor]:
-        """The projection of ``x`` a producer handed over: computed already, or from raw rows with the row statistics it left (LayerNorm fold)."""
-        if h is not None and h.proj is None and h.stats is not None and self._ln_fold_ok(ln, x):
-            ws, c, d = self._fused.ln_folded(tag, lins, ln)
-            return ops.linear_ln_folded(x, ws, c, d, h.stats, ln.eps)
-        return None if h is None else h.proj
-
-    def _tail_route(self, attn: Tensor, x_skip: Tensor, cond: Optional[Tensor], carrier: Optional[Carrier], extra: Optional[Tensor] = None,
-                    shares: Optional[tuple] = None) -> TailRoute:
-        """Every gate of a block tail, evaluated here and nowhere else.  ``shares`` (a sharded block at inference): the row counts of ALL ranks -
-        the halo payload of the next exchange must be the same on every rank."""
-        ln, mlp = self.layer_norm_mlp_dst, self.node_dst_mlp
-        nxt = None if carrier is None else carrier.next_block
-        cluster = cond is None and self._chain_ok(ln, attn, cluster=True)
-        if (cond is None and (cluster or self._chain_ok(ln, attn)) and attn.shape == x_skip.shape
-                and (extra is None or extra.shape == x_skip.shape)):
-            kind, hidden = "cluster" if cluster else "chain2", mlp.mlp[0].weight.shape[0]
-            supported = ops.gt_cluster_chain_supported if cluster else ops.gt_layer_chain2_supported
-            halo = shares is not None
-            # the NEXT consumer of this tail's output whose LayerNorm + projections ride at the end of the launch: the next processor block
-            # (q|k|v|self), or - behind the LAST processor block and the latent skip - the decoder's block (k|v of its source rows).  A sharded
-            # block's k|v need the halo rows: only the cluster chain, on every rank, hands them over
-            to_mapper = isinstance(nxt, GraphTransformerMapperBlock)
-            nb = nxt if nxt is not None and (not cluster and not halo if to_mapper else extra is None) and nxt._projections_chain_ok(x_skip) else None
-            if halo and not (_CLUSTER_HALO and cluster and getattr(nb, "shard_strategy", None) == "edges" and shares
-                             and all(0 < n < _LAYER_CHAIN_MIN_ROWS for n in shares)):
-                nb = None
-            if nb is not None:
-                lnq, projs = nb._chain_projections(halo)
-                if supported(attn, hidden, sum(p.out_features for p in projs)):
-                    return TailRoute(kind, nb, tuple(projs), lnq, halo=halo)
-            # a decoder's node_data_extractor (LayerNorm + Linear(512, out), layers/mapper.py) as the chain launch's NARROW trailing projection:
-            # the tail's output rows are then neither written nor read back, and two launches disappear
-            if nb is None and carrier is not None and carrier.tail_proj is not None and extra is None and not cluster:
-                ln_t, lin_t = carrier.tail_proj
-                o_pad = (lin_t.out_features + 127) // 128 * 128
-                if (o_pad < ops.CHAIN_CHANNELS and lin_t.in_features == ops.CHAIN_CHANNELS and plain_layer_norm(ln_t)
-                        and supported(attn, hidden, o_pad) and inference_in(attn, ln_t, lin_t)):
-                    return TailRoute(kind, projs=(lin_t,), lnq=ln_t, tail_width=o_pad)
-            if supported(attn, hidden, 0):
-                return TailRoute(kind)
-            # (a hidden width whose vectors do not fit the kernel's LDS region: the GEMM launches)
-        if mlp.mlp_implementation == "mlp" and len(mlp.mlp) == 3 and mlp.layer_norm is None and self._ln_fold_ok(ln, attn):
-            # the last GEMM leaves row statistics only for a reader: the next processor block, unsharded
-            reader = isinstance(nxt, GraphTransformerProcessorBlock) and shares is None and extra is None
-            return TailRoute("lnfold", nxt if reader else None)
-        return TailRoute("plain")
-
-    def _post_attention(self, attn_plus_self: Tensor, x_skip: Tensor, cond: Optional[Tensor] = None, carrier: Optional[Carrier] = None,
-                        extra: Optional[Tensor] = None, halo=None) -> Tensor:
-        """projection + residual, LayerNorm, MLP + residual on the route ``_tail_route`` picks.  ``extra`` (last block of a processor): the model's
-        latent skip (encoder_processor_decoder.py:295-296), a second residual.  ``halo`` (sharded block at inference: (HaloPlan, group)): where the
-        cluster chain takes every rank's tail it also writes the NEXT block's q | self of the local rows and their k | v into the head of the
-        [local + halo, 2A] buffer of the next exchange: the owners' k | v rows cross the wire (2 KiB per row instead of the 1-KiB LayerNorm'd row
-        of the reference, layers/block.py:1159-1172 - the exchange is latency-bound, SURVEY 8e) and no rank projects a halo row again."""
-        if extra is not None and (ops._needs_grad(attn_plus_self, x_skip, extra, self.projection.weight) or extra.shape != x_skip.shape):
-            return self._post_attention(attn_plus_self, x_skip, cond) + extra
-        r = self._tail_route(attn_plus_self, x_skip, cond, carrier, extra, None if halo is None else halo[0].shares)
-        if r.kind in ("chain2", "cluster"):
-            return self._tail_chain(r, attn_plus_self, x_skip, carrier, extra, halo)
-        y = self._tail_lnfold(r, attn_plus_self, x_skip, carrier, extra) if r.kind == "lnfold" else None
-        if y is not None:
-            return y
-        out = ops.linear(attn_plus_self, self.projection.weight, self.projection.bias, residual=x_skip)
-        y = self.node_dst_mlp(apply_layer_norm(self.layer_norm_mlp_dst, out, cond), residual=out)
-        return y if extra is None else y + extra
-
-    def _tail_chain(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor], halo) -> Tensor:
-        """The tail as ONE chain launch (the LayerNorms' affine parts folded into weight images built once per parameter version), with the
-        route's trailing projection."""
-        ln, lin1, lin2 = self.layer_norm_mlp_dst, self.node_dst_mlp.mlp[0], self.node_dst_mlp.mlp[2]
-        hidden, lnq = lin1.weight.shape[0], r.lnq
-        q_out = r.tail_width or sum(lin.out_features for lin in r.projs)
-        params = [self.projection.weight, self.projection.bias, ln.weight, ln.bias, lin1.weight, lin1.bias, lin2.weight, lin2.bias]
-        params += [q for lin in r.projs for q in (lin.weight, lin.bias)] + ([] if lnq is None else [lnq.weight, lnq.bias])
-
-        def build():
-            w1g, d1 = ops.fold_layer_norm(lin1.weight, lin1.bias, ln.weight, ln.bias)
-            parts, wqg = [self.projection.bias.float(), d1, lin2.bias.float()], None
-            if r.projs:  # (a narrow extractor: zero rows up to its padded width - the padded output columns are zeros)
-                pad = q_out - sum(lin.out_features for lin in r.projs)
-                wq = torch.nn.functional.pad(torch.cat([lin.weight for lin in r.projs], dim=0), (0, 0, 0, pad))
-                bq = torch.nn.functional.pad(torch.cat([lin.bias if lin.bias is not None else lin.weight.new_zeros(lin.out_features)
-                                                        for lin in r.projs]), (0, pad))
-                wq, dq = ops.fold_layer_norm(wq, bq, lnq.weight, lnq.bias)
-                wqg = ops.pack_weight_frag(wq)
-                parts.append(dq)
-            return (ops.pack_weight_frag(self.projection.weight), ops.pack_weight_frag(w1g), ops.pack_weight_frag(lin2.weight),
-                    torch.cat(parts).to(lin1.weight.dtype).contiguous(), wqg)
-
-        wp, w1g, w2, vec, wqg = self._fused.derived(r.weights_tag, params, build)
-        kw = dict(extra=extra, wqg=wqg, q_out_features=q_out, lnq_eps=1e-5 if lnq is None else lnq.eps)
-        if r.tail_width:
-            _, q_t = ops.gt_layer_chain2(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, want_x_out=False, **kw)
-            carrier.tail_out = q_t[:, :r.projs[0].out_features]  # (a strided [N, out] view, as the mapper's own GEMM returns)
-            return q_t
-        buf = None
-        if r.halo:
-            plan, group = halo
-            nl, width = x_skip.shape[0], 2 * r.next_block.attn_channels
-            buf = comm.recv_buffer(nl, plan.send_counts, plan.recv_counts, width, x_skip.dtype, x_skip.device, group)
-            kw.update(q_out2=buf[:nl], q_split=width // ops.CHAIN_CHANNELS)
-        res = (ops.gt_cluster_chain if r.kind == "cluster" else ops.gt_layer_chain2)(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, **kw)
-        return res if r.next_block is None else carrier.put(res[0], proj=res[1], kv=buf)
-
-    def _tail_lnfold(self, r: TailRoute, attn: Tensor, x_skip: Tensor, carrier: Optional[Carrier], extra: Optional[Tensor]) -> Optional[Tensor]:
-        """The tail as GEMM launches with the LayerNorm folded into the MLP's first: the projection GEMM emits the row statistics of its output.
-        None where the shapes are not eligible."""
-        ln, lin1, lin2 = self.layer_norm_mlp_dst, self.node_dst_mlp.mlp[0], self.node_dst_mlp.mlp[2]
-        first = ops.linear_with_row_stats(attn, self.projection.weight, self.projection.bias, x_skip)
-        if first is None:
-            return None
-        out, stats = first
-        ws, c, d = self._fused.ln_folded("mlp1", [lin1], ln)
-        h = ops.linear_ln_folded(out, ws, c, d, stats, ln.eps, act="gelu")
-        if h is None:
-            h = ops.linear(ops.layer_norm(out, ln.weight, ln.bias, ln.eps), lin1.weight, lin1.bias, act="gelu")
-        if extra is not None:  # second residual = the gather-add epilogue with the identity index
-            return ops.linear(h, lin2.weight, lin2.bias, residual=out, g1=extra, idx1=_identity_index(extra))
-        last = ops.linear_with_row_stats(h, lin2.weight, lin2.bias, out) if r.next_block is not None else None
-        if last is not None:  # the next block's first LayerNorm folds these statistics
-            return carrier.put(last[0], stats=last[1])
-        return ops.linear(h, lin2.weight, lin2.bias, residual=out)
 
 
 class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
@@ -565,6 +587,8 @@ class GraphTransformerMapperBlock(GraphTransformerBaseBlock):
 class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
     """Hidden-mesh block (block.py:1032-1273).  With a model-parallel group the LayerNorm'd rows of cut edges are
     exchanged once per layer (halo), k/v are computed on local+halo rows and attention runs on the relabelled graph."""
+
+    folds_row_stats = True  # a previous tail may leave the row statistics of this block's input for its LayerNorm fold (BlockTail)
 
     def __init__(self, *, in_channels: int, hidden_dim: int, out_channels: int, num_heads: int, edge_dim: int,
                  bias: bool = True, qk_norm: bool = False, mlp_implementation: str = "mlp", update_src_nodes: bool = False,
@@ -686,6 +710,74 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
         qkvs = ops.linear(xn, w, b)
         out = self._heads_attention(qkvs[:, :A], qkvs[:, A:2 * A], qkvs[:, 2 * A:3 * A], ea_full, ei_full, sizes, sizes, group, train)
         return self._post_attention(out + qkvs[:, 3 * A:], x, cond, extra=extra)
+
+
+# ============================================================================================ Transformer blocks
+class TransformerProcessorBlock(BlockTail, BaseBlock):
+    """Transformer block (reference block.py:123-196): ``x = x + projection(MHSA(LN_att(x)))``, ``x = x + MLP(LN_mlp(x))``.  Inference path:
+    LayerNorm + q|k|v as one GEMM (or handed over by the previous tail), the window-attention kernel reading the column slices in place, and
+    the tail on the route ``BlockTail._tail_route`` picks - the GraphTransformer tail without the ``lin_self`` term."""
+
+    folds_row_stats = True
+
+    def __init__(self, *, num_channels: int, hidden_dim: int, num_heads: int, window_size: Optional[int], layer_kernels,
+                 attn_channels: Optional[int] = None, dropout_p: float = 0.0, qk_norm: bool = False,
+                 attention_implementation: str = "flash_attention", mlp_implementation: str = "mlp", softcap: Optional[float] = None,
+                 use_alibi_slopes: bool = False, use_rotary_embeddings: bool = False):
+        super().__init__()
+        from .attention import MultiHeadSelfAttention
+
+        self.layer_norm_attention = layer_kernels.LayerNorm(normalized_shape=num_channels)
+        self.layer_norm_mlp = layer_kernels.LayerNorm(normalized_shape=num_channels)
+        self.attention = MultiHeadSelfAttention(num_heads=num_heads, embed_dim=num_channels, attn_channels=attn_channels, window_size=window_size,
+                                                qkv_bias=False, is_causal=False, qk_norm=qk_norm, dropout_p=dropout_p, layer_kernels=layer_kernels,
+                                                attention_implementation=attention_implementation, softcap=softcap,
+                                                use_alibi_slopes=use_alibi_slopes, use_rotary_embeddings=use_rotary_embeddings)
+        self.mlp = MLP(in_features=num_channels, hidden_dim=hidden_dim, out_features=num_channels, layer_kernels=layer_kernels,
+                       n_extra_layers=0, layer_norm=False, mlp_implementation=mlp_implementation)
+        self._fused = _FusedWeights()
+
+    @property
+    def _tail_projection(self):
+        return self.attention.projection
+
+    @property
+    def _tail_ln(self):
+        return self.layer_norm_mlp
+
+    @property
+    def _tail_mlp(self):
+        return self.mlp
+
+    def _chain_projections(self, halo: bool = False) -> tuple:
+        """(LayerNorm, Linears) of this block's q|k|v projection of its input rows, in the order a chain launch writes their columns."""
+        att = self.attention
+        return self.layer_norm_attention, [att.lin_q, att.lin_k, att.lin_v]
+
+    def _projections_chain_ok(self, x: Tensor) -> bool:
+        """LayerNorm + q|k|v of this block can ride at the end of the chain launch that produces ``x`` (with qk_norm they cannot: the same
+        rule as the GraphTransformer block's)."""
+        ln, projs = self._chain_projections()
+        return (plain_layer_norm(ln) and not self.attention.qk_norm and x.shape[1] == ops.CHAIN_CHANNELS
+                and sum(p.out_features for p in projs) % ops.CHAIN_CHANNELS == 0 and projs[0].weight.shape[1] == ops.CHAIN_CHANNELS
+                and inference_in(x, ln, *projs))
+
+    def forward(self, x: Tensor, shard_info: GraphShardInfo, batch_size: int, model_comm_group=None, cond: Optional[Tensor] = None,
+                **layer_kwargs) -> tuple:
+        from .attention import forbid_autograd
+
+        att = self.attention
+        forbid_autograd(self, x, cond, dropout_p=att.dropout_p)
+        carrier, extra = layer_kwargs.get("carrier"), layer_kwargs.get("extra_residual")
+        ln, A = self.layer_norm_attention, att.attn_channels
+        lins = [att.lin_q, att.lin_k, att.lin_v]
+        h = None if carrier is None else carrier.take(x)  # what the launch that produced x left for this block
+        qkv = self._ready_projection(h, x, ln, "qkv", lins) if cond is None else None
+        if qkv is None:
+            w, b = self._fused.get("qkv", lins)
+            qkv = ops.linear(apply_layer_norm(ln, x, cond), w, None if att.lin_q.bias is None else b)
+        o = att.attend(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], batch_size, shard_info.nodes, model_comm_group)
+        return (self._post_attention(o, x, cond, carrier, extra),)
 
 
 class HaloPlan:

@@ -12,7 +12,7 @@ from torch import Tensor, nn
 from ..distributed.partition import edge_shard_plan, ensure_edges_are_dst_sorted, sort_edge_index_by_dst, take_edge_rows
 from ..distributed.primitives import gather_tensor, scoped_forward
 from ..distributed.shapes import GraphShardInfo
-from .block import GraphConvProcessorBlock, GraphTransformerProcessorBlock
+from .block import GraphConvProcessorBlock, GraphTransformerProcessorBlock, TransformerProcessorBlock
 from .handoff import Carrier
 from .utils import compute_mlp_hidden_dim, load_layer_kernels
 from ..utils.tensors import version
@@ -103,6 +103,45 @@ class GraphTransformerProcessor(BaseProcessor):
             last_layer_kwargs=None if latent_skip is None else {"extra_residual": latent_skip},
             **kwargs,
         )
+        return x
+
+
+class TransformerProcessor(BaseProcessor):
+    """Stack of sliding-window self-attention blocks over the hidden rows (reference processor.py:204-316).  Inference only (the window
+    attention has no backward kernel yet).  The graph arguments it is given (``edge_attr``, ``edge_index``, ``edge_dim``) are ignored, as
+    in the reference; so is ``use_rotary_embeddings``, which the reference accepts but never passes to its blocks."""
+
+    def __init__(self, *, num_layers: int, num_channels: int, num_chunks: int, num_heads: int, mlp_hidden_ratio: float,
+                 attn_channels: Optional[int] = None, qk_norm: bool = False, dropout_p: float = 0.0,
+                 attention_implementation: str = "flash_attention", mlp_implementation: str = "mlp", softcap: Optional[float] = None,
+                 use_alibi_slopes: bool = False, window_size: Optional[int] = None, cpu_offload: bool = False, layer_kernels=None,
+                 **kwargs) -> None:
+        super().__init__(num_layers=num_layers, num_channels=num_channels, num_chunks=num_chunks, cpu_offload=cpu_offload,
+                         layer_kernels=layer_kernels, **kwargs)
+        self.build_layers(
+            TransformerProcessorBlock,
+            num_channels=num_channels,
+            hidden_dim=compute_mlp_hidden_dim(num_channels, mlp_hidden_ratio),
+            attn_channels=attn_channels,
+            num_heads=num_heads,
+            qk_norm=qk_norm,
+            window_size=window_size,
+            layer_kernels=self.layer_factory,
+            dropout_p=dropout_p,
+            attention_implementation=attention_implementation,
+            mlp_implementation=mlp_implementation,
+            softcap=softcap,
+            use_alibi_slopes=use_alibi_slopes,
+        )
+
+    @scoped_forward
+    def forward(self, x: Tensor, batch_size: int, shard_info: GraphShardInfo, edge_attr: Optional[Tensor] = None,
+                edge_index: Optional[Tensor] = None, model_comm_group=None, *args, **kwargs) -> Tensor:
+        carrier = kwargs.pop("carrier", None)
+        latent_skip = kwargs.pop("latent_skip", None)  # model glue: x_latent, added by the LAST block's tail (returns x + skip)
+        kwargs.pop("edges_are_dst_sorted", None)
+        (x,) = self.run_layers((x,), shard_info, batch_size, model_comm_group=model_comm_group, carrier=Carrier() if carrier is None else carrier,
+                               last_layer_kwargs=None if latent_skip is None else {"extra_residual": latent_skip}, **kwargs)
         return x
 
 

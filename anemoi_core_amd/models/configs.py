@@ -24,12 +24,23 @@ def make_data_indices(n_vars_in, n_prog):
     return {"data": ns}
 
 
-def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="anemoi.models.layers"):
+def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="anemoi.models.layers", window_size=512):
     """Same nested config the reference model is built from (tests/golden/make_golden.py); by default it even carries
-    the REFERENCE's ``_target_`` strings, which the model retargets to the MI355X classes."""
+    the REFERENCE's ``_target_`` strings, which the model retargets to the MI355X classes.  ``kind``: "gt", "gnn" or "transformer"
+    (GraphTransformer mappers around a TransformerProcessor with ``window_size``, the reference's transformer.yaml; its graph needs no
+    hidden -> hidden edges)."""
     common = dict(cpu_offload=False, gradient_checkpointing=False, layer_kernels=None, trainable_size=trainable,
                   sub_graph_edge_attributes=["edge_length", "edge_dirs"])
-    if kind == "gt":
+    if kind == "transformer":
+        common.update(num_heads=num_heads, mlp_hidden_ratio=4, qk_norm=False, mlp_implementation="mlp")
+        mapper = dict(common, shard_strategy="edges", graph_attention_backend="triton", edge_pre_mlp=False)
+        enc = dict(mapper, _target_=f"{prefix}.mapper.GraphTransformerForwardMapper", num_chunks=2)
+        dec = dict(mapper, _target_=f"{prefix}.mapper.GraphTransformerBackwardMapper", num_chunks=2, initialise_data_extractor_zero=False)
+        proc = dict(common, _target_=f"{prefix}.processor.TransformerProcessor", num_chunks=1, num_layers=num_layers, window_size=window_size,
+                    dropout_p=0.0, attention_implementation="flash_attention", softcap=0.0, use_alibi_slopes=False, use_rotary_embeddings=False)
+        proc.pop("sub_graph_edge_attributes")
+        proc.pop("trainable_size")
+    elif kind == "gt":
         common.update(num_heads=num_heads, mlp_hidden_ratio=4, qk_norm=False, shard_strategy="edges",
                       graph_attention_backend="pyg", edge_pre_mlp=False)
         enc = dict(common, _target_=f"{prefix}.mapper.GraphTransformerForwardMapper", num_chunks=2)

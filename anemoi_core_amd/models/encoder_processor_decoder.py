@@ -50,12 +50,17 @@ def _graph_views(graph_data):
         nodes = {"data": torch.as_tensor(g.data_latlon), "hidden": torch.as_tensor(g.hidden_latlon)}
         mk = lambda ei, ea: {"edge_index": torch.as_tensor(ei), "edge_length": torch.as_tensor(ea[:, :1]), "edge_dirs": torch.as_tensor(ea[:, 1:])}  # noqa: E731
         edges = {("data", "to", "hidden"): mk(g.enc_edge_index, g.enc_edge_attr),
-                 ("hidden", "to", "hidden"): mk(g.proc_edge_index, g.proc_edge_attr),
+                 ("hidden", "to", "hidden"): None if g.proc_edge_index is None else mk(g.proc_edge_index, g.proc_edge_attr),
                  ("hidden", "to", "data"): mk(g.dec_edge_index, g.dec_edge_attr)}
         return nodes, edges
 
     class _Edges(dict):
         def __missing__(self, key):
+            # an edge type the graph does not have (e.g. no hidden -> hidden edges for a TransformerProcessor): None, so that the
+            # provider is a NoOpGraphProvider, as in the reference
+            types = getattr(graph_data, "edge_types", None)
+            if types is not None and key not in types:
+                return None
             return graph_data[key]
 
     nodes = {name: torch.as_tensor(graph_data[name].x) for name in graph_data.node_types}

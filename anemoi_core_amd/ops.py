@@ -387,6 +387,43 @@ def gt_attention_fused_edge(q: Tensor, k: Tensor, v: Tensor, edge_feat: Tensor, 
     return (out, lse) if return_lse else out
 
 
+WINDOW_HEAD_DIMS = (32, 64, 128)  # the head dimensions csrc/window_attention.hip is built for
+
+
+def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Optional[int], *, scale: Optional[float] = None,
+                     softcap: Optional[float] = None, alibi_slopes: Optional[Tensor] = None, batch_size: int = 1, return_lse: bool = False):
+    """Sliding-window multi-head self-attention (layers/attention.py MultiHeadSelfAttention with flash-attention semantics).  q, k, v:
+    [batch * N, A] (column slices of one projection buffer are read in place), head h = columns [h d, (h+1) d), d = A / num_heads in
+    WINDOW_HEAD_DIMS; query i attends keys j of its own sequence with |i - j| <= window (None or -1: all).  scale defaults to d^-1/2;
+    softcap > 0 caps the scores; alibi_slopes fp32 [num_heads].  Returns out [batch * N, A] (and the fp32 LSE [batch * N, num_heads])."""
+    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError(f"q, k and v must be 2-D of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    rows, A = q.shape
+    if num_heads <= 0 or A % num_heads:
+        raise ValueError(f"channels {A} not divisible by heads {num_heads}")
+    d = A // num_heads
+    if d not in WINDOW_HEAD_DIMS:
+        raise ValueError(f"window_attention: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
+    if batch_size <= 0 or rows % batch_size:
+        raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    w = -1 if window is None or window < 0 else int(min(window, 2**31 - 1))
+    scale = float(d ** -0.5 if scale is None else scale)
+    cap = float(softcap) if softcap is not None and softcap > 0 else 0.0
+    ext = _ext.ops()
+    if ext is not None:
+        out, lse = ext.window_attention(q, k, v, num_heads, w, scale, cap, alibi_slopes, batch_size, return_lse)
+        return (out, lse) if return_lse else out
+    _dev(q, k, v, alibi_slopes)
+    out = torch.empty((rows, A), dtype=q.dtype, device=q.device)
+    lse = torch.empty((rows, num_heads), dtype=torch.float32, device=q.device) if return_lse else None
+    (qp, ldq), (kp, ldk), (vp, ldv) = _rows(q, "q"), _rows(k, "k", q.dtype), _rows(v, "v", q.dtype)
+    rc = _lib.load().anemoi_window_attention_fwd(qp, ldq, kp, ldk, vp, ldv, out.data_ptr(), A, lse.data_ptr() if return_lse else 0,
+                                                 batch_size, rows // batch_size, num_heads, d, w, scale, cap,
+                                                 _vec(alibi_slopes, "alibi_slopes", num_heads, torch.float32), _dt(q), _stream())
+    _lib.check(rc, "window_attention_fwd")
+    return (out, lse) if return_lse else out
+
+
 def cond_layer_norm(x: Tensor, scale: Tensor, shift: Tensor, eps: float = 1e-5) -> Tensor:
     """y = LayerNorm(x) * (scale + 1) + shift over the last dim, per-row scale / shift [N, D] (column slices allowed)."""
     if _needs_grad(x, scale, shift):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 13
+#define ANEMOI_HIP_ABI_VERSION 14
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -511,6 +511,19 @@ int anemoi_gnn_node_chain_segsum_fwd(const void* x, int64_t ld_x, const void* ed
                                      int32_t t_out_features, void* t_out, int64_t ld_t, int32_t n_rows, int32_t channels,
                                      anemoi_dtype_t dtype, void* stream);
 
+
+/* Sliding-window (banded) multi-head self-attention, forward.
+ * Replaces: MultiHeadSelfAttention.attention_computation with its flash-attention / SDPA wrappers (layers/attention.py:41-262, 283-316,
+ * 362-520): rows are (batch seq_len), head h is columns [h d, (h+1) d) of every operand; query i attends keys j of its own sequence with
+ * |i - j| <= window (window < 0 or >= seq_len - 1: all of them):
+ *     s = <q_i, k_j> * scale;  s = softcap tanh(s / softcap)  (softcap > 0);  s -= alibi_slopes[h] |i - j|  (alibi_slopes != NULL)
+ *     out_i = sum_j softmax_j(s) v_j;  lse[i, h] = ln sum_j exp(s_j)  (fp32 [batch seq_len, H], if lse != NULL)
+ * q, k, v, out: [batch seq_len, >= H d] with their own leading dimensions (column slices of one [rows, 3A] buffer work as they are);
+ * alibi_slopes: fp32 [H] or NULL.  d in {32, 64, 128}, otherwise ANEMOI_E_UNSUPPORTED.  16-bit operands need 16-byte aligned rows of
+ * q / k / v and 8-byte aligned rows of out.  The work is proportional to seq_len (2 window + 1); no allocation, no synchronisation. */
+int anemoi_window_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
+                                float* lse, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window, float scale, float softcap,
+                                const float* alibi_slopes, anemoi_dtype_t dtype, void* stream);
 
 #ifdef __cplusplus
 }
