@@ -552,7 +552,8 @@ extern "C" int anemoi_layernorm_bwd(const void* x, int64_t ldx, const void* gamm
                                     int64_t lddx, float* d_gamma, float* d_beta, float* workspace, int32_t n_rows, int32_t D,
                                     float eps, anemoi_dtype_t dtype, void* stream) {
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D && lddy >= D && lddx >= D, "layernorm_bwd: bad sizes n_rows=%d D=%d", n_rows, D);
-  ANEMOI_REQUIRE(x && gamma && d_y && d_x, "layernorm_bwd: null pointer");
+  // no rows: nothing is read or written but the sums (zeros), and a zero-row tensor's data pointer is null
+  ANEMOI_REQUIRE(n_rows == 0 || (x && gamma && d_y && d_x), "layernorm_bwd: null pointer");
   ANEMOI_REQUIRE(workspace || (!d_gamma && !d_beta), "layernorm_bwd: d_gamma/d_beta need the workspace (anemoi_reduce_workspace_bytes)");
   hipStream_t st = as_stream(stream);
   switch (dtype) {
@@ -566,7 +567,7 @@ extern "C" int anemoi_layernorm_bwd(const void* x, int64_t ldx, const void* gamm
 extern "C" int anemoi_colsum(const void* x, int64_t ldx, float* out, float* workspace, int32_t n_rows, int32_t D,
                              anemoi_dtype_t dtype, void* stream) {
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D, "colsum: bad sizes n_rows=%d D=%d", n_rows, D);
-  ANEMOI_REQUIRE(x && out && workspace, "colsum: null pointer");
+  ANEMOI_REQUIRE((x || n_rows == 0) && out && workspace, "colsum: null pointer");
   hipStream_t st = as_stream(stream);
   switch (dtype) {
     case ANEMOI_F32: return launch_rowwise_bwd<float, 1>(x, ldx, nullptr, nullptr, 0, nullptr, 0, nullptr, out, workspace, n_rows, D, 0.f, st);

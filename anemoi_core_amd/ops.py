@@ -690,6 +690,8 @@ def segment_sum_rows(x: Tensor, ptr: Tensor, ids: Optional[Tensor] = None) -> Te
         if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
             raise ValueError("ptr / ids must be contiguous int32 vectors")
     D, n_out = x.shape[1], ptr.shape[0] - 1
+    if x.shape[0] == 0:  # no rows to sum (a shard without edges): every segment is empty, and x has no data pointer to pass
+        return torch.zeros((n_out, D), dtype=x.dtype, device=x.device)
     out = torch.empty((n_out, D), dtype=x.dtype, device=x.device)
     p, ld = _rows(x, "x")
     rc = _lib.load().anemoi_segment_sum_rows(p, ld, ptr.data_ptr(), ids.data_ptr() if ids is not None else 0, out.data_ptr(), D, n_out, D,

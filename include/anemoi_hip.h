@@ -180,7 +180,8 @@ int anemoi_assemble_output(const void* x_out, int64_t ldx, const void* x_skip, i
 /* LayerNorm backward.  Replaces: autograd of layer_kernels.LayerNorm (layers/utils.py:107-121).
  *   d_x [n_rows, D] (same dtype), d_gamma / d_beta fp32 [D] (either may be NULL; both NULL: no column sums);
  *   workspace: anemoi_reduce_workspace_bytes(D) bytes of fp32 scratch (per-wave partial column sums, added in a fixed
- *   order by a second kernel: deterministic, no atomics).  Statistics are recomputed from x (nothing saved by the forward). */
+ *   order by a second kernel: deterministic, no atomics).  Statistics are recomputed from x (nothing saved by the forward).
+ *   n_rows == 0 (here and in anemoi_colsum): the row pointers may be NULL, the sums are written as zeros. */
 int64_t anemoi_reduce_workspace_bytes(int32_t D);
 int anemoi_layernorm_bwd(const void* x, int64_t ldx, const void* gamma, const void* d_y, int64_t lddy, void* d_x,
                          int64_t lddx, float* d_gamma, float* d_beta, float* workspace, int32_t n_rows, int32_t D,
