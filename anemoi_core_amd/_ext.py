@@ -64,6 +64,10 @@ def _register_fakes() -> None:
     def _(x, weight, bias, eps, residual, out):
         return None
 
+    @fake("anemoi_hip::cond_layer_norm_proj")
+    def _(x, cond, w, bias, eps, residual):
+        return x.new_empty(x.shape)
+
     @fake("anemoi_hip::gt_attention_fused_edge")
     def _(q, k, v, edge_feat, w_packed, row, colptr, order, n_src, num_heads, addend, return_lse):
         n_dst = q.shape[0]

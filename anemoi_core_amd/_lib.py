@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -40,6 +40,7 @@ SIGNATURES = {
     "anemoi_gelu_bwd": ([_p, _i64, _p, _i64, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_cond_layernorm_bwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _f, C.c_int, _p], C.c_int),
     "anemoi_cond_layernorm_fwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _f, C.c_int, _p], C.c_int),
+    "anemoi_cond_layernorm_proj_fwd": ([_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _f, C.c_int, _p], C.c_int),
     "anemoi_assemble_input": ([_p, _i64, _i64, _i32, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_assemble_output": ([_p, _i64, _p, _i64, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_assemble_input_norm": ([_p, C.c_int, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),

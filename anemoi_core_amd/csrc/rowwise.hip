@@ -7,6 +7,8 @@
 // "edge_mlp(...) + edge_attr" followed by scatter-sum (models/src/anemoi/models/layers/conv.py:73-81).
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "common.h"
 
 namespace anemoi {
@@ -169,6 +171,145 @@ __global__ __launch_bounds__(64 * kRowWaves) void cond_layernorm_fwd_kernel(cons
   load_row<T, VEC, CH>(x + (int64_t)rowi * ldx, D, lane, r);
   normalise_row<T, VEC, CH>(r, D, lane, scale + (int64_t)rowi * lds, shift + (int64_t)rowi * ldsh, eps, 1.0f);
   store_row<T, VEC, CH>(y + (int64_t)rowi * ldy, D, lane, r);
+}
+
+// ConditionalLayerNorm with the modulation computed IN the kernel (anemoi_cond_layernorm_proj_fwd):
+//   y[r, :] = LN(x[r, :]) * (1 + cond[r, :] . Ws^T + bs) + (cond[r, :] . Wb^T + bb)  [+ residual[r, :]]
+// for a conditioning width C <= kCondMax, where "the two Linear maps of the conditioning" are a handful of FMAs per output element: no
+// [N, 2D] modulation tensor is written and read back.  w is the C-major image [C][2][D] of [scale.weight ; bias.weight] (row c = column c
+// of both weights: a lane's VEC columns are contiguous), bias is [2][D].  One wave per row as in cond_layernorm_fwd_kernel, but the waves
+// walk the rows with a grid stride so that what a lane needs of the image - the 2 C weights of its own columns - is fetched once per
+// wave, not once per row.  Where the image lives (MODE):
+//   kWReg    C <= kCondReg and one 16-byte chunk of row per lane (D <= 512 16-bit, D <= 256 fp32 at full vector width): in registers
+//            (the hot shape D = 512, C = 4: 80 values per lane with the biases, 118 VGPRs in all, four waves per SIMD);
+//   kWLds    the whole image fits the CU's LDS (160 KiB; 128 KiB at D = 1024, C = 32 in 16 bit): staged once per workgroup, then
+//            conflict-free ds_read of VEC contiguous elements per lane (lanes read consecutive addresses);
+//   kWGlobal larger images (fp32 at D = 1024, C = 32 is 256 KiB): read through L1 / L2 for every row.
+// A row's C conditioning values are loaded by lanes 0 .. C-1 (element loads: any alignment, column slices) and broadcast with
+// v_readlane; the modulation is accumulated in fp32 and never rounded to T.  The next row's x is in flight while a row is computed.
+constexpr int kCondMax = 32;
+constexpr int kCondReg = 4;
+constexpr int kProjWaves = 8;
+constexpr int kLdsBytes = 160 * 1024;
+enum { kWReg = 0, kWLds = 1, kWGlobal = 2 };
+
+template <typename T, int VEC, int CH, int MODE>
+__global__ __launch_bounds__(64 * kProjWaves) void cond_layernorm_proj_fwd_kernel(const T* __restrict__ x, int64_t ldx, const T* __restrict__ cond,
+                                                                                  int64_t ldc, const T* __restrict__ w, const T* __restrict__ bias,
+                                                                                  const T* __restrict__ residual, int64_t ldr, T* __restrict__ y,
+                                                                                  int64_t ldy, int n_rows, int D, int C, float eps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char proj_smem[];
+  using V = Vec<T, VEC>;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * kProjWaves + (threadIdx.x >> 6));
+  const int n_waves = gridDim.x * kProjWaves;
+  const T* wsrc = w;
+  const T* bsrc = bias;
+  if constexpr (MODE == kWLds) {
+    T* s = reinterpret_cast<T*>(proj_smem);
+    const int nw = 2 * C * D, nb = 2 * D;  // both multiples of VEC
+    for (int i = threadIdx.x * VEC; i < nw; i += 64 * kProjWaves * VEC) *reinterpret_cast<V*>(s + i) = *reinterpret_cast<const V*>(w + i);
+    for (int i = threadIdx.x * VEC; i < nb; i += 64 * kProjWaves * VEC) *reinterpret_cast<V*>(s + nw + i) = *reinterpret_cast<const V*>(bias + i);
+    __syncthreads();
+    wsrc = s;
+    bsrc = s + nw;
+  }
+  V wr[MODE == kWReg ? kCondReg : 1][2][CH], br[2][CH];
+  if constexpr (MODE == kWReg) {
+#pragma unroll
+    for (int t = 0; t < CH; ++t) {
+      const int col = (t * 64 + lane) * VEC;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) br[h][t].v[j] = from_float<T>(0.f);
+        if (col < D) br[h][t] = *reinterpret_cast<const V*>(bias + h * D + col);
+#pragma unroll
+        for (int c = 0; c < kCondReg; ++c) {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) wr[c][h][t].v[j] = from_float<T>(0.f);
+          if (c < C && col < D) wr[c][h][t] = *reinterpret_cast<const V*>(w + (int64_t)(2 * c + h) * D + col);
+        }
+      }
+    }
+  }
+  if (wave >= n_rows) return;
+  float r[CH][VEC];
+  load_row<T, VEC, CH>(x + (int64_t)wave * ldx, D, lane, r);
+  for (int rowi = wave; rowi < n_rows; rowi += n_waves) {
+    const int nxt = rowi + n_waves < n_rows ? rowi + n_waves : rowi;  // the last trip re-reads its own row (an L1 hit) and drops it
+    float rn[CH][VEC];
+    load_row<T, VEC, CH>(x + (int64_t)nxt * ldx, D, lane, rn);
+    const float cv = lane < C ? to_float(cond[(int64_t)rowi * ldc + lane]) : 0.f;
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < CH; ++t)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) s += r[t][j];
+    const float mean = wave_sum(s) / (float)D;
+    float ss = 0.f;
+#pragma unroll
+    for (int t = 0; t < CH; ++t) {
+      if ((t * 64 + lane) * VEC < D) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          const float dlt = r[t][j] - mean;
+          ss = fmaf(dlt, dlt, ss);
+        }
+      }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)D + eps);
+#pragma unroll
+    for (int t = 0; t < CH; ++t) {
+      const int col = (t * 64 + lane) * VEC;
+      if (col < D) {
+        float sc[VEC], sh[VEC];
+        if constexpr (MODE == kWReg) {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) {
+            sc[j] = to_float(br[0][t].v[j]);
+            sh[j] = to_float(br[1][t].v[j]);
+          }
+#pragma unroll
+          for (int c = 0; c < kCondReg; ++c) {
+            const float cc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cv), c));
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              sc[j] = fmaf(cc, to_float(wr[c][0][t].v[j]), sc[j]);
+              sh[j] = fmaf(cc, to_float(wr[c][1][t].v[j]), sh[j]);
+            }
+          }
+        } else {
+          load_vec<T, VEC>(bsrc + col, sc);
+          load_vec<T, VEC>(bsrc + D + col, sh);
+          for (int c = 0; c < C; ++c) {
+            const float cc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cv), c));
+            float ws[VEC], wb[VEC];
+            load_vec<T, VEC>(wsrc + (2 * c) * D + col, ws);
+            load_vec<T, VEC>(wsrc + (2 * c + 1) * D + col, wb);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+              sc[j] = fmaf(cc, ws[j], sc[j]);
+              sh[j] = fmaf(cc, wb[j], sh[j]);
+            }
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) r[t][j] = fmaf((r[t][j] - mean) * rstd, 1.0f + sc[j], sh[j]);
+        if (residual != nullptr) {
+          float rs[VEC];
+          load_vec<T, VEC>(residual + (int64_t)rowi * ldr + col, rs);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) r[t][j] += rs[j];
+        }
+      }
+    }
+    store_row<T, VEC, CH>(y + (int64_t)rowi * ldy, D, lane, r);
+#pragma unroll
+    for (int t = 0; t < CH; ++t)
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) r[t][j] = rn[t][j];
+  }
 }
 
 // e_new = LN(z) + e_old (LN optional) ; agg[d] = sum over the in-edges of d (dst-sorted => contiguous rows).
@@ -579,6 +720,72 @@ static int cond_layernorm_launch(const void* x, int64_t ldx, const void* scale, 
   return check_launch("cond_layernorm_fwd_kernel");
 }
 
+static int cu_count() {
+  static int cached[64];
+  int d = 0;
+  (void)hipGetDevice(&d);
+  int n = (d >= 0 && d < 64) ? cached[d] : 0;
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) n = 256;
+    if (d >= 0 && d < 64) cached[d] = n;
+  }
+  return n;
+}
+
+template <typename T, int VEC, int CH>
+static int cond_proj_launch_vc(const T* x, int64_t ldx, const T* cond, int64_t ldc, const T* w, const T* bias, const T* residual, int64_t ldr, T* y,
+                               int64_t ldy, int n_rows, int D, int C, float eps, hipStream_t st) {
+  constexpr bool kRegOk = CH * VEC * sizeof(T) <= 16;  // one 16-byte chunk per lane: twice that costs 226 VGPRs (two waves per SIMD)
+  const size_t image = (size_t)(2 * C + 2) * D * sizeof(T);
+  const int blocks_needed = (n_rows + kProjWaves - 1) / kProjWaves;
+  const dim3 block(64 * kProjWaves);
+  // workgroups of 8 waves per CU.  Register form: 2 (two waves per SIMD, each with two rows in flight, and a wave amortises its weights over
+  // ~10 rows of the 40 968-row hot shape) - measured at D = 512, C = 4, bf16, with / without residual: 25.8 / 23.0 us at 2, 29.2 / 26.5 at 4,
+  // 32.8 / 28.7 at 8.  LDS form: as many images as fit, 4 at most (D = 1024, C = 4: 50.4 / 44.2 us at 2, 49.2 / 41.8 at 4, 50.2 / 43.6 at 8).
+  static const int reg_per_cu = env_int(getenv("ANEMOI_CLNP_BLOCKS_PER_CU"), 2, 1, 8);
+  if constexpr (kRegOk) {
+    if (C <= kCondReg) {
+      const dim3 grid(std::min(blocks_needed, cu_count() * reg_per_cu));
+      hipLaunchKernelGGL((cond_layernorm_proj_fwd_kernel<T, VEC, CH, kWReg>), grid, block, 0, st, x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy,
+                         n_rows, D, C, eps);
+      return check_launch("cond_layernorm_proj_fwd_kernel");
+    }
+  }
+  if (image <= (size_t)kLdsBytes) {
+    static PerDeviceOnce once;
+    once.run([&] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cond_layernorm_proj_fwd_kernel<T, VEC, CH, kWLds>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    });
+    const int per_cu = std::max(1, std::min(4, (int)(kLdsBytes / image)));
+    const dim3 grid(std::min(blocks_needed, cu_count() * per_cu));
+    hipLaunchKernelGGL((cond_layernorm_proj_fwd_kernel<T, VEC, CH, kWLds>), grid, block, image, st, x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy,
+                       n_rows, D, C, eps);
+    return check_launch("cond_layernorm_proj_fwd_kernel");
+  }
+  const dim3 grid(std::min(blocks_needed, cu_count() * 4));
+  hipLaunchKernelGGL((cond_layernorm_proj_fwd_kernel<T, VEC, CH, kWGlobal>), grid, block, 0, st, x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy,
+                     n_rows, D, C, eps);
+  return check_launch("cond_layernorm_proj_fwd_kernel");
+}
+
+template <typename T>
+static int cond_layernorm_proj_launch(const void* x, int64_t ldx, const void* cond, int64_t ldc, const void* w, const void* bias, const void* residual,
+                                      int64_t ldr, void* y, int64_t ldy, int n_rows, int D, int C, float eps, hipStream_t st) {
+  const int vec = pick_vec<T>(D, {ldx, ldy, residual ? ldr : (int64_t)0}, {x, y, residual, w, bias});
+  const int ch = pick_chunks(D, vec);
+  ANEMOI_REQUIRE(ch > 0, "cond_layernorm_proj_fwd: D=%d too large for the register-resident row", D);
+#define CLNP_CASE(V, CC)                                                                                                                      \
+  case V * 16 + CC:                                                                                                                           \
+    return cond_proj_launch_vc<T, V, CC>((const T*)x, ldx, (const T*)cond, ldc, (const T*)w, (const T*)bias, (const T*)residual, ldr, (T*)y, ldy, \
+                                         n_rows, D, C, eps, st);
+  switch (vec * 16 + ch) {
+    ALL_VEC_CH(CLNP_CASE)
+    default: set_error("cond_layernorm_proj_fwd: bad vector width"); return ANEMOI_E_INVALID;
+  }
+#undef CLNP_CASE
+}
+
 template <typename T>
 static int edge_launch(const void* z, int64_t ldz, const void* e_old, int64_t lde, const void* gamma, const void* beta,
                        float eps, const int32_t* colptr, void* e_new, int64_t ldn, void* agg, int64_t ldagg, int n_dst,
@@ -689,6 +896,26 @@ extern "C" int anemoi_cond_layernorm_fwd(const void* x, int64_t ldx, const void*
     case ANEMOI_F32: return cond_layernorm_launch<float>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
     case ANEMOI_BF16: return cond_layernorm_launch<bf16_t>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
     case ANEMOI_F16: return cond_layernorm_launch<f16_t>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
+    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
+  }
+}
+
+extern "C" int anemoi_cond_layernorm_proj_fwd(const void* x, int64_t ldx, const void* cond, int64_t ldc, const void* w, const void* bias,
+                                              const void* residual, int64_t ldr, void* y, int64_t ldy, int32_t n_rows, int32_t D, int32_t C,
+                                              float eps, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && C > 0 && ldx >= D && ldy >= D && ldc >= C && (!residual || ldr >= D),
+                 "cond_layernorm_proj_fwd: bad sizes n_rows=%d D=%d C=%d", n_rows, D, C);
+  if (C > kCondMax) {
+    set_error("cond_layernorm_proj_fwd: C=%d conditioning channels, the in-kernel modulation takes 1 to %d", C, kCondMax);
+    return ANEMOI_E_UNSUPPORTED;
+  }
+  if (n_rows == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && cond && w && bias && y, "cond_layernorm_proj_fwd: null pointer");
+  hipStream_t st = as_stream(stream);
+  switch (dtype) {
+    case ANEMOI_F32: return cond_layernorm_proj_launch<float>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
+    case ANEMOI_BF16: return cond_layernorm_proj_launch<bf16_t>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
+    case ANEMOI_F16: return cond_layernorm_proj_launch<f16_t>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
     default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
   }
 }

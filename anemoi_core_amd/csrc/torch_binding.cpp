@@ -152,6 +152,33 @@ void layer_norm_out(const Tensor& x, const Tensor& weight, const OptTensor& bias
   layer_norm_impl(x, weight, bias, eps, residual, out);
 }
 
+// ConditionalLayerNorm with the modulation computed in the kernel (+ residual)                  (anemoi_cond_layernorm_proj_fwd)
+Tensor cond_layer_norm_proj(const Tensor& x, const Tensor& cond, const Tensor& w, const Tensor& bias, double eps, const OptTensor& residual) {
+  on_current_device(x);
+  const auto dt = x.scalar_type();
+  const auto dev = x.device();
+  const int64_t D = x.size(-1);
+  Tensor x2 = x.reshape({-1, D});
+  if (x2.size(1) > 1 && x2.stride(1) != 1) x2 = x2.contiguous();
+  const int64_t n = x2.size(0);
+  TORCH_CHECK_VALUE(cond.dim() == 2 && cond.size(0) == n, "cond must be [rows(x), C], got ", cond.sizes());
+  const int64_t C = cond.size(1);
+  TORCH_CHECK_VALUE(w.dim() == 2 && w.size(0) == C && w.size(1) == 2 * D && w.is_contiguous() && w.scalar_type() == dt && w.device() == dev,
+                    "w must be the contiguous [C, 2 D] image of [scale.weight ; bias.weight] in x's dtype");
+  TORCH_CHECK_VALUE(bias.device() == dev, "bias must be on x's device");
+  OptTensor r2;
+  if (residual.has_value() && residual->defined()) {
+    TORCH_CHECK_VALUE(residual->sizes() == x.sizes(), "residual shape does not match x");
+    r2 = residual->reshape({-1, D});
+  }
+  Tensor y = at::empty({n, D}, x.options());
+  const Rows rx = rows(x2, "x", dt, dev), rc = rows(cond, "cond", dt, dev), rr = rows(r2, "residual", dt, dev);
+  check(anemoi_cond_layernorm_proj_fwd(rx.p, rx.ld, rc.p, rc.ld, w.data_ptr(), vec(bias, "bias", 2 * D, dt), rr.p, rr.ld, y.data_ptr(), D, (int32_t)n,
+                                       (int32_t)D, (int32_t)C, (float)eps, dt_of(x), cur_stream()),
+        "cond_layernorm_proj_fwd");
+  return y.view(x.sizes());
+}
+
 // lin_edge fused into the edge attention (+ self term)                                 (anemoi_gt_attention_fused_edge_fwd)
 std::tuple<Tensor, Tensor> gt_attention_fused_edge(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& edge_feat, const Tensor& w_packed,
                                                    const Tensor& row, const Tensor& colptr, const OptTensor& order, int64_t n_src, int64_t num_heads,
@@ -272,6 +299,7 @@ TORCH_LIBRARY(anemoi_hip, m) {
         "Tensor(a!) out) -> ()");
   m.def("layer_norm(Tensor x, Tensor weight, Tensor? bias, float eps, Tensor? residual) -> Tensor");
   m.def("layer_norm_out(Tensor x, Tensor weight, Tensor? bias, float eps, Tensor? residual, Tensor(a!) out) -> ()");
+  m.def("cond_layer_norm_proj(Tensor x, Tensor cond, Tensor w, Tensor bias, float eps, Tensor? residual) -> Tensor");
   m.def("gt_attention_fused_edge(Tensor q, Tensor k, Tensor v, Tensor edge_feat, Tensor w_packed, Tensor row, Tensor colptr, Tensor? order, "
         "int n_src, int num_heads, Tensor? addend, bool return_lse) -> (Tensor, Tensor)");
   m.def("linear_with_row_stats(Tensor x, Tensor weight, Tensor? bias, Tensor? residual) -> (Tensor, Tensor)");
@@ -285,6 +313,7 @@ TORCH_LIBRARY_IMPL(anemoi_hip, CUDA, m) {  // the ROCm build of PyTorch dispatch
   m.impl("linear_out", &linear_out);
   m.impl("layer_norm", &layer_norm);
   m.impl("layer_norm_out", &layer_norm_out);
+  m.impl("cond_layer_norm_proj", &cond_layer_norm_proj);
   m.impl("gt_attention_fused_edge", &gt_attention_fused_edge);
   m.impl("linear_with_row_stats", &linear_with_row_stats);
   m.impl("linear_ln_folded", &linear_ln_folded);
@@ -295,6 +324,7 @@ TORCH_LIBRARY_IMPL(anemoi_hip, CPU, m) {  // fail loudly, like the ctypes path
   m.impl("linear", [](const Tensor&, const Tensor&, const OptTensor&, int64_t, const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&,
                       const OptTensor&, const OptTensor&) -> Tensor { no_cpu(); });
   m.impl("layer_norm", [](const Tensor&, const Tensor&, const OptTensor&, double, const OptTensor&) -> Tensor { no_cpu(); });
+  m.impl("cond_layer_norm_proj", [](const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, const OptTensor&) -> Tensor { no_cpu(); });
   m.impl("window_attention", [](const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, double, double, const OptTensor&, int64_t,
                                 bool) -> std::tuple<Tensor, Tensor> { no_cpu(); });
 }

@@ -1,1 +1,2 @@
 from .encoder_processor_decoder import AnemoiModelEncProcDec  # noqa: F401
+from .ens_encoder_processor_decoder import AnemoiEnsModelEncProcDec  # noqa: F401

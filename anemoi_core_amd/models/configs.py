@@ -63,3 +63,22 @@ def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="a
     }
 
 
+def ens_model_config(kind, num_channels, num_layers, num_heads, trainable, *, noise_channels_dim=4, noise_mlp_hidden_dim=32, noise_std=1,
+                     injector="NoiseConditioning", condition_on_residual=False, prefix="anemoi.models.layers", window_size=512):
+    """The nested config of the reference's AnemoiEnsModelEncProcDec (training/src/anemoi/training/config/model/graphtransformer_ens.yaml,
+    transformer_ens.yaml): ``model_config(kind, ...)`` ("gt" or "transformer") plus ``condition_on_residual`` and the ``noise_injector``.
+    ``injector``: "NoiseConditioning" (the noise conditions the processor, whose ``layer_kernels.LayerNorm`` becomes a ConditionalLayerNorm of
+    ``condition_shape = noise_channels_dim``), "NoiseInjector" (projected into the latent; plain LayerNorms) or "NoOpNoiseInjector"."""
+    cfg = model_config(kind, num_channels, num_layers, num_heads, trainable, prefix=prefix, window_size=window_size)
+    m = cfg["model"]
+    m["condition_on_residual"] = condition_on_residual
+    inj = {"_target_": f"{prefix}.ensemble.{injector}"}
+    if injector != "NoOpNoiseInjector":
+        inj.update(noise_std=noise_std, noise_channels_dim=noise_channels_dim, noise_mlp_hidden_dim=noise_mlp_hidden_dim, noise_matrix=None,
+                   layer_kernels=None)
+    if injector == "NoiseConditioning":
+        inj.update(noise_edges_name=None, edge_weight_attribute=None, row_normalize_noise_matrix=False, autocast=False)
+        m["processor"]["layer_kernels"] = {"LayerNorm": {"_target_": f"{prefix}.normalization.ConditionalLayerNorm", "_partial_": True,
+                                                         "condition_shape": noise_channels_dim, "zero_init": True, "autocast": False}}
+    m["noise_injector"] = inj
+    return cfg

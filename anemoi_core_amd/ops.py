@@ -446,6 +446,43 @@ def _cond_layer_norm_fwd(x: Tensor, scale: Tensor, shift: Tensor, eps: float = 1
     return y.view(x.shape)
 
 
+COND_PROJ_MAX = 32  # conditioning widths the in-kernel modulation of cond_layer_norm_proj takes (csrc/rowwise.hip: kCondMax)
+
+
+def cond_layer_norm_proj_weights(scale_weight: Tensor, scale_bias: Tensor, shift_weight: Tensor, shift_bias: Tensor) -> tuple[Tensor, Tensor]:
+    """The prepared operands of ``cond_layer_norm_proj`` from the two Linear maps of a ConditionalLayerNorm ([D, C] weights, [D] biases):
+    the C-major image [C, 2 D] (row c = column c of both weights, so that a lane's columns are contiguous) and the biases [2 D]."""
+    return (torch.cat([scale_weight, shift_weight], 0).t().contiguous(), torch.cat([scale_bias, shift_bias]).contiguous())
+
+
+def cond_layer_norm_proj(x: Tensor, cond: Tensor, w: Tensor, b: Tensor, eps: float = 1e-5, residual: Optional[Tensor] = None) -> Tensor:
+    """y = LayerNorm(x) * (1 + cond Ws^T + bs) + (cond Wb^T + bb) [+ residual] in ONE launch: the modulation is computed in the kernel,
+    in fp32, from the conditioning rows ``cond`` [rows(x), C] (C <= COND_PROJ_MAX; a column slice or unaligned rows are fine) and the
+    prepared operands (w [C, 2 D], b [2 D]) of ``cond_layer_norm_proj_weights``.  Inference only (no autograd)."""
+    ext = _ext.ops()
+    if ext is not None:
+        return ext.cond_layer_norm_proj(x, cond, w, b, float(eps), residual)
+    _dev(x, cond, w, b, residual)
+    D = x.shape[-1]
+    x2 = x.reshape(-1, D)
+    if x2.shape[1] > 1 and x2.stride(1) != 1:
+        x2 = x2.contiguous()
+    if cond.dim() != 2 or cond.shape[0] != x2.shape[0]:
+        raise ValueError(f"cond must be [rows(x), C], got {tuple(cond.shape)}")
+    C = cond.shape[1]
+    if tuple(w.shape) != (C, 2 * D) or not w.is_contiguous() or w.dtype != x.dtype:
+        raise ValueError("w must be the contiguous [C, 2 D] image of [scale.weight ; bias.weight] in x's dtype")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("residual shape does not match x")
+    y = torch.empty((x2.shape[0], D), dtype=x.dtype, device=x.device)
+    (p, ld), (cp, ldc) = _rows(x2, "x"), _rows(cond, "cond", x.dtype)
+    rp, ldr = _rows(None if residual is None else residual.reshape(-1, D), "residual", x.dtype)
+    rc = _lib.load().anemoi_cond_layernorm_proj_fwd(p, ld, cp, ldc, w.data_ptr(), _vec(b, "bias", 2 * D, x.dtype), rp, ldr, y.data_ptr(), D,
+                                                    x2.shape[0], D, C, float(eps), _dt(x), _stream())
+    _lib.check(rc, "cond_layernorm_proj_fwd")
+    return y.view(x.shape)
+
+
 def cond_layer_norm_backward(d_y: Tensor, x: Tensor, scale: Tensor, eps: float = 1e-5):
     """(dx, d_scale) of cond_layer_norm, both [N, D]; d_shift is d_y itself."""
     _dev(d_y, x, scale)

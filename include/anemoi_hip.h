@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 14
+#define ANEMOI_HIP_ABI_VERSION 15
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -150,7 +150,19 @@ int anemoi_layernorm_fwd(const void* x, int64_t ldx, const void* gamma, const vo
 int anemoi_cond_layernorm_fwd(const void* x, int64_t ldx, const void* scale, int64_t lds, const void* shift, int64_t ldsh,
                               void* y, int64_t ldy, int32_t n_rows, int32_t D, float eps, anemoi_dtype_t dtype, void* stream);
 
-/* Backward of the above: d_x [n_rows, D] and d_scale [n_rows, D] = d_y * x^ (per row; d_shift = d_y needs no kernel); the
+/* ConditionalLayerNorm forward with the modulation computed in the kernel - no [n_rows, 2D] tensor between the conditioning's two
+ * Linear maps and the LayerNorm (layers/normalization.py:34-94 in one launch):
+ *   y[r, :] = LN(x[r, :]) * (1 + cond[r, :] . Ws^T + bs) + (cond[r, :] . Wb^T + bb)  (+ residual[r, :])
+ * cond: [n_rows, C], leading dimension ldc >= C, any element alignment (column slices allowed), C in 1 .. 32 (beyond:
+ * ANEMOI_E_UNSUPPORTED - run anemoi_linear_fwd + anemoi_cond_layernorm_fwd).  w: the C-major image [C][2][D] of
+ * [scale.weight ; bias.weight] (w[c][0][d] = Ws[d][c], w[c][1][d] = Wb[d][c]), bias: [2][D] = [scale.bias ; bias.bias], both
+ * contiguous in the model dtype and built once per weight version.  The modulation is accumulated in fp32 and not rounded
+ * to the model dtype.  D: every width anemoi_cond_layernorm_fwd accepts. */
+int anemoi_cond_layernorm_proj_fwd(const void* x, int64_t ldx, const void* cond, int64_t ldc, const void* w, const void* bias,
+                                   const void* residual, int64_t ldr, void* y, int64_t ldy, int32_t n_rows, int32_t D, int32_t C,
+                                   float eps, anemoi_dtype_t dtype, void* stream);
+
+/* Backward of anemoi_cond_layernorm_fwd: d_x [n_rows, D] and d_scale [n_rows, D] = d_y * x^ (per row; d_shift = d_y needs no kernel); the
  * gradients of the conditioning's two Linear maps follow from d_scale / d_shift through anemoi_linear_fwd. */
 int anemoi_cond_layernorm_bwd(const void* x, int64_t ldx, const void* scale, int64_t lds, const void* d_y, int64_t lddy,
                               void* d_x, int64_t lddx, void* d_scale, int64_t ldds, int32_t n_rows, int32_t D, float eps,
