@@ -87,3 +87,8 @@ def _register_fakes() -> None:
     @fake("anemoi_hip::window_attention")
     def _(q, k, v, num_heads, window, scale, softcap, alibi_slopes, batch_size, return_lse):
         return q.new_empty(q.shape), q.new_empty((q.shape[0] if return_lse else 0, num_heads), dtype=torch.float32)
+
+    @fake("anemoi_hip::sparse_project")
+    def _(x, indptr, indices, w, cols, mul, add, out_fp32):
+        C = x.shape[-1] if cols is None else cols.shape[0]
+        return x.new_empty((*x.shape[:-2], indptr.shape[0] - 1, C), dtype=torch.float32 if out_fp32 else x.dtype)

@@ -195,6 +195,34 @@ class GeluFunction(torch.autograd.Function):
         return ops.gelu_backward(x.reshape(-1, D), d_y.reshape(-1, D).contiguous()).view(x.shape)
 
 
+class SparseProjectFunction(torch.autograd.Function):
+    """y = A f(x[..., cols]) (``anemoi_sparse_project_fwd``); backward: d_x[..., cols] = mul * (A^T d_y) with the same kernel on the transposed
+    matrix (fp32 result), scattered into the selected columns.  The matrix, the column list and the affine map are constants."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, matrix, cols: Optional[Tensor], mul: Optional[Tensor], add: Optional[Tensor], out_dtype):
+        if matrix.t is None:
+            raise ValueError("sparse_project: the backward pass needs the transposed matrix (ops.build_sparse_matrix(..., with_transpose=True))")
+        ctx.matrix, ctx.x_shape, ctx.x_dtype = matrix, x.shape, x.dtype
+        ctx.save_for_backward(*[t for t in (cols, mul) if t is not None])
+        ctx.has = (cols is not None, mul is not None)
+        return ops._sparse_project_fwd(x, matrix, cols, mul, add, out_dtype)
+
+    @staticmethod
+    def backward(ctx, d_y: Tensor):
+        saved = list(ctx.saved_tensors)
+        cols = saved.pop(0) if ctx.has[0] else None
+        mul = saved.pop(0) if ctx.has[1] else None
+        g = ops._sparse_project_fwd(d_y.contiguous(), ctx.matrix.t, None, mul, None, torch.float32)  # (A^T d_y) * mul, fp32
+        if cols is None:
+            d_x = g.to(ctx.x_dtype)
+        else:
+            d_x = torch.zeros(ctx.x_shape, dtype=torch.float32, device=d_y.device)
+            d_x.index_add_(-1, cols.long(), g)  # (add: a column may be selected more than once) in fp32, rounded once
+            d_x = d_x.to(ctx.x_dtype)
+        return d_x, None, None, None, None, None
+
+
 class GatherRowsFunction(torch.autograd.Function):
     """out[i] = x[idx[i]]; backward: d_x[r] = sum of d_out rows with idx == r (fp32 accumulation)."""
 

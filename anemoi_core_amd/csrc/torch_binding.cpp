@@ -287,6 +287,40 @@ std::tuple<Tensor, Tensor> window_attention(const Tensor& q, const Tensor& k, co
   return {out, lse};
 }
 
+// y = A f(x): constant CSR matrix times node rows, column selection and affine map folded in            (anemoi_sparse_project_fwd)
+Tensor sparse_project(const Tensor& x, const Tensor& indptr, const Tensor& indices, const Tensor& w, const OptTensor& cols, const OptTensor& mul,
+                      const OptTensor& add, bool out_fp32) {
+  on_current_device(x);
+  const auto dev = x.device();
+  TORCH_CHECK_VALUE(x.dim() == 3 || x.dim() == 4, "sparse_project: x must be [batch, n_src, V] or [outer, inner, n_src, V], got ", x.dim(), " dimensions");
+  TORCH_CHECK_VALUE(x.size(-1) <= 1 || x.stride(-1) == 1, "sparse_project: the last dimension of x must be contiguous");
+  const bool two = x.dim() == 4;
+  TORCH_CHECK_VALUE(indptr.scalar_type() == at::kInt && indices.scalar_type() == at::kInt && w.scalar_type() == at::kFloat && indptr.dim() == 1 &&
+                        indices.dim() == 1 && w.dim() == 1 && indptr.size(0) >= 1 && indices.size(0) == w.size(0) && indptr.is_contiguous() &&
+                        indices.is_contiguous() && w.is_contiguous(),
+                    "sparse_project: indptr [n_dst + 1] / indices [nnz] must be contiguous int32 and w [nnz] contiguous fp32");
+  TORCH_CHECK_VALUE(indptr.device() == dev && indices.device() == dev && w.device() == dev, "sparse_project: the matrix must be on x's device");
+  const int64_t inner = two ? x.size(1) : 1, B = x.size(0) * inner, n_src = x.size(-2), V = x.size(-1), n_dst = indptr.size(0) - 1;
+  TORCH_CHECK_VALUE(inner >= 1 || B == 0, "sparse_project: empty inner dimension");
+  const bool has_cols = cols.has_value() && cols->defined();
+  const int64_t C = has_cols ? cols->size(0) : V;
+  if (has_cols) TORCH_CHECK_VALUE(cols->device() == dev, "sparse_project: cols must be on x's device");
+  for (const OptTensor* t : {&mul, &add})
+    if (t->has_value() && (*t)->defined()) TORCH_CHECK_VALUE((*t)->device() == dev, "sparse_project: mul / add must be on x's device");
+  const int64_t ldx = n_src > 1 ? x.stride(-2) : std::max<int64_t>(V, x.stride(-2));
+  const int64_t bsx = x.size(0) > 1 ? x.stride(0) : 0, bsx_in = (two && inner > 1) ? x.stride(1) : 0;
+  TORCH_CHECK_VALUE(ldx >= V && bsx >= 0 && bsx_in >= 0, "sparse_project: x must have non-negative batch strides and a row stride of at least its width");
+  Tensor y = two ? at::empty({x.size(0), inner, n_dst, C}, out_fp32 ? x.options().dtype(at::kFloat) : x.options())
+                 : at::empty({B, n_dst, C}, out_fp32 ? x.options().dtype(at::kFloat) : x.options());
+  check(anemoi_sparse_project_fwd(x.data_ptr(), ldx, bsx, (int32_t)std::max<int64_t>(inner, 1), bsx_in, (int32_t)n_src, (int32_t)V, indptr.data_ptr<int32_t>(), indices.data_ptr<int32_t>(),
+                                  w.data_ptr<float>(), static_cast<const int32_t*>(vec(cols, "cols", C, at::kInt)),
+                                  static_cast<const float*>(vec(mul, "mul", C, at::kFloat)), static_cast<const float*>(vec(add, "add", C, at::kFloat)),
+                                  y.data_ptr(), C, n_dst * C, (int32_t)B, (int32_t)n_dst, (int32_t)C, dt_of(x), out_fp32 ? ANEMOI_F32 : dt_of(x),
+                                  cur_stream()),
+        "sparse_project_fwd");
+  return y;
+}
+
 [[noreturn]] void no_cpu() {
   TORCH_CHECK(false, "anemoi_core_amd kernels run on an MI355X (ROCm) device only; got a CPU tensor. There is no CPU fallback in the product path.");
 }
@@ -306,6 +340,7 @@ TORCH_LIBRARY(anemoi_hip, m) {
   m.def("linear_ln_folded(Tensor x, Tensor w_scaled, Tensor c, Tensor d, Tensor stats, float eps, int act) -> Tensor");
   m.def("window_attention(Tensor q, Tensor k, Tensor v, int num_heads, int window, float scale, float softcap, Tensor? alibi_slopes, "
         "int batch_size, bool return_lse) -> (Tensor, Tensor)");
+  m.def("sparse_project(Tensor x, Tensor indptr, Tensor indices, Tensor w, Tensor? cols, Tensor? mul, Tensor? add, bool out_fp32) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(anemoi_hip, CUDA, m) {  // the ROCm build of PyTorch dispatches HIP tensors under the CUDA key
@@ -318,6 +353,7 @@ TORCH_LIBRARY_IMPL(anemoi_hip, CUDA, m) {  // the ROCm build of PyTorch dispatch
   m.impl("linear_with_row_stats", &linear_with_row_stats);
   m.impl("linear_ln_folded", &linear_ln_folded);
   m.impl("window_attention", &window_attention);
+  m.impl("sparse_project", &sparse_project);
 }
 
 TORCH_LIBRARY_IMPL(anemoi_hip, CPU, m) {  // fail loudly, like the ctypes path
@@ -327,4 +363,6 @@ TORCH_LIBRARY_IMPL(anemoi_hip, CPU, m) {  // fail loudly, like the ctypes path
   m.impl("cond_layer_norm_proj", [](const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, const OptTensor&) -> Tensor { no_cpu(); });
   m.impl("window_attention", [](const Tensor&, const Tensor&, const Tensor&, int64_t, int64_t, double, double, const OptTensor&, int64_t,
                                 bool) -> std::tuple<Tensor, Tensor> { no_cpu(); });
+  m.impl("sparse_project", [](const Tensor&, const Tensor&, const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
+                              bool) -> Tensor { no_cpu(); });
 }

@@ -243,3 +243,50 @@ def build_synthetic_graph(data_grid: str = "o96", hidden_resolution: int = 5, *,
         dec_edge_attr=edge_attributes(hidden, data, dec),
         meta={"data_grid": data_grid, "hidden_resolution": hidden_resolution},
     )
+
+
+# --------------------------------------------------------------------------- truncation pair (layers/residual.py TruncatedConnection)
+def gaussian_weights(src_latlon: np.ndarray, dst_latlon: np.ndarray, edge_index: np.ndarray, sigma: float) -> np.ndarray:
+    """exp(-d^2 / (2 sigma^2)) of the chord distance d of every edge, fp32 [M]."""
+    d = np.linalg.norm(latlon_to_xyz(src_latlon[edge_index[0]]) - latlon_to_xyz(dst_latlon[edge_index[1]]), axis=1)
+    return np.exp(-0.5 * (d / sigma) ** 2).astype(np.float32)
+
+
+def build_truncation_pair(data_latlon: np.ndarray, coarse_grid: str = "o48", *, k: int = 3, down: str = "cutoff", cutoff_factor: float = 1.0,
+                          max_neighbours: int = 64) -> dict:
+    """The two edge sets of a truncated residual between a data grid and a coarser octahedral grid ``coarse_grid`` ("o<n>"):
+
+    * ``down`` (data -> truncation): "cutoff" - for every coarse node the data nodes within ``cutoff_factor`` * the coarse grid's reference
+      distance (a near-uniform count per row), or "knn" - its ``k`` nearest data nodes;
+    * ``up`` (truncation -> data): the ``k`` nearest coarse nodes of every data node.
+
+    Weights are Gaussians of the chord distance with sigma = the coarse grid's reference distance, NOT normalised: ``row_normalize=True`` of the
+    residual does that.  Returns {"latlon", "down_edge_index", "down_weight", "up_edge_index", "up_weight"} (edge lists dst-sorted)."""
+    data = np.asarray(data_latlon, dtype=np.float64)
+    coarse = octahedral_grid(int(coarse_grid.lower()[1:]))
+    sigma = reference_distance(coarse)
+    dn = cutoff_edges(data, coarse, cutoff_factor, max_neighbours) if down == "cutoff" else knn_edges(data, coarse, k)
+    up = knn_edges(coarse, data, k)
+    return {"latlon": coarse.astype(np.float32), "down_edge_index": dn, "down_weight": gaussian_weights(data, coarse, dn, sigma),
+            "up_edge_index": up, "up_weight": gaussian_weights(coarse, data, up, sigma)}
+
+
+def to_graph_data(g: SyntheticGraph, truncation: Optional[dict] = None, weight_attribute: str = "gauss_weight"):
+    """The synthetic graph as a ``graphs/io.GraphData`` (the HeteroData-shaped container the models accept), with the node set
+    "truncation" and the edge sets ("data", "to", "truncation") / ("truncation", "to", "data") of ``build_truncation_pair`` if given."""
+    import torch
+
+    from .io import GraphData
+
+    t = torch.from_numpy
+    nodes = {"data": {"x": t(g.data_latlon), "num_nodes": g.num_data}, "hidden": {"x": t(g.hidden_latlon), "num_nodes": g.num_hidden}}
+    edges = {}
+    for key, ei, ea in ((("data", "to", "hidden"), g.enc_edge_index, g.enc_edge_attr), (("hidden", "to", "hidden"), g.proc_edge_index, g.proc_edge_attr),
+                        (("hidden", "to", "data"), g.dec_edge_index, g.dec_edge_attr)):
+        if ei is not None:
+            edges[key] = {"edge_index": t(ei), "edge_length": t(ea[:, :1].copy()), "edge_dirs": t(ea[:, 1:].copy())}
+    if truncation is not None:
+        nodes["truncation"] = {"x": t(truncation["latlon"]), "num_nodes": int(truncation["latlon"].shape[0])}
+        edges[("data", "to", "truncation")] = {"edge_index": t(truncation["down_edge_index"]), weight_attribute: t(truncation["down_weight"])[:, None]}
+        edges[("truncation", "to", "data")] = {"edge_index": t(truncation["up_edge_index"]), weight_attribute: t(truncation["up_weight"])[:, None]}
+    return GraphData(nodes, edges)

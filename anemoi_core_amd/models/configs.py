@@ -24,11 +24,12 @@ def make_data_indices(n_vars_in, n_prog):
     return {"data": ns}
 
 
-def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="anemoi.models.layers", window_size=512):
+def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="anemoi.models.layers", window_size=512, residual=None):
     """Same nested config the reference model is built from (tests/golden/make_golden.py); by default it even carries
     the REFERENCE's ``_target_`` strings, which the model retargets to the MI355X classes.  ``kind``: "gt", "gnn" or "transformer"
     (GraphTransformer mappers around a TransformerProcessor with ``window_size``, the reference's transformer.yaml; its graph needs no
-    hidden -> hidden edges)."""
+    hidden -> hidden edges).  ``residual``: the ``model.residual`` entry (default: the SkipConnection of the last step), e.g.
+    ``truncated_residual_config()``."""
     common = dict(cpu_offload=False, gradient_checkpointing=False, layer_kernels=None, trainable_size=trainable,
                   sub_graph_edge_attributes=["edge_length", "edge_dirs"])
     if kind == "transformer":
@@ -57,19 +58,27 @@ def model_config(kind, num_channels, num_layers, num_heads, trainable, prefix="a
             "trainable_parameters": {"data": trainable, "hidden": trainable, "data2hidden": trainable, "hidden2data": trainable, "hidden2hidden": trainable},
             "model": {"hidden_nodes_name": "hidden", "latent_skip": True},
             "encoder": enc, "processor": proc, "decoder": dec,
-            "residual": {"_target_": "anemoi.models.layers.residual.SkipConnection", "step": -1},
+            "residual": dict(residual) if residual is not None else {"_target_": "anemoi.models.layers.residual.SkipConnection", "step": -1},
             "bounding": [],
         }
     }
 
 
+def truncated_residual_config(prefix="anemoi.models.layers", *, data="data", truncation="truncation", edge_weight_attribute=None,
+                              src_node_weight_attribute=None, row_normalize=False, **extra):
+    """The ``model.residual`` entry of a TruncatedConnection over pre-resolved edge sets (training config model/residual: truncated)."""
+    return dict({"_target_": f"{prefix}.residual.TruncatedConnection", "truncation_down_edges_name": (data, "to", truncation),
+                 "truncation_up_edges_name": (truncation, "to", data), "edge_weight_attribute": edge_weight_attribute,
+                 "src_node_weight_attribute": src_node_weight_attribute, "autocast": False, "row_normalize": row_normalize}, **extra)
+
+
 def ens_model_config(kind, num_channels, num_layers, num_heads, trainable, *, noise_channels_dim=4, noise_mlp_hidden_dim=32, noise_std=1,
-                     injector="NoiseConditioning", condition_on_residual=False, prefix="anemoi.models.layers", window_size=512):
+                     injector="NoiseConditioning", condition_on_residual=False, prefix="anemoi.models.layers", window_size=512, residual=None):
     """The nested config of the reference's AnemoiEnsModelEncProcDec (training/src/anemoi/training/config/model/graphtransformer_ens.yaml,
     transformer_ens.yaml): ``model_config(kind, ...)`` ("gt" or "transformer") plus ``condition_on_residual`` and the ``noise_injector``.
     ``injector``: "NoiseConditioning" (the noise conditions the processor, whose ``layer_kernels.LayerNorm`` becomes a ConditionalLayerNorm of
     ``condition_shape = noise_channels_dim``), "NoiseInjector" (projected into the latent; plain LayerNorms) or "NoOpNoiseInjector"."""
-    cfg = model_config(kind, num_channels, num_layers, num_heads, trainable, prefix=prefix, window_size=window_size)
+    cfg = model_config(kind, num_channels, num_layers, num_heads, trainable, prefix=prefix, window_size=window_size, residual=residual)
     m = cfg["model"]
     m["condition_on_residual"] = condition_on_residual
     inj = {"_target_": f"{prefix}.ensemble.{injector}"}

@@ -5,8 +5,9 @@
 
 ``model_config`` is the reference's nested config (attribute dict).  ``_target_`` strings may name either this
 package's classes or the reference's ``anemoi.models.layers.*`` classes (rewritten to the MI355X implementations), so an
-existing config selects the HIP path without edits.  Residual = SkipConnection (step); boundings: all eight classes of
-layers/bounding.py, run as one in-place column program.
+existing config selects the HIP path without edits.  Residual: ``model.residual`` is instantiated per dataset as the reference does
+(models/base.py:244-258) - SkipConnection (step) or TruncatedConnection (layers/residual.py; any other target raises); boundings: all
+eight classes of layers/bounding.py, run as one in-place column program.
 """
 from __future__ import annotations
 
@@ -44,7 +45,10 @@ def _retarget(cfg) -> dict:
 
 def _graph_views(graph_data):
     """Accept the synthetic generator's ``SyntheticGraph`` or a HeteroData-like object (``g[name].x``,
-    ``g[(src,'to',dst)].edge_index / edge_length / edge_dirs``)."""
+    ``g[(src,'to',dst)].edge_index / edge_length / edge_dirs``).  Returns (node coordinates by name, edge stores by type, the graph the
+    residual connection is built from): a HeteroData-like graph or a ``graphs/io.GraphData`` is handed to the residual as it is - it reads the
+    truncation node set (``num_nodes``, node attributes) and the truncation edge stores with their weight attribute by name; a
+    ``SyntheticGraph`` has no such sets (None)."""
     if hasattr(graph_data, "enc_edge_index"):  # SyntheticGraph
         g = graph_data
         nodes = {"data": torch.as_tensor(g.data_latlon), "hidden": torch.as_tensor(g.hidden_latlon)}
@@ -52,7 +56,7 @@ def _graph_views(graph_data):
         edges = {("data", "to", "hidden"): mk(g.enc_edge_index, g.enc_edge_attr),
                  ("hidden", "to", "hidden"): None if g.proc_edge_index is None else mk(g.proc_edge_index, g.proc_edge_attr),
                  ("hidden", "to", "data"): mk(g.dec_edge_index, g.dec_edge_attr)}
-        return nodes, edges
+        return nodes, edges, None
 
     class _Edges(dict):
         def __missing__(self, key):
@@ -64,7 +68,7 @@ def _graph_views(graph_data):
             return graph_data[key]
 
     nodes = {name: torch.as_tensor(graph_data[name].x) for name in graph_data.node_types}
-    return nodes, _Edges()
+    return nodes, _Edges(), graph_data
 
 
 class AnemoiModelEncProcDec(nn.Module):
@@ -83,7 +87,7 @@ class AnemoiModelEncProcDec(nn.Module):
         self.latent_skip = mc.model.latent_skip
         if not isinstance(self._graph_name_hidden, str):
             raise NotImplementedError("hierarchical hidden node lists belong to another model family")
-        nodes, edges = _graph_views(graph_data)
+        nodes, edges, residual_graph = _graph_views(graph_data)
         tp = dict(mc.trainable_parameters)
         self.node_attributes = NamedNodesAttributes(
             {**{ds: tp.get("data", 0) for ds in self.dataset_names}, self._graph_name_hidden: tp.get("hidden", 0)},
@@ -91,8 +95,7 @@ class AnemoiModelEncProcDec(nn.Module):
         )
         self._calculate_shapes_and_indices(data_indices)
         self._build_networks(mc, edges)
-        res = mc.get("residual", {}) or {}
-        self._skip_step = int(res.get("step", -1))
+        self._build_residual(mc, residual_graph)
         self.boundings = self._build_boundings(mc.get("bounding", []) or [])
         self._pad_zeros = self._hidden_padded = None
         self._bound_tables: dict = {}
@@ -146,6 +149,58 @@ class AnemoiModelEncProcDec(nn.Module):
             self.decoder[ds] = instantiate(_retarget(mc.decoder), _recursive_=False, in_channels_src=self.num_channels,
                                            in_channels_dst=self.target_dim[ds], hidden_dim=self.num_channels,
                                            out_channels_dst=self.output_dim[ds], edge_dim=self.decoder_graph_provider[ds].edge_dim)
+
+    def _build_residual(self, mc, graph) -> None:
+        """models/base.py:244-258: ``model.residual`` instantiated per dataset.  An absent or empty entry is the SkipConnection of the last
+        step.  A TruncatedConnection gets the device-resident column vectors of its compact skip: the prognostic input columns it projects and
+        the map from output column to compact column (non-persistent buffers: nothing is added to the state_dict)."""
+        from ..layers.residual import SkipConnection, TruncatedConnection
+
+        cfg = mc.get("residual", None) or {}
+        chunks = (mc.get("sparse_projector", None) or {}).get("num_chunks", 1)
+        self.residual = nn.ModuleDict()
+        for ds in self.dataset_names:
+            if not cfg or "_target_" not in cfg:
+                self.residual[ds] = SkipConnection(step=int(cfg.get("step", -1)))
+                continue
+            target = _retarget(cfg)["_target_"]
+            if target not in (_OUR_PREFIX + "residual.SkipConnection", _OUR_PREFIX + "residual.TruncatedConnection"):
+                raise NotImplementedError(f"residual '{cfg['_target_']}' is not implemented; supported: SkipConnection, TruncatedConnection "
+                                          "(layers/residual.py)")
+            stats = self.statistics.get(ds) if isinstance(self.statistics, dict) else self.statistics
+            self.residual[ds] = instantiate(_retarget(cfg), _recursive_=False, graph=graph, data_node_name=ds if len(self.dataset_names) > 1 else "data",
+                                            statistics=stats, data_indices=self.data_indices[ds], dataset_name=ds,
+                                            sparse_projector_num_chunks=chunks)
+            if isinstance(self.residual[ds], TruncatedConnection):
+                out_idx, in_idx = self._internal_output_idx[ds], self._internal_input_idx[ds]
+                cmap = torch.full((self.num_output_channels[ds],), -1, dtype=torch.int32)
+                cmap[torch.tensor(out_idx, dtype=torch.long)] = torch.arange(len(out_idx), dtype=torch.int32)
+                self.register_buffer(f"_col_map_c_{ds}", cmap if len(set(out_idx)) == len(out_idx) else None, persistent=False)
+                self.register_buffer(f"_prog_cols_{ds}", torch.tensor(in_idx, dtype=torch.int32), persistent=False)
+        first = self.residual[self.dataset_names[0]]
+        self._skip_step = int(first.step) if isinstance(first, SkipConnection) else -1
+        self._truncated = {ds: isinstance(self.residual[ds], TruncatedConnection) for ds in self.dataset_names}
+        self._skip_programs: dict = {}
+
+    def _truncated_skip(self, ds: str, x_last: Tensor, raw: bool, norm, shard_sizes) -> Tensor:
+        """The truncated residual of one forward: x_last [batch, ensemble, grid, vars] (the last input step, read in place) -> the
+        NORMALISED compact skip [batch, ensemble, grid, prognostic columns].  ``raw``: x_last is the raw batch (``predict_step`` fused the
+        input normaliser), whose column program then runs on every value the down projection gathers."""
+        if shard_sizes is not None:
+            raise NotImplementedError("TruncatedConnection with a sharded data grid (grid_shard_sizes) needs the reference's grid-to-channel "
+                                      "transposes (layers/residual.py:287-293) and is not implemented; pass the whole grid")
+        cols = getattr(self, f"_prog_cols_{ds}")
+        mul = add = None
+        if raw:
+            # one entry per (dataset, device), replaced when the normaliser or its state changes.  The gather below runs on the first
+            # forward with that normaliser: run one eager predict_step before capturing it, as for the bounding tables.
+            slot, state = (ds, str(x_last.device)), (id(norm), norm._norm_mul._version, norm._norm_add._version)
+            hit = self._skip_programs.get(slot)
+            if hit is None or hit[0] != state:
+                m, a = norm.column_program(x_last.shape[-1])
+                hit = self._skip_programs[slot] = (state, (m[cols.long()].contiguous(), a[cols.long()].contiguous()))
+            mul, add = hit[1]
+        return self.residual[ds].project(x_last, cols=cols, mul=mul, add=add)
 
     def _build_boundings(self, cfgs) -> nn.ModuleDict:
         """models/base.py:94-97 / layers/bounding.py:312-400: one ModuleList per dataset, configuration order."""
@@ -213,12 +268,13 @@ class AnemoiModelEncProcDec(nn.Module):
         return self._hidden_padded[1]
 
     def _assemble_output(self, x_out: Tensor, x_skip: Tensor, batch_size: int, ensemble_size: int, dtype, ds: str, norm=None,
-                         skip_is_raw: bool = False, denorm=None) -> Tensor:
+                         skip_is_raw: bool = False, denorm=None, compact: bool = False) -> Tensor:
         """``norm`` / ``skip_is_raw``: x_skip is the RAW input and is normalised inside the residual kernel; ``denorm``: the
-        output InputNormalizer whose inverse transform is appended to the column program of the boundings."""
+        output InputNormalizer whose inverse transform is appended to the column program of the boundings; ``compact``: x_skip holds the
+        prognostic columns only, in their order (the truncated residual)."""
         N = x_out.shape[0] // (batch_size * ensemble_size)
         in_idx, out_idx = getattr(self, f"_in_idx_{ds}"), getattr(self, f"_out_idx_{ds}")
-        col_map = getattr(self, f"_col_map_{ds}")
+        col_map = getattr(self, f"_col_map_c_{ds}" if compact else f"_col_map_{ds}")
         fusable = (col_map is not None and batch_size == 1 and ensemble_size == 1 and self.n_step_output == 1 and x_out.is_cuda
                    and not (torch.is_grad_enabled() and (x_out.requires_grad or x_skip.requires_grad)))
         fused_norm = fusable and skip_is_raw and x_skip.dtype == dtype and dtype in (x_out.dtype, torch.float32)
@@ -234,7 +290,7 @@ class AnemoiModelEncProcDec(nn.Module):
             x_out = x_out.reshape(batch_size, ensemble_size, N, self.n_step_output, -1).permute(0, 3, 1, 2, 4).to(dtype=dtype).clone()
             # SkipConnection._expand_time (layers/residual.py:53-57): the skip is repeated over the output steps
             skip = x_skip.unsqueeze(1).expand(-1, self.n_step_output, -1, -1, -1)
-            x_out.index_add_(-1, out_idx, skip.index_select(-1, in_idx).to(dtype))
+            x_out.index_add_(-1, out_idx, (skip if compact else skip.index_select(-1, in_idx)).to(dtype))
         if len(self.boundings[ds]) or denorm is not None:
             # all configured boundings (configuration order) and, fused, the output de-normalisation as ONE in-place column program
             from ..layers.bounding import apply_program_torch, program_tables
@@ -290,6 +346,8 @@ class AnemoiModelEncProcDec(nn.Module):
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
             norm_in, norm_out = (_fused_norm or {}).get(ds, (None, None))
             x_data_latent, x_skip, raw = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds, norm=norm_in)
+            if self._truncated[ds]:  # once per dataset and forward: down (columns, normaliser), up; the skip is then normalised
+                x_skip, raw = self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data), False
             skips[ds], data_shards[ds] = (x_skip, raw, norm_in, norm_out), shard_sizes_data
             ea, ei, es = self.encoder_graph_provider[ds].get_edges(batch_size=batch_size, model_comm_group=model_comm_group)
             info = BipartiteGraphShardInfo(src_nodes=shard_sizes_data, dst_nodes=shard_sizes_hidden, edges=es)
@@ -325,7 +383,7 @@ class AnemoiModelEncProcDec(nn.Module):
                                      edge_index=ei, model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds], **chain_kw)
             x_skip, raw, norm_in, norm_out = skips[ds]
             out[ds] = self._assemble_output(x_out, x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=norm_in, skip_is_raw=raw,
-                                            denorm=norm_out)
+                                            denorm=norm_out, compact=self._truncated[ds])
         return out
 
     # -- predict_step (models/base.py:303-391) ----------------------------------------------------------------------------

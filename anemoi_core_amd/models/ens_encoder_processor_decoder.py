@@ -53,10 +53,12 @@ class AnemoiEnsModelEncProcDec(AnemoiModelEncProcDec):
         B, T, E, N, V = x.shape
         x = x.to(node_attr.dtype)
         x_skip = x[:, self._skip_step, ...]  # SkipConnection: [batch, ensemble, grid, vars]; repeated over the output steps where it is added
+        if self._truncated[ds]:  # TruncatedConnection: the prognostic columns only, coarse-grained and reconstructed (two launches)
+            x_skip = self._truncated_skip(ds, x_skip, False, None, shard_sizes)
         flat = x.permute(0, 2, 3, 1, 4).reshape(B * E * N, T * V)  # "(batch ensemble grid) (time vars)"
         cols = [flat, node_attr, torch.full((B * E * N, 1), float(fcstep), dtype=flat.dtype, device=flat.device)]
         if self.condition_on_residual:
-            cols.append(x_skip.reshape(B * E * N, V))
+            cols.append(x_skip.reshape(B * E * N, -1))  # (the compact columns of a truncated residual)
         return torch.cat(cols, dim=-1), x_skip
 
     @scoped_forward
@@ -107,7 +109,8 @@ class AnemoiEnsModelEncProcDec(AnemoiModelEncProcDec):
             x_out = self.decoder[ds]((x_latent_proc, data_latents[ds]), batch_size=batch_ens_size, shard_info=info, edge_attr=ea, edge_index=ei,
                                      model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds])
             # "(bs e n) (time vars) -> bs time e n vars", the residual on the prognostic columns, the boundings: the base class's generic path
-            out[ds] = AnemoiModelEncProcDec._assemble_output(self, x_out, skips[ds], batch_size, ensemble_size, x[ds].dtype, ds)
+            out[ds] = AnemoiModelEncProcDec._assemble_output(self, x_out, skips[ds], batch_size, ensemble_size, x[ds].dtype, ds,
+                                                             compact=self._truncated[ds])
         return out
 
     def predict_step(self, *args, **kwargs):

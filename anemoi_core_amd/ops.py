@@ -424,6 +424,125 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
     return (out, lse) if return_lse else out
 
 
+# ------------------------------------------------------------------------------------------ sparse projection
+@dataclass(frozen=True)
+class SparseMatrix:
+    """A constant CSR matrix [n_rows, n_cols] (rows = destination nodes, columns = source nodes): int32 ``indptr`` [n_rows + 1] and
+    ``indices`` [nnz], fp32 ``values`` [nnz]; ``t``: its transpose (the matrix of the backward pass), built once on the host."""
+
+    indptr: Tensor
+    indices: Tensor
+    values: Tensor
+    n_rows: int
+    n_cols: int
+    t: Optional["SparseMatrix"] = None
+
+    @property
+    def nnz(self) -> int:
+        return self.indices.shape[0]
+
+    def to(self, device) -> "SparseMatrix":
+        mv = lambda a: a.to(device)  # noqa: E731
+        return SparseMatrix(mv(self.indptr), mv(self.indices), mv(self.values), self.n_rows, self.n_cols, None if self.t is None else self.t.to(device))
+
+
+def build_sparse_matrix(indptr, indices, values, shape: tuple[int, int], with_transpose: bool = True) -> SparseMatrix:
+    """Host-side constructor (CPU tensors or numpy arrays of a CSR matrix): checks the structure ONCE - the kernel trusts it - and builds
+    the transposed copy (stable sort by column: the rows of a column stay in ascending order, the order is a function of the matrix only)."""
+    indptr, indices = torch.as_tensor(indptr).long().reshape(-1), torch.as_tensor(indices).long().reshape(-1)
+    values = torch.as_tensor(values).to(torch.float32).reshape(-1)
+    n_rows, n_cols = int(shape[0]), int(shape[1])
+    if max(n_rows, n_cols, indices.numel()) >= 2**31:
+        raise ValueError("matrix too large for int32 indices")
+    if indptr.numel() != n_rows + 1 or int(indptr[0]) != 0 or int(indptr[-1]) != indices.numel() or bool((indptr[1:] < indptr[:-1]).any()):
+        raise ValueError(f"indptr is not a row pointer of {n_rows} rows over {indices.numel()} entries")
+    if values.numel() != indices.numel():
+        raise ValueError(f"{values.numel()} values for {indices.numel()} indices")
+    if indices.numel() and (int(indices.min()) < 0 or int(indices.max()) >= n_cols):
+        raise ValueError(f"column index outside [0, {n_cols})")
+    i32 = lambda a: a.to(torch.int32).contiguous()  # noqa: E731
+    t = None
+    if with_transpose:
+        rows = torch.repeat_interleave(torch.arange(n_rows), indptr[1:] - indptr[:-1])
+        order = torch.sort(indices, stable=True)[1]
+        tptr = torch.zeros(n_cols + 1, dtype=torch.long)
+        if indices.numel():
+            tptr[1:] = torch.cumsum(torch.bincount(indices, minlength=n_cols), 0)
+        t = SparseMatrix(i32(tptr), i32(rows[order]), values[order].contiguous(), n_cols, n_rows)
+    return SparseMatrix(i32(indptr), i32(indices), values.contiguous(), n_rows, n_cols, t)
+
+
+def sparse_project(x: Tensor, matrix: SparseMatrix, cols: Optional[Tensor] = None, mul: Optional[Tensor] = None, add: Optional[Tensor] = None,
+                   out_dtype=None) -> Tensor:
+    """y[..., m, c] = sum_e matrix[m, e] * (x[..., e, cols[c]] * mul[c] + add[c]): the projection of SparseProjector
+    (layers/sparse_projector.py:78-104) as one launch.  x: [..., n_src, V], last dimension contiguous, row and batch strides free (a time
+    step of [B, T, E, N, V] is read in place); cols: int32 [C] (default: all V columns); mul / add: fp32 [C]; the result is
+    [..., n_dst, C] in ``out_dtype`` (x's dtype or float32; default x's).  fp32 accumulation in CSR order, bitwise reproducible.
+    Differentiable in x (the adjoint runs the same kernel on ``matrix.t``)."""
+    if _needs_grad(x):
+        from .autograd import SparseProjectFunction
+
+        return SparseProjectFunction.apply(x, matrix, cols, mul, add, out_dtype)
+    return _sparse_project_fwd(x, matrix, cols, mul, add, out_dtype)
+
+
+def _sparse_project_fwd(x: Tensor, matrix: SparseMatrix, cols: Optional[Tensor], mul: Optional[Tensor], add: Optional[Tensor], out_dtype) -> Tensor:
+    if x.dim() < 2 or x.shape[-2] != matrix.n_cols:
+        raise ValueError(f"sparse_project: x {tuple(x.shape)} does not have the matrix's {matrix.n_cols} source rows in its last but one dimension")
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (x.dtype, torch.float32):
+        raise ValueError(f"sparse_project: out_dtype must be {x.dtype} or float32, got {out_dtype}")
+    lead, V = x.shape[:-2], x.shape[-1]
+    if V > 1 and x.stride(-1) != 1:
+        raise ValueError("sparse_project: the last dimension of x must be contiguous")
+    xk = _two_leading(x)  # [outer, inner, n_src, V]: a view; a copy only if the leading dimensions need more than two strides
+    C = V if cols is None else cols.shape[0]
+    ext = _ext.ops()
+    if ext is not None:
+        y = ext.sparse_project(xk, matrix.indptr, matrix.indices, matrix.values, cols, mul, add, out_dtype == torch.float32)
+        return y.view(*lead, matrix.n_rows, C)
+    _dev(xk, matrix.indptr, matrix.indices, matrix.values, cols, mul, add)
+    _dt(xk)
+    if matrix.indptr.dtype != torch.int32 or matrix.indices.dtype != torch.int32 or matrix.values.dtype != torch.float32:
+        raise ValueError("sparse_project: the matrix must be int32 / int32 / float32")
+    outer, inner = xk.shape[0], xk.shape[1]
+    ldx = xk.stride(2) if matrix.n_cols > 1 else max(V, xk.stride(2))
+    bsx, bsx_in = (xk.stride(0) if outer > 1 else 0), (xk.stride(1) if inner > 1 else 0)
+    if ldx < V or bsx < 0 or bsx_in < 0:
+        raise ValueError("sparse_project: x must have non-negative batch strides and a row stride of at least its width")
+    B = outer * inner
+    y = torch.empty((B, matrix.n_rows, C), dtype=out_dtype, device=x.device)
+    rc = _lib.load().anemoi_sparse_project_fwd(xk.data_ptr(), ldx, bsx, max(inner, 1), bsx_in, matrix.n_cols, V, matrix.indptr.data_ptr(),
+                                               matrix.indices.data_ptr(), matrix.values.data_ptr(), _vec(cols, "cols", C, torch.int32),
+                                               _vec(mul, "mul", C, torch.float32), _vec(add, "add", C, torch.float32), y.data_ptr(), C,
+                                               matrix.n_rows * C, B, matrix.n_rows, C, _DT[xk.dtype], _DT[out_dtype], _stream())
+    _lib.check(rc, "sparse_project_fwd")
+    return y.view(*lead, matrix.n_rows, C)
+
+
+def _two_leading(x: Tensor) -> Tensor:
+    """x [..., n, V] as [outer, inner, n, V] without copying when its leading dimensions can be addressed by two strides (adjacent dimensions
+    that share a stride are merged; size-1 dimensions are dropped): every [B, E] step slice of [B, T, E, N, V] qualifies.  Otherwise a
+    contiguous copy."""
+    n, V = x.shape[-2], x.shape[-1]
+    groups: list = []  # [size, stride] of merged leading dimensions, outermost first
+    for size, stride in zip(x.shape[:-2], x.stride()[:-2]):
+        if size == 1:
+            continue
+        if groups and groups[-1][1] == size * stride:
+            groups[-1] = [groups[-1][0] * size, stride]
+        else:
+            groups.append([size, stride])
+    if len(groups) > 2 or x.numel() == 0:
+        lead = 1
+        for d in x.shape[:-2]:
+            lead *= d
+        return x.reshape(1, lead, n, V)
+    while len(groups) < 2:
+        groups.insert(0, [1, 0])
+    return x.as_strided((groups[0][0], groups[1][0], n, V), (groups[0][1], groups[1][1], x.stride(-2), x.stride(-1)), x.storage_offset())
+
+
 def cond_layer_norm(x: Tensor, scale: Tensor, shift: Tensor, eps: float = 1e-5) -> Tensor:
     """y = LayerNorm(x) * (scale + 1) + shift over the last dim, per-row scale / shift [N, D] (column slices allowed)."""
     if _needs_grad(x, scale, shift):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 15
+#define ANEMOI_HIP_ABI_VERSION 16
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -537,6 +537,23 @@ int anemoi_gnn_node_chain_segsum_fwd(const void* x, int64_t ld_x, const void* ed
 int anemoi_window_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
                                 float* lse, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window, float scale, float softcap,
                                 const float* alibi_slopes, anemoi_dtype_t dtype, void* stream);
+
+/* Sparse projection of node rows by a constant CSR matrix, forward (and, on the transposed matrix, backward).
+ * Replaces: SparseProjector._project_flattened (layers/sparse_projector.py:78-104: permute copy, torch.sparse.mm, permute copy) as
+ * TruncatedConnection uses it twice (layers/residual.py:275-296), with the column selection of the residual's prognostic variables and the
+ * input normaliser folded in:
+ *     y[b, m, c] = sum_{e in [indptr[m], indptr[m+1])} w[e] * f(x[b, indices[e], cols[c]]),   f(v) = v * mul[c] + add[c]
+ * x: [batch, n_src, n_cols_x] of x_dtype, row stride ldx in elements; the batch index b = bo * batch_inner + bi addresses x at
+ * bo * bsx + bi * bsx_inner (two leading dimensions with strides of their own, batch_inner >= 1 dividing batch: the [B, E] of a time-step slice
+ * of [B, T, E, N, V] is read in place); y: [batch, n_dst, C] of y_dtype (fp32 or x_dtype), row stride ldy, batch stride bsy; indptr [n_dst + 1], indices [nnz] int32 and
+ * w [nnz] fp32: the CSR matrix, rows = destinations; cols: int32 [C] or NULL (the first C columns); mul, add: fp32 [C] or NULL (1 and 0).
+ * Entries are summed in CSR order in fp32 without atomics (bitwise reproducible); a row without entries yields zeros; an index outside
+ * [0, n_src) or a column outside [0, n_cols_x) contributes nothing and is never dereferenced. */
+int anemoi_sparse_project_fwd(const void* x, int64_t ldx, int64_t bsx, int32_t batch_inner, int64_t bsx_inner, int32_t n_src, int32_t n_cols_x,
+                              const int32_t* indptr,
+                              const int32_t* indices, const float* w, const int32_t* cols, const float* mul, const float* add, void* y,
+                              int64_t ldy, int64_t bsy, int32_t batch, int32_t n_dst, int32_t C, anemoi_dtype_t x_dtype, anemoi_dtype_t y_dtype,
+                              void* stream);
 
 #ifdef __cplusplus
 }
