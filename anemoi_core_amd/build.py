@@ -65,13 +65,11 @@ def build_library(force: bool = False, verbose: bool = True, extra_flags: tuple[
     objdir = os.path.join(LIBDIR, "obj_exp" if experiments else "obj")
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "chain_core.h"), os.path.join(CSRC, "chain2_core.h"), os.path.join(CSRC, "gnn_chain_args.h"), os.path.join(INCLUDE, "anemoi_hip.h")]
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC, "-Wall", "-Wno-unused-function", *extra_flags]
     sources, libpath = SOURCES, LIBPATH
     inc_dirs = [CSRC, INCLUDE] + ([os.path.join(CSRC, "experiments")] if experiments else [])
     if experiments:
         flags += ["-DANEMOI_EXPERIMENTS", "-I", os.path.join(CSRC, "experiments")]
-        headers.append(os.path.join(CSRC, "experiments", "anemoi_hip_experiments.h"))
         sources, libpath = SOURCES + EXPERIMENT_SOURCES, EXP_LIBPATH
 
     def compile_one(src: str) -> str:

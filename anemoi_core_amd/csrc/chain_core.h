@@ -1,7 +1,9 @@
-// Shared device code of the row-resident chain kernels (gt_chain.hip: GraphTransformer block; gnn_chain.hip: GraphConv edge / node
-// MLPs).  A workgroup of 8 waves owns a panel of <= 48 rows x 512 channels in LDS (16-byte slots XOR-swizzled by the row); every wave
-// owns a 64-column slab of each GEMM's output and streams its B fragments from a fragment-major weight image straight into a
-// register ring (see gt_chain.hip for the measurements behind each choice).
+// Shared device code of the row-resident chain kernels (gt_chain2 / gt_cluster_chain / gt_rowchain.hip: GraphTransformer block tails and
+// mapper sides; gnn_chain.hip: GraphConv edge / node MLPs).  A workgroup of 8 waves owns a panel of <= 48 rows x 512 channels in LDS
+// (16-byte slots XOR-swizzled by the row); a wave owns a 64-column slab of each GEMM's output (or, role-split, a 128-column one:
+// chain2_core.h) and streams its B fragments from a fragment-major weight image straight into a register ring (see
+// experiments/gt_chain.hip for the measurements behind each choice).  Here: the 64-column GEMM segment, the panel layout, the lanes'
+// coordinates in it, the LayerNorm statistics and the epilogue forms of both wave layouts.
 #pragma once
 #include "common.h"
 
@@ -75,8 +77,10 @@ constexpr int kPanel = 48;                  // panel rows (3 MFMA row bands)
 constexpr int kRowBytes = kCh * 2;          // one 16-bit row in LDS
 constexpr int kBufBytes = kPanel * kRowBytes;
 constexpr int kSlab = 16 * 4096;            // one segment of a wave's weight stream: 16 K-steps x (4 fragments x 1 KiB)
-constexpr int kRedOff = 3 * kBufBytes;      // [48][8][2] fp32 LayerNorm partials
-constexpr int kChainSmem = kRedOff + kPanel * 8 * 2 * 4;
+// LDS map of every kernel of the family: three panel buffers | [48 rows][waves][2] fp32 LayerNorm partials | the per-column vectors
+constexpr int kRedOff = 3 * kBufBytes;
+constexpr int vec_off(int waves) { return kRedOff + kPanel * waves * 2 * 4; }
+constexpr int kChainSmem = vec_off(8);      // (no vectors in LDS: the GraphConv chains keep theirs in registers)
 constexpr int kTlOff = kChainSmem;          // instrumented instantiation only: [8 waves][kTlSlots] stamps, copied out at the end
 
 // a pointer the compiler must keep in scalar registers (it is wave-uniform by construction): the loads then take the
@@ -150,21 +154,55 @@ __device__ __forceinline__ void lds_barrier() {  // LDS writes of all waves visi
   asm volatile("" ::: "memory");
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the panel and its epilogues
+// One layout serves every kernel of the family: row r, 16-byte slot s of a panel buffer sits at panel_off(r, s).  Two wave layouts work on
+// it, told apart by NI, the 16-column blocks a wave owns of each GEMM's output: NI = 4 (eight waves x 64 columns, acc[mi][0..3]) and
+// NI = 8 (four waves x 128 columns, acc[mi][0..7]).  In both, lane = row mi*16 + x, 4 consecutive columns w*16*NI + ni*16 + g*4 + r.
+__device__ __forceinline__ int panel_off(int row, int slot16) { return row * kRowBytes + ((slot16 ^ (row & 15)) << 4); }
+// (the address itself, summed left to right: the row term joins the buffer's wave-uniform base and the swizzled slot stays the only
+// per-lane term, where `buf + panel_off(..)` would carry the row into every lane's offset)
+template <typename B>
+__device__ __forceinline__ B* panel_at(B* buf, int row, int slot16) { return buf + row * kRowBytes + ((slot16 ^ (row & 15)) << 4); }
+template <int NI>
+constexpr int kWaves = kCh / (16 * NI);  // waves that share a row (= partials per row)
+
+// Row streams (panel rows in, output rows out) are touched once per launch.  ANEMOI_CHAIN2_NT (build-time mask): 1 = the loads carry the
+// non-temporal hint, so that in the XCD's L2 they do not push out the WEIGHTS, which all 32 CUs of the XCD read - and, in multi-round
+// launches, read again (res 6 forward -2.4 %); 2 = the stores too (O96 +1.7 %: the attention launch behind reads them - off); 4 = the
+// stores write through (sc1) instead of sitting dirty in this XCD's L2 until the end of the kernel (O96 -0.4 % on one box, 0 on the next).
+// Default 1.
+#ifndef ANEMOI_CHAIN2_NT
+#define ANEMOI_CHAIN2_NT 1
+#endif
+__device__ __forceinline__ u32x4 stream_load(const u32x4* p) {
+  if constexpr ((ANEMOI_CHAIN2_NT & 1) != 0) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+__device__ __forceinline__ void stream_store(u32x4 v, u32x4* p) {
+  if constexpr ((ANEMOI_CHAIN2_NT & 2) != 0) __builtin_nontemporal_store(v, p);
+  else if constexpr ((ANEMOI_CHAIN2_NT & 4) != 0) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");  // write-through
+  else *p = v;
+}
+
 // Per-lane coordinates, re-derived from an OPAQUE copy of the lane id at the start of every phase: the epilogues' address
 // arithmetic (a few dozen registers of LDS / global offsets per phase) is invariant over the panel loop, LICM hoists all of it
 // to the kernel's entry, and the allocator then spills it around the GEMM segments (scratch reloads retire in order behind the
 // weight ring: every reload would drain it).  Behind the barrier the values are computed where they are used.
-struct LaneCtx {
+// (The 128-column layout pins the wave index too, the 64-column one the lane only: each as its kernels were tuned.)
+template <int NI>
+struct LaneCols {
   int x, g;
-  int coff[4];  // LDS byte offset (inside a panel row) of this lane's 4 columns of column block ni: slot = wave*8 + ni*2 + (g>>1), swizzled by the row
+  int coff[NI];  // LDS byte offset (inside a panel row) of this lane's 4 columns of column block ni: slot = w*2*NI + ni*2 + (g>>1), swizzled by the row
 };
-__device__ __forceinline__ LaneCtx lane_ctx(int lane, int wave) {
-  asm volatile("" : "+v"(lane));
-  LaneCtx c;
+template <int NI>
+__device__ __forceinline__ LaneCols<NI> lane_cols(int lane, int w) {
+  if constexpr (NI == 8) asm volatile("" : "+v"(lane), "+s"(w));
+  else asm volatile("" : "+v"(lane));
+  LaneCols<NI> c;
   c.x = lane & 15;
   c.g = lane >> 4;
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) c.coff[ni] = (((wave * 8 + ni * 2 + (c.g >> 1)) ^ c.x) << 4) + (c.g & 1) * 8;
+  for (int ni = 0; ni < NI; ++ni) c.coff[ni] = (((w * 2 * NI + ni * 2 + (c.g >> 1)) ^ c.x) << 4) + (c.g & 1) * 8;
   return c;
 }
 
@@ -176,46 +214,63 @@ __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NB][4]) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// Row statistics of the panel rows held as v[mi][ni][r] (fp32 images of the ROUNDED row values; lane = row mi*16 + x, columns
-// wave*64 + ni*16 + g*4 + r): per-wave (mean, M2) partials through LDS, merged in wave order with Chan's formula (no
-// E[x^2] - mean^2 cancellation).  ONE barrier inside; `red` may be reused after the NEXT barrier of the caller.
+// LayerNorm statistics are the plain fp32 statistics of the ROUNDED 16-bit rows, in two steps with no E[x^2] - mean^2 cancellation:
+// row_partial: (mean, M2) of one row over this wave's 16 NI columns, from the lane's values a[0..NI-1] (fp32 images of the rounded values);
+// every lane of the wave takes part (shuffles), the lanes with g == 0 then store the row's partial as red[row][w] (kWaves<NI> per row);
+template <int NI>
+__device__ __forceinline__ float2 row_partial(const f32x4* a) {
+  float s = 0.f;
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) s += (a[ni][0] + a[ni][1]) + (a[ni][2] + a[ni][3]);
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  const float mw = s * (1.0f / (float)(16 * NI));
+  float q = 0.f;
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float d = a[ni][r] - mw;
+      q = fmaf(d, d, q);
+    }
+  q += __shfl_xor(q, 16, 64);
+  q += __shfl_xor(q, 32, 64);
+  return make_float2(mw, q);
+}
+// merge_partials: the W waves' partials of a row merged in wave order (Chan et al.): M2 = sum M2_w + n_w sum (mean_w - mean)^2
+template <int W>
+__device__ __forceinline__ void merge_partials(const float* red, int row, float eps, float& mu, float& rstd) {
+  static_assert(W == 4 || W == 8, "four 128-column or eight 64-column partials per row");
+  const f32x4* pr = reinterpret_cast<const f32x4*>(red + row * (2 * W));
+  float m2;
+  if constexpr (W == 8) {
+    const f32x4 p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3];
+    mu = (((p0[0] + p0[2]) + (p1[0] + p1[2])) + ((p2[0] + p2[2]) + (p3[0] + p3[2]))) * 0.125f;
+    m2 = ((p0[1] + p0[3]) + (p1[1] + p1[3])) + ((p2[1] + p2[3]) + (p3[1] + p3[3]));
+    const float d0 = p0[0] - mu, d1 = p0[2] - mu, d2 = p1[0] - mu, d3 = p1[2] - mu;
+    const float d4 = p2[0] - mu, d5 = p2[2] - mu, d6 = p3[0] - mu, d7 = p3[2] - mu;
+    m2 = fmaf(64.0f, ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) + ((d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7)), m2);
+  } else {
+    const f32x4 p0 = pr[0], p1 = pr[1];
+    mu = ((p0[0] + p0[2]) + (p1[0] + p1[2])) * 0.25f;
+    const float d0 = p0[0] - mu, d1 = p0[2] - mu, d2 = p1[0] - mu, d3 = p1[2] - mu;
+    m2 = fmaf(128.0f, (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3), (p0[1] + p0[3]) + (p1[1] + p1[3]));
+  }
+  rstd = rsqrtf(m2 * (1.0f / (float)kCh) + eps);
+}
+
+// Row statistics of the panel rows held as v[mi][ni][r] (64-column layout).  ONE barrier inside; `red` may be reused after the NEXT
+// barrier of the caller.
 template <typename T, int NB = 3>
 __device__ __forceinline__ void panel_row_stats(const f32x4 (&v)[NB][4], float eps, float* red, int wave, int x, int g, float (&mean)[NB], float (&rstd)[NB]) {
 #pragma unroll
   for (int mi = 0; mi < NB; ++mi) {
-    float s = 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) s += (v[mi][ni][0] + v[mi][ni][1]) + (v[mi][ni][2] + v[mi][ni][3]);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mw = s * (1.0f / 64.0f);  // mean of this wave's 64 columns of the row
-    float q = 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = v[mi][ni][r] - mw;
-        q = fmaf(d, d, q);
-      }
-    q += __shfl_xor(q, 16, 64);
-    q += __shfl_xor(q, 32, 64);
-    if (g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + x) * 8 + wave) * 2) = make_float2(mw, q);
+    const float2 p = row_partial<4>(v[mi]);
+    if (g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + x) * 8 + wave) * 2) = p;
   }
   lds_barrier();
 #pragma unroll
-  for (int mi = 0; mi < NB; ++mi) {
-    // the 8 waves' (mean, M2) of the row, merged in wave order (Chan et al.): M2 = sum M2_w + 64 sum (mean_w - mean)^2
-    const f32x4* pr = reinterpret_cast<const f32x4*>(red + (mi * 16 + x) * 16);
-    const f32x4 p0 = pr[0], p1 = pr[1], p2 = pr[2], p3 = pr[3];
-    const float mu = (((p0[0] + p0[2]) + (p1[0] + p1[2])) + ((p2[0] + p2[2]) + (p3[0] + p3[2]))) * 0.125f;
-    float m2 = ((p0[1] + p0[3]) + (p1[1] + p1[3])) + ((p2[1] + p2[3]) + (p3[1] + p3[3]));
-    const float d0 = p0[0] - mu, d1 = p0[2] - mu, d2 = p1[0] - mu, d3 = p1[2] - mu;
-    const float d4 = p2[0] - mu, d5 = p2[2] - mu, d6 = p3[0] - mu, d7 = p3[2] - mu;
-    const float dm = ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3)) + ((d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7));
-    m2 = fmaf(64.0f, dm, m2);
-    mean[mi] = mu;
-    rstd[mi] = rsqrtf(m2 * (1.0f / (float)kCh) + eps);
-  }
+  for (int mi = 0; mi < NB; ++mi) merge_partials<8>(red, mi * 16 + x, eps, mean[mi], rstd[mi]);
 }
 
 // LayerNorm of the panel rows held as v[mi][ni][r] and store of the normalised rows (model dtype) into the LDS panel `dst`.  gm / bt:
@@ -223,7 +278,7 @@ __device__ __forceinline__ void panel_row_stats(const f32x4 (&v)[NB][4], float e
 template <typename T>
 __device__ __forceinline__ void panel_layernorm(f32x4 (&v)[3][4], const u32x2 (&gm)[4], const u32x2 (&bt)[4], float eps, unsigned char* dst,
                                                 float* red, int wave, int lane) {
-  const LaneCtx lc = lane_ctx(lane, wave);
+  const LaneCols<4> lc = lane_cols<4>(lane, wave);
   float mean[3], rstd[3];
   panel_row_stats<T>(v, eps, red, wave, lc.x, lc.g, mean, rstd);
 #pragma unroll
@@ -248,7 +303,7 @@ __device__ __forceinline__ void panel_layernorm(f32x4 (&v)[3][4], const u32x2 (&
 // (panel row 0, the wave's first column); the wave's own LDS operations are ordered: no barrier.
 template <typename T, int NB = 3>
 __device__ __forceinline__ void store_block_via_strip(const u32x2 (&pk)[NB][4], unsigned char* strip, T* out, int64_t ld, int nr, int lane, int wave) {
-  const LaneCtx lc = lane_ctx(lane, wave);
+  const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
   for (int mi = 0; mi < NB; ++mi) {
     const int m = mi * 16 + lc.x;
@@ -265,6 +320,159 @@ __device__ __forceinline__ void store_block_via_strip(const u32x2 (&pk)[NB][4], 
     if (m < nr) *reinterpret_cast<u32x4*>(out + (int64_t)m * ld + sl * 8) = v;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the strip may be rewritten
+}
+
+// ---- epilogues of a wave's 48 x 16 NI block held as acc[mi][0..NI-1] (wave w of kWaves<NI>), on the swizzled panel buffers
+
+// acc[mi][ni] = vec[col0 + column] (+ the panel values at the lane's positions of `rows`): the accumulators of a GEMM start at its bias (+ residual)
+template <typename T, int NI, bool ROWS>
+__device__ __forceinline__ void init_acc(f32x4 (&acc)[3][8], const unsigned char* vec, int col0, const unsigned char* rows, int lane, int w) {
+  const LaneCols<NI> lc = lane_cols<NI>(lane, w);
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) {
+    float b[4];
+    unpack4<T>(*reinterpret_cast<const u32x2*>(vec + (col0 + w * (16 * NI) + ni * 16 + lc.g * 4) * 2), b);
+#pragma unroll
+    for (int mi = 0; mi < 3; ++mi) {
+      if (ROWS) {
+        float r[4];
+        unpack4<T>(*reinterpret_cast<const u32x2*>(rows + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]), r);
+        acc[mi][ni] = f32x4{b[0] + r[0], b[1] + r[1], b[2] + r[2], b[3] + r[3]};
+      } else {
+        acc[mi][ni] = f32x4{b[0], b[1], b[2], b[3]};
+      }
+    }
+  }
+}
+
+// The wave's block rounded to the model dtype into the panel buffer `dst` (its own columns).
+// ADD: first + vec[col0 + column] (Bias), or + vec[col0 + column] + the values `dst` holds at the same positions (BiasRows: a projection's
+// bias and the skip rows; each lane rewrites the positions it read).
+// STATS: acc keeps the ROUNDED values; per-wave (mean, M2) of every row over the wave's columns -> red[row][w].
+// STORE = false: the rounded values stay in acc only (dst unused) - the pipelined row chain keeps a panel in registers across a barrier.
+enum class Add { None, Bias, BiasRows };
+template <typename T, int NI, Add ADD, bool STATS, bool STORE = true>
+__device__ __forceinline__ void round_rows(f32x4 (&acc)[3][8], unsigned char* dst, float* red, int lane, int w, const unsigned char* vec = nullptr, int col0 = 0) {
+  const LaneCols<NI> lc = lane_cols<NI>(lane, w);
+  u32x2 rb[NI], rr[NI];
+  if constexpr (ADD == Add::Bias) {  // (once, outside the row-band loop)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) rb[ni] = *reinterpret_cast<const u32x2*>(vec + (col0 + w * (16 * NI) + ni * 16 + lc.g * 4) * 2);
+  }
+#pragma unroll
+  for (int mi = 0; mi < 3; ++mi) {
+    unsigned char* drow = dst + (mi * 16 + lc.x) * kRowBytes;
+    // (BiasRows: the reads of half a 128-column row band are requested together, pinned - the ring's next fragments are live here: all 48 reads
+    // at once spill, one pair at a time exposes an LDS round trip twelve times)
+    if constexpr (ADD == Add::BiasRows) {
+#pragma unroll
+      for (int h = 0; h < NI / 4; ++h) {
+#pragma unroll
+        for (int ni = 4 * h; ni < 4 * h + 4; ++ni) {
+          rb[ni] = *reinterpret_cast<const u32x2*>(vec + (col0 + w * (16 * NI) + ni * 16 + lc.g * 4) * 2);
+          rr[ni] = *reinterpret_cast<const u32x2*>(drow + lc.coff[ni]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float o[4] = {acc[mi][ni][0], acc[mi][ni][1], acc[mi][ni][2], acc[mi][ni][3]};
+      if constexpr (ADD != Add::None) {
+        float b[4];
+        unpack4<T>(rb[ni], b);
+        if constexpr (ADD == Add::BiasRows) {
+          float r[4];
+          unpack4<T>(rr[ni], r);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o[k] += b[k] + r[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o[k] += b[k];
+        }
+      }
+      const u32x2 pk = pack4<T>(o);
+      if constexpr (STORE) *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pk;
+      if (STATS) {
+        unpack4<T>(pk, o);
+        acc[mi][ni] = f32x4{o[0], o[1], o[2], o[3]};
+      }
+    }
+    if (STATS) {
+      const float2 p = row_partial<NI>(acc[mi]);
+      if (lc.g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + lc.x) * kWaves<NI> + w) * 2) = p;
+    }
+  }
+}
+
+// GELU of the wave's block, rounded to the model dtype into the panel buffer `dst` (its own columns).  Column block by column block,
+// pinned: left alone the scheduler interleaves all 48 polynomial chains and spills 32 registers around them.
+template <typename T, int NI>
+__device__ __forceinline__ void gelu_rows(const f32x4 (&acc)[3][8], unsigned char* dst, int lane, int w) {
+  const LaneCols<NI> lc = lane_cols<NI>(lane, w);
+#pragma unroll
+  for (int mi = 0; mi < 3; ++mi) {
+    unsigned char* drow = dst + (mi * 16 + lc.x) * kRowBytes;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float o[4] = {acc[mi][ni][0], acc[mi][ni][1], acc[mi][ni][2], acc[mi][ni][3]};
+      gelu_fast2(o[0], o[1]);
+      gelu_fast2(o[2], o[3]);
+      *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pack4<T>(o);
+      if (ni & 1) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// LayerNorm without the affine part: the waves' partials of each row merged, the rounded values in acc normalised and stored (model dtype)
+// into the panel buffer `dst`.
+template <typename T, int NI>
+__device__ __forceinline__ void normalise_rows(const f32x4 (&acc)[3][8], const float* red, float eps, unsigned char* dst, int lane, int w) {
+  const LaneCols<NI> lc = lane_cols<NI>(lane, w);
+#pragma unroll
+  for (int mi = 0; mi < 3; ++mi) {
+    float mu, rstd;
+    merge_partials<kWaves<NI>>(red, mi * 16 + lc.x, eps, mu, rstd);
+    const float nm = -mu * rstd;
+    unsigned char* drow = dst + (mi * 16 + lc.x) * kRowBytes;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      float o[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = fmaf(acc[mi][ni][r], rstd, nm);
+      *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pack4<T>(o);
+    }
+  }
+}
+// The same in REGISTERS: acc <- (acc - mean) rstd, unrounded (a round_rows writes - and rounds - it later)
+template <typename T, int NI>
+__device__ __forceinline__ void normalise_regs(f32x4 (&acc)[3][8], const float* red, float eps, int lane, int w) {
+  const LaneCols<NI> lc = lane_cols<NI>(lane, w);
+#pragma unroll
+  for (int mi = 0; mi < 3; ++mi) {
+    float mu, rstd;
+    merge_partials<kWaves<NI>>(red, mi * 16 + lc.x, eps, mu, rstd);
+    const float nm = -mu * rstd;
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[mi][ni][r] = fmaf(acc[mi][ni][r], rstd, nm);
+  }
+}
+
+// The wave's staged block (panel layout, its own columns) to global memory as row pieces of 32 NI bytes: 2 NI lanes per row
+template <typename T, int NI>
+__device__ __forceinline__ void store_staged(const unsigned char* strip, T* out, int64_t ld, int nr, int lane, int w) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave reads back only what it wrote itself: no barrier
+  asm volatile("" : "+v"(lane), "+s"(w));
+  constexpr int kLpr = 2 * NI, kRpi = 64 / kLpr;  // lanes per row, rows per iteration
+  const int rl = lane >> (NI == 8 ? 4 : 3), sl = lane & (kLpr - 1);
+#pragma unroll
+  for (int it = 0; it < kPanel / kRpi; ++it) {
+    const int row = it * kRpi + rl;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(panel_at(strip, row, w * kLpr + sl));
+    if (row < nr) stream_store(v, reinterpret_cast<u32x4*>(out + (int64_t)row * ld + w * (16 * NI) + sl * 8));
+  }
 }
 
 }  // namespace anemoi

@@ -57,7 +57,7 @@ __device__ __forceinline__ void load_rows12_w(const T* src, int64_t ld, int r0, 
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
       const int row = wq * 12 + i;  // (the swizzle permutes the 16 slots of a 128-column group among themselves)
-      *reinterpret_cast<u32x4*>(dst + row * kRowBytes + ((lane ^ (row & 15)) << 4)) = row < nr ? v[i] : u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(panel_at(dst, row, lane)) = row < nr ? v[i] : u32x4{0u, 0u, 0u, 0u};
     }
   }
 }
@@ -87,9 +87,9 @@ __device__ __forceinline__ void edge_group_chain(const EdgeChainArgs& a, unsigne
     // all six row indices first, then the rows of two bands in flight at a time)
     load_rows12_w<T>((const T*)a.e, a.ld_e, r0, nr, buf, lane, wq, nq0 * 8);
     {
-      const Lane2 lc = lane2(lane, wq);
+      const LaneCols<8> lc = lane_cols<8>(lane, wq);
       if constexpr (MLP) {
-        init_acc<T, false>(acc, vec, 0, nullptr, lane, wq);
+        init_acc<T, 8, false>(acc, vec, 0, nullptr, lane, wq);
       } else {
         int i1[3], i2[3];
 #pragma unroll
@@ -137,22 +137,22 @@ __device__ __forceinline__ void edge_group_chain(const EdgeChainArgs& a, unsigne
     // ---- h1 = gelu(e W_e^T + ...) in place
     gemm128<T>(buf, lane, ring, w0w, cs0, w1w, kSlab, loff, acc, nq0);
     group4_barrier(ctr, epoch, lane);  // every wave of the group is behind its last fragment read
-    if (a.dbg & 1) round_rows<T, false>(acc, buf, nullptr, lane, wq);
-    else gelu_rows<T>(acc, buf, lane, wq);
-    init_acc<T, false>(acc, vec, kCh, nullptr, lane, wq);
+    if (a.dbg & 1) round_rows<T, 8, Add::None, false>(acc, buf, nullptr, lane, wq);
+    else gelu_rows<T, 8>(acc, buf, lane, wq);
+    init_acc<T, 8, false>(acc, vec, kCh, nullptr, lane, wq);
     group4_barrier(ctr, epoch, lane);
     // ---- h2 = gelu(h1 W_1^T + b_1) in place
     gemm128<T>(buf, lane, ring, w1w, kSlab, w2w, kSlab, loff, acc);
     group4_barrier(ctr, epoch, lane);
-    if (a.dbg & 1) round_rows<T, false>(acc, buf, nullptr, lane, wq);
-    else gelu_rows<T>(acc, buf, lane, wq);
-    init_acc<T, false>(acc, vec, 2 * kCh, nullptr, lane, wq);
+    if (a.dbg & 1) round_rows<T, 8, Add::None, false>(acc, buf, nullptr, lane, wq);
+    else gelu_rows<T, 8>(acc, buf, lane, wq);
+    init_acc<T, 8, false>(acc, vec, 2 * kCh, nullptr, lane, wq);
     group4_barrier(ctr, epoch, lane);
     // ---- z = h2 W_2^T + b_2 (rounded, as the Linear's output is); e' = LayerNorm(z) + e -> global
     gemm128<T>(buf, lane, ring, w2w, kSlab, w0w, cs0, loff, acc);
     {
       // this lane's values of the residual rows (L2-hot: the group read the same rows for the panel): in flight under the rounding and the statistics
-      const Lane2 lc = lane2(lane, wq);
+      const LaneCols<8> lc = lane_cols<8>(lane, wq);
       u32x2 er[3][8];
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
@@ -208,7 +208,7 @@ __device__ __forceinline__ void edge_group_chain(const EdgeChainArgs& a, unsigne
           *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pack4<T>(o);
         }
       }
-      store_staged<T>(buf, (T*)a.e_new + (int64_t)r0 * a.ld_o, a.ld_o, (a.dbg & 8) ? 0 : nr, lane, wq);
+      store_staged<T, 8>(buf, (T*)a.e_new + (int64_t)r0 * a.ld_o, a.ld_o, (a.dbg & 8) ? 0 : nr, lane, wq);
     }
     group4_barrier(ctr, epoch, lane);  // every wave has read its staged columns back (and the partials): the next panel's rows may come in
   }

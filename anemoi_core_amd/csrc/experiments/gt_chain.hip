@@ -138,7 +138,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     for (int i = 0; i < 6; ++i) {
       const int idx = tid + 512 * i;
       const int row = idx >> 6, slot = idx & 63;
-      *reinterpret_cast<u32x4*>(bufA + row * kRowBytes + ((slot ^ (row & 15)) << 4)) = row < nr ? va[i] : zero4;
+      *reinterpret_cast<u32x4*>(panel_at(bufA, row, slot)) = row < nr ? va[i] : zero4;
     }
     lds_barrier();
     stamp();  // 1: panel in LDS
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     // the ring loads issued behind them here are the next segment's, first waited for behind the epilogue that consumes the rows anyway)
     gemm_seg<T>(bufA, lane, bq, wp0, wp0 + 3 * 16384, loff, acc, NoHook(), 3);
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
         const T* xrow = (const T*)a.xres + (int64_t)(r0 + min(mi * 16 + lc.x, nr - 1)) * a.ld_x + wave * 64 + lc.g * 4;
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     gemm_seg<T>(bufA + 48 * 16, lane, bq, wp0 + 3 * 16384, w10, loff, acc, NoHook(), 1);  // K = 384 .. 511 (slots 48 + s: the swizzle stays in the low 4 bits)
     stamp();  // 2: projection GEMM done
     if (!(a.dbg & 8)) {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
         const int m = mi * 16 + lc.x;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
       if (c > 0) lds_barrier();  // all waves: M2(c-2) read and h_(c-1) written (c = 0: bufA was last read by the projection, two barriers ago)
       stamp();  // barrier passed
       {
-        const LaneCtx lc = lane_ctx(lane, wave);
+        const LaneCols<4> lc = lane_cols<4>(lane, wave);
         unsigned char* const hb = (c & 1) ? bufC : bufA;
 #pragma unroll
         for (int mi = 0; mi < 3; ++mi)
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
       }
     }
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
         const T* orow = (const T*)a.xout + (int64_t)(r0 + min(mi * 16 + lc.x, nr - 1)) * a.ld_out + wave * 64 + lc.g * 4;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     stamp();  // last MLP-2 K-chunk done
     // ---- x2 = h W2^T + b2 + x1 [+ extra] -> global; LayerNorm_attn'(x2) -> bufB
     if (!(a.dbg & 8)) {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
         const int m = mi * 16 + lc.x;
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
         if (!(a.dbg & 4)) {
           // strip row m, 16-byte slot s (8 per row) at m*128 + ((s ^ ((m >> 1) & 7)) << 4): conflict-free for the 8-byte writes in
           // the MFMA layout and for the 16-byte row-major read-back (8 lanes per row, 8 rows per instruction)
-          const LaneCtx lc = lane_ctx(lane, wave);
+          const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
           for (int mi = 0; mi < 3; ++mi) {
             const int m = mi * 16 + lc.x;

@@ -65,8 +65,8 @@ struct Chain2Args {
   unsigned long long* timeline;             // developer aid (TL instantiation only): [workgroups][8 waves][kTl2Slots] s_memtime stamps
 };
 constexpr int kTl2Slots = 48;
-constexpr int kRed2Off = 3 * kBufBytes;                   // [48 rows][8 waves][2] fp32 LayerNorm partials (x1: eight 64-column waves; x2: four 128-column waves, [48][4][2] in the first 1 536 bytes)
-constexpr int kVecOff = kRed2Off + kPanel * 8 * 2 * 4;    // the per-column vectors (16-bit)
+constexpr int kRed2Off = kRedOff;                        // [48 rows][8 waves][2] fp32 LayerNorm partials (x1: eight 64-column waves; x2: four 128-column waves, [48][4][2] in the first 1 536 bytes)
+constexpr int kVecOff = vec_off(8);                       // the per-column vectors (16-bit)
 constexpr int kVecMaxElems = 6144;                        // 12 KiB: 512 + hidden + 512 + q_out <= 6144 (hidden = q_out = 2048: 5120)
 constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;
 constexpr int kVecMaxElemsTl = 5120;                      // the instrumented instantiation gives 2 KiB of the vector region to its stamps
@@ -142,7 +142,7 @@ struct Rows6 {
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const int row = w8 * 6 + i;
-      *reinterpret_cast<u32x4*>(dst + row * kRowBytes + ((lane ^ (row & 15)) << 4)) = row < nr ? v[i] : u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(panel_at(dst, row, lane)) = row < nr ? v[i] : u32x4{0u, 0u, 0u, 0u};
     }
   }
 };
@@ -173,10 +173,10 @@ __device__ __forceinline__ void projection_phase(const Chain2Args& a, Ctx2& c, u
     skip.store(bufC, nr, c.lane, w8);
     lds_barrier();  // the skip rows are in LDS
   }
-  round_rows64_add_stats<T>(acc, bufC, red, c.lane, w8, smem + kVecOff);
+  round_rows<T, 4, Add::BiasRows, true>(acc, bufC, red, c.lane, w8, smem + kVecOff);
   stamp2<TL>(c, smem);
   lds_barrier();  // x1 and the partials are complete; every wave is behind its last read of the attention rows
-  normalise_rows64<T>(acc, red, a.eps1, bufB, c.lane, w8);
+  normalise_rows<T, 4>(acc, red, a.eps1, bufB, c.lane, w8);
   stamp2<TL>(c, smem);
 }
 
@@ -235,7 +235,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
     // the MLP's first Linear, chunk by chunk (+ GELU); step hc is group B's alone
     for (int t = 0; t < hc; ++t) {
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 512 + 512 * t, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 512 + 512 * t, nullptr, lane, wq);
       // (behind the last chunk: the first chunk of the trailing projection, or the next panel's projection slab in gemm64's ring layout)
       const char* nxt = t + 1 < hc ? w1c(t + 1) : (qc > 0 ? wqc(0) : wpw);
       const int64_t ns = (t + 1 < hc || qc > 0) ? s1 : 8192;
@@ -244,8 +244,8 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
       if (kExperiments && a.prio_a == 1) __builtin_amdgcn_s_setprio(0);
       touch(t == 0 ? nullptr : seg_a(t + 1), a.w2 + (int64_t)t * kSlab, sw2);  // the next step's M1(t + 1) (t = 0: touched behind P) and M2(t)
       stamp2<TL>(c, smem);
-      if (dbg & 1) round_rows<T, false>(acc, hbuf(t), nullptr, lane, wq);
-      else gelu_rows<T>(acc, hbuf(t), lane, wq);
+      if (dbg & 1) round_rows<T, 8, Add::None, false>(acc, hbuf(t), nullptr, lane, wq);
+      else gelu_rows<T, 8>(acc, hbuf(t), lane, wq);
       stamp2<TL>(c, smem);
       lds_barrier();
     }
@@ -267,7 +267,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
 #pragma unroll
       for (int i = 0; i < 12; ++i) {
         const int row = w0 * 12 + i;
-        u32x4 v = *reinterpret_cast<const u32x4*>(xb + row * kRowBytes + ((l0 ^ (row & 15)) << 4));
+        u32x4 v = *reinterpret_cast<const u32x4*>(panel_at(xb, row, l0));
         if (row < nr) {
           if (a.extra != nullptr) {
             // the latent skip rides on the last block's output, added to the block's ROUNDED output as `x + skip` does
@@ -294,14 +294,14 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
     // the even chunks of the trailing projection, staged (rounded) in x2's buffer
     for (int k = 0; k < qc; k += 2) {
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
       set_chunk_prio(kExperiments && a.prio_q, k);
       gemm128<T>(bufB, lane, ring, wqc(k), s1, k + 2 < qc ? wqc(k + 2) : wpw, k + 2 < qc ? s1 : 8192, c.loff, acc);
       if (kExperiments && a.prio_q) __builtin_amdgcn_s_setprio(0);
       touch(k + 2 < qc ? a.wq + (int64_t)(8 * (k + 2)) * kSlab : nullptr, k + 3 < qc ? a.wq + (int64_t)(8 * (k + 3)) * kSlab : nullptr, kSlab);
       stamp2<TL>(c, smem);
-      round_rows<T, false>(acc, hbuf(hc), nullptr, lane, wq);
-      if (!(dbg & 4)) store_staged<T>(hbuf(hc), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, hbuf(hc), nullptr, lane, wq);
+      if (!(dbg & 4)) store_staged<T, 8>(hbuf(hc), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
       stamp2<TL>(c, smem);
     }
     if (qc > 0) lds_barrier();  // (the groups' chunks are independent of each other: one barrier behind them all, for the next panel's S0)
@@ -360,7 +360,7 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
     else projection_phase<T, TL, false>(a, c, smem, ring, acc, w2c(0), s2, r0, nr, [] {});
     first = false;
     // S2: x2's accumulators start at b_2 + x1
-    init_acc<T, true>(acc, vec, 512 + 512 * hc, bufC, lane, wq);
+    init_acc<T, 8, true>(acc, vec, 512 + 512 * hc, bufC, lane, wq);
     stamp2<TL>(c, smem);
     lds_barrier();
     stamp2<TL>(c, smem);
@@ -378,27 +378,27 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
       gemm128<T>(hbuf(t - 1), lane, ring, w2c(t - 1), s2, nxt, ns, c.loff, acc);
       stamp2<TL>(c, smem);
       if (t == hc) {  // x2 (rounded) -> the h buffer nobody reads any more, for group A to store
-        if (qc > 0) round_rows<T, true>(acc, hbuf(hc), red, lane, wq);
-        else round_rows<T, false>(acc, hbuf(hc), nullptr, lane, wq);
+        if (qc > 0) round_rows<T, 8, Add::None, true>(acc, hbuf(hc), red, lane, wq);
+        else round_rows<T, 8, Add::None, false>(acc, hbuf(hc), nullptr, lane, wq);
         stamp2<TL>(c, smem);
       }
       lds_barrier();
     }
     // S8: LayerNorm_attn'(x2) without its affine part -> bufB
-    if (qc > 0) normalise_rows<T>(acc, red, a.epsq, bufB, lane, wq);
+    if (qc > 0) normalise_rows<T, 8>(acc, red, a.epsq, bufB, lane, wq);
     stamp2<TL>(c, smem);
     lds_barrier();
     // the odd chunks of the trailing projection, staged in the other h buffer
     for (int k = 1; k < qc; k += 2) {
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
       const bool last = k + 2 >= qc;
       set_chunk_prio(kExperiments && a.prio_q, k);
       gemm128<T>(bufB, lane, ring, wqc(k), s1, last ? wpw : wqc(k + 2), last ? 8192 : s1, c.loff, acc);
       if (kExperiments && a.prio_q) __builtin_amdgcn_s_setprio(0);
       stamp2<TL>(c, smem);
-      round_rows<T, false>(acc, hbuf(hc + 1), nullptr, lane, wq);
-      if (!(dbg & 4)) store_staged<T>(hbuf(hc + 1), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, hbuf(hc + 1), nullptr, lane, wq);
+      if (!(dbg & 4)) store_staged<T, 8>(hbuf(hc + 1), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
       stamp2<TL>(c, smem);
     }
     if (qc > 0) lds_barrier();

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
       const int idx = td + 512 * (pc * kPiece + i);
       const int row = idx >> 6, slot = idx & 63;
       if (!MLP || slot < nslots)  // (the swizzle permutes the 16 slots of a 128-column group among themselves)
-        *reinterpret_cast<u32x4*>(bufE + row * kRowBytes + ((slot ^ (row & 15)) << 4)) = row < nr ? va[i] : zero4;
+        *reinterpret_cast<u32x4*>(panel_at(bufE, row, slot)) = row < nr ? va[i] : zero4;
     }
   };
 #pragma unroll 1
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
     u32x2 ga[MLP ? 1 : NB][4], gb[MLP ? 1 : NB][4], pb[4];
     [[maybe_unused]] int i1[NB], i2[NB];
     if constexpr (!MLP) {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi) {
         const int m = r0 + min(mi * 16 + lc.x, nr - 1);
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
     } else {
       gemm_seg<T, NB>(bufE, lane, bq, w0, w0 + 3 * 16384, loff, acc, NoHook(), 3, flip);  // K = 0 .. 383
       {
-        const LaneCtx lc = lane_ctx(lane, wave);
+        const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
         for (int mi = 0; mi < NB; ++mi) {
           const T* r1 = (const T*)a.g1 + (int64_t)i1[mi] * a.ld_g1 + wave * 64 + lc.g * 4;
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
     }
     stamp();  // + 1: first GEMM done
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi)
 #pragma unroll
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
       }
     lds_barrier();
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi)
 #pragma unroll
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
     gemm_seg<T, NB>(bufH, lane, bq, w2, w0, loff, acc, NoHook(), 4, flip);  // (behind it: the next panel's first segment; after the last panel a harmless re-read)
     stamp();  // + 5: third GEMM done
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
       u32x2 er[NB][4];  // this lane's values of the e rows (the residual): in flight under the bias add and the row statistics
       const T* const resp = MLP ? (const T*)a.res : (const T*)a.e;
       const int64_t ld_res = MLP ? a.ld_res : a.ld_e;
@@ -422,7 +422,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
       }
       float lo[4] = {s8[0], s8[1], s8[2], s8[3]}, hi[4] = {s8[4], s8[5], s8[6], s8[7]};
       const u32x2 pl = pack4<T>(lo), ph = pack4<T>(hi);
-      *reinterpret_cast<u32x4*>(bufC + row * kRowBytes + ((lane ^ (row & 15)) << 4)) = u32x4{pl[0], pl[1], ph[0], ph[1]};
+      *reinterpret_cast<u32x4*>(panel_at(bufC, row, lane)) = u32x4{pl[0], pl[1], ph[0], ph[1]};
     }
   };
   request_panel(tile);
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     for (int i = 0; i < 6; ++i) {
       const int idx = tid + 512 * i;
       const int row = idx >> 6, slot = idx & 63;
-      const int off = row * kRowBytes + ((slot ^ (row & 15)) << 4);
+      const int off = panel_off(row, slot);
       *reinterpret_cast<u32x4*>(bufA + off) = row < nr ? va[i] : zero4;
       if (a.seg_ptr == nullptr) *reinterpret_cast<u32x4*>(bufC + off) = row < nr ? vb[i] : zero4;
     }
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     gemm_seg<T>(bufA, lane, bq, wa0, wa0 + kSlab, loff, acc);
     gemm_seg<T>(bufC, lane, bq, wa0 + kSlab, wb0, loff, acc);
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     zero_acc<T>(acc);
     gemm_seg<T>(bufB, lane, bq, wb0, wc0, loff, acc);
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
@@ -512,7 +512,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     const bool more = next_tile < a.n_tiles;
     unsigned char* const strip = bufC + wave * (kPanel * 128);  // behind the statistics' barrier no wave reads bufC any more
     {
-      const LaneCtx lc = lane_ctx(lane, wave);
+      const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi)
 #pragma unroll

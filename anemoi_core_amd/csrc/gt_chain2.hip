@@ -68,8 +68,7 @@ struct Chain2Args {
   unsigned long long* timeline;             // developer aid (TL instantiation only): [workgroups][8 waves][kTl2Slots] s_memtime stamps
 };
 constexpr int kTl2Slots = 48;
-constexpr int kRed2Off = 3 * kBufBytes;                   // [48 rows][4 waves][2] fp32 LayerNorm partials
-constexpr int kVecOff = kRed2Off + kPanel * 4 * 2 * 4;    // the per-column vectors (16-bit)
+constexpr int kVecOff = vec_off(4);                       // the per-column vectors (16-bit), behind the [48 rows][4 waves][2] partials
 constexpr int kVecMaxElems = 6144;                        // 12 KiB: 512 + hidden + 512 + q_out <= 6144 (hidden = q_out = 2048: 5120)
 constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;
 constexpr int kVecMaxElemsTl = 5120;                      // the instrumented instantiation gives 2 KiB of the vector region to its stamps
@@ -127,7 +126,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
   // trailing projection (attention rows, LN(x1), LN'(x2)); bufC: skip rows, then x1, then the odd hidden chunks
   unsigned char* const bufB = smem + kBufBytes;
   unsigned char* const bufC = smem + 2 * kBufBytes;
-  float* const red = reinterpret_cast<float*>(smem + kRed2Off);
+  float* const red = reinterpret_cast<float*>(smem + kRedOff);
   const unsigned char* const vec = smem + kVecOff;
   auto hbuf = [&](int t) { return smem + (t & 1) * (2 * kBufBytes); };
   const int64_t s1 = kSlab;
@@ -178,26 +177,26 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
     touch(seg_a(0), hc > 1 ? seg_a(1) : nullptr, kSlab);  // M1(0) (4 us away) and M1(1)
     stamp2<TL>(c, smem);
     lds_barrier();  // group B's skip rows and vectors are in LDS
-    round_rows<T, true, true>(acc, bufC, red, lane, wq, vec, 0);
+    round_rows<T, 8, Add::BiasRows, true>(acc, bufC, red, lane, wq, vec, 0);
     stamp2<TL>(c, smem);
     lds_barrier();
     // S2: LayerNorm_mlp(x1) without its affine part -> bufB (every wave has read the attention rows)
-    if (dbg & 2) round_rows<T, false>(acc, bufB, nullptr, lane, wq);
-    else normalise_rows<T>(acc, red, a.eps1, bufB, lane, wq);
+    if (dbg & 2) round_rows<T, 8, Add::None, false>(acc, bufB, nullptr, lane, wq);
+    else normalise_rows<T, 8>(acc, red, a.eps1, bufB, lane, wq);
     stamp2<TL>(c, smem);
     lds_barrier();
     // the MLP's first Linear, chunk by chunk (+ GELU); step hc is group B's alone
     for (int t = 0; t < hc; ++t) {
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 512 + 512 * t, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 512 + 512 * t, nullptr, lane, wq);
       const char* nxt = t + 1 < hc ? w1c(t + 1) : ((qc > 0 && !narrow_idle) ? wqc(0) : wpw);
       if (kExperiments && a.prio_a == 1) __builtin_amdgcn_s_setprio(2);
       gemm128<T>(bufB, lane, ring, w1c(t), s1, nxt, s1, c.loff, acc);
       if (kExperiments && a.prio_a == 1) __builtin_amdgcn_s_setprio(0);
       touch(t == 0 ? nullptr : seg_a(t + 1), a.w2 + (int64_t)t * kSlab, sw2);  // the next step's M1(t + 1) (t = 0: touched behind P) and M2(t)
       stamp2<TL>(c, smem);
-      if (dbg & 1) round_rows<T, false>(acc, hbuf(t), nullptr, lane, wq);
-      else gelu_rows<T>(acc, hbuf(t), lane, wq);
+      if (dbg & 1) round_rows<T, 8, Add::None, false>(acc, hbuf(t), nullptr, lane, wq);
+      else gelu_rows<T, 8>(acc, hbuf(t), lane, wq);
       stamp2<TL>(c, smem);
       lds_barrier();
     }
@@ -219,7 +218,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
 #pragma unroll
       for (int i = 0; i < 12; ++i) {
         const int row = w0 * 12 + i;
-        u32x4 v = *reinterpret_cast<const u32x4*>(xb + row * kRowBytes + ((l0 ^ (row & 15)) << 4));
+        u32x4 v = *reinterpret_cast<const u32x4*>(panel_at(xb, row, l0));
         if (row < nr && a.xout != nullptr) {
           if (a.extra != nullptr) {
             // the latent skip rides on the last block's output, added to the block's ROUNDED output as `x + skip` does
@@ -237,7 +236,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
             const u32x2 hi = pack4<T>(p);
             v = u32x4{lo[0], lo[1], hi[0], hi[1]};
             // (a trailing projection behind the latent skip - the decoder's k | v - reads LayerNorm(x2 + skip): the sum goes back into the panel)
-            if (qc > 0) *reinterpret_cast<u32x4*>(hbuf(hc) + row * kRowBytes + ((l0 ^ (row & 15)) << 4)) = v;
+            if (qc > 0) *reinterpret_cast<u32x4*>(panel_at(hbuf(hc), row, l0)) = v;
           }
           stream_store(v, reinterpret_cast<u32x4*>((T*)a.xout + (int64_t)(r0 + row) * a.ld_out + l0 * 8));
         }
@@ -253,14 +252,14 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
     for (int k = 0; k < qc; k += 2) {
       if (narrow_idle) break;  // (a narrow projection: this wave's columns do not exist)
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
       set_chunk_prio(kExperiments && a.prio_q, k);
       gemm128<T>(bufB, lane, ring, wqc(k), s1, k + 2 < qc ? wqc(k + 2) : wpw, s1, c.loff, acc);
       if (kExperiments && a.prio_q) __builtin_amdgcn_s_setprio(0);
       touch(k + 2 < qc ? a.wq + (int64_t)(8 * (k + 2)) * kSlab : nullptr, k + 3 < qc ? a.wq + (int64_t)(8 * (k + 3)) * kSlab : nullptr, kSlab);
       stamp2<TL>(c, smem);
-      round_rows<T, false>(acc, hbuf(hc), nullptr, lane, wq);
-      if (!(dbg & 4)) store_staged<T>(hbuf(hc), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, hbuf(hc), nullptr, lane, wq);
+      if (!(dbg & 4)) store_staged<T, 8>(hbuf(hc), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
       stamp2<TL>(c, smem);
     }
     if (qc > 0) lds_barrier();  // (the groups' chunks are independent of each other: one barrier behind them all, for the next panel's S0)
@@ -284,7 +283,7 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
   // trailing projection (attention rows, LN(x1), LN'(x2)); bufC: skip rows, then x1, then the odd hidden chunks
   unsigned char* const bufB = smem + kBufBytes;
   unsigned char* const bufC = smem + 2 * kBufBytes;
-  float* const red = reinterpret_cast<float*>(smem + kRed2Off);
+  float* const red = reinterpret_cast<float*>(smem + kRedOff);
   const unsigned char* const vec = smem + kVecOff;
   auto hbuf = [&](int t) { return smem + (t & 1) * (2 * kBufBytes); };
   const int64_t s1 = kSlab, s2 = (int64_t)hc * kSlab;
@@ -316,7 +315,7 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
     lds_barrier();  // x1 is group A's
     stamp2<TL>(c, smem);
     // S2: x2's accumulators start at b_2 + x1
-    init_acc<T, true>(acc, vec, 512 + 512 * hc, bufC, lane, wq);
+    init_acc<T, 8, true>(acc, vec, 512 + 512 * hc, bufC, lane, wq);
     stamp2<TL>(c, smem);
     lds_barrier();
     stamp2<TL>(c, smem);
@@ -333,8 +332,8 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
       gemm128<T>(hbuf(t - 1), lane, ring, w2c(t - 1), s2, nxt, ns, c.loff, acc);
       stamp2<TL>(c, smem);
       if (t == hc) {  // x2 (rounded) -> the h buffer nobody reads any more, for group A to store
-        if (qc > 0 && a.extra == nullptr) round_rows<T, true>(acc, hbuf(hc), red, lane, wq);
-        else round_rows<T, false>(acc, hbuf(hc), nullptr, lane, wq);
+        if (qc > 0 && a.extra == nullptr) round_rows<T, 8, Add::None, true>(acc, hbuf(hc), red, lane, wq);
+        else round_rows<T, 8, Add::None, false>(acc, hbuf(hc), nullptr, lane, wq);
         stamp2<TL>(c, smem);
       }
       lds_barrier();
@@ -344,7 +343,7 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
       // this group reads them in its accumulator layout and takes the statistics of x2 + skip
       lds_barrier();
       {
-        const Lane2 lc = lane2(lane, wq);
+        const LaneCols<8> lc = lane_cols<8>(lane, wq);
 #pragma unroll
         for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
@@ -354,24 +353,24 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
             acc[mi][ni] = f32x4{o[0], o[1], o[2], o[3]};
           }
       }
-      round_rows<T, true>(acc, hbuf(hc), red, lane, wq);  // (the values are rounded already: this rewrites them unchanged and leaves the per-wave statistics)
+      round_rows<T, 8, Add::None, true>(acc, hbuf(hc), red, lane, wq);  // (the values are rounded already: this rewrites them unchanged and leaves the per-wave statistics)
       lds_barrier();
     }
     // S8: LayerNorm_attn'(x2) without its affine part -> bufB
-    if (qc > 0) normalise_rows<T>(acc, red, a.epsq, bufB, lane, wq);
+    if (qc > 0) normalise_rows<T, 8>(acc, red, a.epsq, bufB, lane, wq);
     stamp2<TL>(c, smem);
     lds_barrier();
     // the odd chunks of the trailing projection, staged in the other h buffer
     for (int k = 1; k < qc; k += 2) {
       stamp2<TL>(c, smem);
-      init_acc<T, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 1024 + 512 * hc + 512 * k, nullptr, lane, wq);
       const bool last = k + 2 >= qc;
       set_chunk_prio(kExperiments && a.prio_q, k);
       gemm128<T>(bufB, lane, ring, wqc(k), s1, last ? w2c(0) : wqc(k + 2), last ? s2 : s1, c.loff, acc);
       if (kExperiments && a.prio_q) __builtin_amdgcn_s_setprio(0);
       stamp2<TL>(c, smem);
-      round_rows<T, false>(acc, hbuf(hc + 1), nullptr, lane, wq);
-      if (!(dbg & 4)) store_staged<T>(hbuf(hc + 1), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, hbuf(hc + 1), nullptr, lane, wq);
+      if (!(dbg & 4)) store_staged<T, 8>(hbuf(hc + 1), (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
       stamp2<TL>(c, smem);
     }
     if (qc > 0) lds_barrier();

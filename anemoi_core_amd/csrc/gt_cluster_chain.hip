@@ -46,57 +46,12 @@ struct ClusterArgs {
   unsigned* counters;                // [clusters], zero at allocation, then monotonic (4 per panel)
   int n_rows, rows_per_tile, n_tiles;
 };
-constexpr int kClRedOff = 3 * kBufBytes;
-constexpr int kClVecOff = kClRedOff + kPanel * 8 * 2 * 4;
+constexpr int kClVecOff = vec_off(8);  // the per-column vectors, behind the [48 rows][8 waves][2] partials
 constexpr int kClVecMax = 5120;  // 512 + 2048 + 512 + 2048
 constexpr int kClusterSmem = kClVecOff + kClVecMax * 2;
 static_assert(kClusterSmem <= 160 * 1024, "LDS budget");
 constexpr size_t kClSlotFloats = (size_t)8 * 3 * 4 * 64 * 4;  // one member's partial [48 x 512] in accumulator layout
 
-// acc[mi][0..3] = vec[col0 + 64 w8 + column]
-template <typename T>
-__device__ __forceinline__ void init_acc64(f32x4 (&acc)[3][8], const unsigned char* vec, int col0, int lane, int w8) {
-  const LaneCtx lc = lane_ctx(lane, w8);
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    float b[4];
-    unpack4<T>(*reinterpret_cast<const u32x2*>(vec + (col0 + w8 * 64 + ni * 16 + lc.g * 4) * 2), b);
-#pragma unroll
-    for (int mi = 0; mi < 3; ++mi) acc[mi][ni] = f32x4{b[0], b[1], b[2], b[3]};
-  }
-}
-// GELU (GELU = false: nothing) of the wave's 48 x 64 block, rounded to the model dtype into the panel buffer `dst` (its own columns)
-template <typename T, bool GELU>
-__device__ __forceinline__ void round_rows64(const f32x4 (&acc)[3][8], unsigned char* dst, int lane, int w8) {
-  const LaneCtx lc = lane_ctx(lane, w8);
-#pragma unroll
-  for (int mi = 0; mi < 3; ++mi) {
-    unsigned char* drow = dst + (mi * 16 + lc.x) * kRowBytes;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float o[4] = {acc[mi][ni][0], acc[mi][ni][1], acc[mi][ni][2], acc[mi][ni][3]};
-      if (GELU) {
-        gelu_fast2(o[0], o[1]);
-        gelu_fast2(o[2], o[3]);
-      }
-      *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pack4<T>(o);
-      if (ni & 1) __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-// the wave's staged 48 x 64 block (panel layout, its own columns) to global memory as 128-byte row pieces: 8 lanes per row
-template <typename T>
-__device__ __forceinline__ void store_staged64(const unsigned char* strip, T* out, int64_t ld, int nr, int lane, int w8) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave reads back only what it wrote itself: no barrier
-  asm volatile("" : "+v"(lane), "+s"(w8));
-  const int rl = lane >> 3, sl = lane & 7;
-#pragma unroll
-  for (int it = 0; it < 6; ++it) {
-    const int row = it * 8 + rl;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(strip + row * kRowBytes + (((w8 * 8 + sl) ^ (row & 15)) << 4));
-    if (row < nr) stream_store(v, reinterpret_cast<u32x4*>(out + (int64_t)row * ld + w8 * 64 + sl * 8));
-  }
-}
 __device__ __forceinline__ void store_sc1(float* p, f32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 __device__ __forceinline__ f32x4 load_sc1(const float* p) {
   f32x4 v;
@@ -110,7 +65,7 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
   unsigned char* const bufH = smem;                  // the member's hidden chunk; then the staging of its projection chunk
   unsigned char* const bufB = smem + kBufBytes;      // attention rows, then LN(x1), then LN'(x2)
   unsigned char* const bufC = smem + 2 * kBufBytes;  // skip rows, then x1, then x2
-  float* const red = reinterpret_cast<float*>(smem + kClRedOff);
+  float* const red = reinterpret_cast<float*>(smem + kRedOff);
   const unsigned char* const vec = smem + kClVecOff;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -148,7 +103,7 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
       const int row = w0 * 6 + i;
-      const int off = row * kRowBytes + ((l0 ^ (row & 15)) << 4);
+      const int off = panel_off(row, l0);
       *reinterpret_cast<u32x4*>(bufB + off) = row < nr ? va[i] : u32x4{0u, 0u, 0u, 0u};
       *reinterpret_cast<u32x4*>(bufC + off) = row < nr ? vx[i] : u32x4{0u, 0u, 0u, 0u};
     }
@@ -176,14 +131,14 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
     gemm64<T>(bufB, lane, ring, wps, w1s, 8192, loff, acc);
-    round_rows64_add_stats<T>(acc, bufC, red, lane, w8, vec);
+    round_rows<T, 4, Add::BiasRows, true>(acc, bufC, red, lane, w8, vec);
     lds_barrier();
-    normalise_rows64<T>(acc, red, a.eps1, bufB, lane, w8);
+    normalise_rows<T, 4>(acc, red, a.eps1, bufB, lane, w8);
     lds_barrier();
     // M1: this member's hidden chunk h_m = GELU(LN(x1) W1[chunk m]^T + d1[chunk m]) -> bufH
-    init_acc64<T>(acc, vec, 512 + 512 * m, lane, w8);
+    init_acc<T, 4, false>(acc, vec, 512 + 512 * m, nullptr, lane, w8);
     gemm64<T>(bufB, lane, ring, w1s, w2s, 8192, loff, acc);
-    round_rows64<T, true>(acc, bufH, lane, w8);
+    gelu_rows<T, 4>(acc, bufH, lane, w8);
     lds_barrier();
     // M2: the member's partial of x2: h_m W2[:, chunk m]^T
 #pragma unroll
@@ -214,8 +169,10 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
       asm volatile("" ::: "memory");
     }
     // x2 = (p0 + p1) + (p2 + p3) + b_2 + x1 (rounded) -> bufC, row statistics; the members' copies are bit-identical
+    // (round_rows<.., Add::BiasRows, STATS> with the four partials summed in front, row band by row band so that 16 loaded quads are live
+    // at a time: with all three bands summed first and a round_rows call behind them the loads of the bands overlap - 256 VGPRs, 76 bytes of scratch)
     {
-      const LaneCtx lc = lane_ctx(lane, w8);
+      const LaneCols<4> lc = lane_cols<4>(lane, w8);
       const float* base = a.scratch + ((size_t)cluster * 2 + (round & 1)) * kClusterSize * kClSlotFloats + (size_t)w8 * (3 * 4 * 64 * 4) + lane * 4;
 #pragma unroll
       for (int mi = 0; mi < 3; ++mi) {
@@ -242,27 +199,12 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
           unpack4<T>(pk, o);
           acc[mi][ni] = f32x4{o[0], o[1], o[2], o[3]};
         }
-        float s = 0.f;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) s += (acc[mi][ni][0] + acc[mi][ni][1]) + (acc[mi][ni][2] + acc[mi][ni][3]);
-        s += __shfl_xor(s, 16, 64);
-        s += __shfl_xor(s, 32, 64);
-        const float mw = s * (1.0f / 64.0f);
-        float q = 0.f;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float d = acc[mi][ni][r] - mw;
-            q = fmaf(d, d, q);
-          }
-        q += __shfl_xor(q, 16, 64);
-        q += __shfl_xor(q, 32, 64);
-        if (lc.g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + lc.x) * 8 + w8) * 2) = make_float2(mw, q);
+        const float2 pw = row_partial<4>(acc[mi]);
+        if (lc.g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + lc.x) * 8 + w8) * 2) = pw;
       }
     }
     lds_barrier();  // x2 and the partials of its statistics are complete
-    if (qc > 0 || a.lnout != nullptr) normalise_rows64<T>(acc, red, a.epsq, bufB, lane, w8);
+    if (qc > 0 || a.lnout != nullptr) normalise_rows<T, 4>(acc, red, a.epsq, bufB, lane, w8);
     // x2 [+ latent skip] -> global: member m stores rows 12 m .. 12 m + 11 as whole 1-KiB rows (768 pieces of 16 bytes)
     {
       int t0 = tid;
@@ -272,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
         const int i = t0 + 512 * k;
         const int row = m * 12 + (i >> 6), sl = i & 63;
         if (i < 768 && row < nr) {
-          u32x4 v = *reinterpret_cast<const u32x4*>(bufC + row * kRowBytes + ((sl ^ (row & 15)) << 4));
+          u32x4 v = *reinterpret_cast<const u32x4*>(panel_at(bufC, row, sl));
           if (a.extra != nullptr) {
             // the latent skip rides on the last block's output, added to the block's ROUNDED output as `x + skip` does
             const u32x4 e = *reinterpret_cast<const u32x4*>((const T*)a.extra + (int64_t)(r0 + row) * a.ld_extra + sl * 8);
@@ -302,7 +244,7 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
         const int i = t0 + 512 * k;
         const int row = m * 12 + (i >> 6), sl = i & 63;
         if (i < 768 && row < nr) {
-          const u32x4 v = *reinterpret_cast<const u32x4*>(bufB + row * kRowBytes + ((sl ^ (row & 15)) << 4));
+          const u32x4 v = *reinterpret_cast<const u32x4*>(panel_at(bufB, row, sl));
           *reinterpret_cast<u32x4*>((T*)a.lnout + (int64_t)(r0 + row) * a.ld_ln + sl * 8) = v;
         }
       }
@@ -311,11 +253,11 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
     const bool more = tile_next < a.n_tiles;
     // Q: chunk m of the trailing projection
     if (myq) {
-      init_acc64<T>(acc, vec, 3072 + 512 * m, lane, w8);
+      init_acc<T, 4, false>(acc, vec, 3072 + 512 * m, nullptr, lane, w8);
       gemm64<T>(bufB, lane, ring, wqs, wps, 8192, loff, acc);
-      round_rows64<T, false>(acc, bufH, lane, w8);
-      if (a.qout2 != nullptr && m >= a.q_split) store_staged64<T>(bufH, (T*)a.qout2 + (int64_t)r0 * a.ld_q2 + (m - a.q_split) * kCh, a.ld_q2, nr, lane, w8);
-      else store_staged64<T>(bufH, (T*)a.qout + (int64_t)r0 * a.ld_q + m * kCh, a.ld_q, nr, lane, w8);
+      round_rows<T, 4, Add::None, false>(acc, bufH, nullptr, lane, w8);
+      if (a.qout2 != nullptr && m >= a.q_split) store_staged<T, 4>(bufH, (T*)a.qout2 + (int64_t)r0 * a.ld_q2 + (m - a.q_split) * kCh, a.ld_q2, nr, lane, w8);
+      else store_staged<T, 4>(bufH, (T*)a.qout + (int64_t)r0 * a.ld_q + m * kCh, a.ld_q, nr, lane, w8);
     }
     if (!more) break;
     lds_barrier();  // every wave is behind its last read of bufB / bufH

@@ -31,54 +31,10 @@ struct RowChainArgs {
   void* qout;      int64_t ld_q;             // [n_rows, 512 qc]
   int n_rows, rows_per_tile, n_tiles;
 };
-constexpr int kRcRedOff = 3 * kBufBytes;                   // [48 rows][8 waves][2] fp32 LayerNorm partials
-constexpr int kRcVecOff = kRcRedOff + kPanel * 8 * 2 * 4;  // the per-column vectors (16-bit): 512 + 512 qc <= 2560
+constexpr int kRcVecOff = vec_off(8);  // the per-column vectors (16-bit), behind the [48 rows][8 waves][2] partials: 512 + 512 qc <= 2560
 constexpr int kRcVecMax = 2560;
 constexpr int kRowChainSmem = kRcVecOff + kRcVecMax * 2;
 static_assert(kRowChainSmem <= 160 * 1024, "LDS budget");
-
-// The wave's 48 x 64 block (acc[mi][0..3]) + vec[column], rounded to the model dtype into the panel buffer `dst`; acc keeps the ROUNDED
-// values; per-wave (mean, M2) of every row over the wave's 64 columns -> red[row][w8]   (round_rows64_add_stats without the skip rows)
-template <typename T>
-__device__ __forceinline__ void round_rows64_bias_stats(f32x4 (&acc)[3][8], unsigned char* dst, float* red, int lane, int w8, const unsigned char* vec) {
-  const LaneCtx lc = lane_ctx(lane, w8);
-  u32x2 rb[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) rb[ni] = *reinterpret_cast<const u32x2*>(vec + (w8 * 64 + ni * 16 + lc.g * 4) * 2);
-#pragma unroll
-  for (int mi = 0; mi < 3; ++mi) {
-    unsigned char* drow = dst + (mi * 16 + lc.x) * kRowBytes;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      float o[4] = {acc[mi][ni][0], acc[mi][ni][1], acc[mi][ni][2], acc[mi][ni][3]};
-      float b[4];
-      unpack4<T>(rb[ni], b);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] += b[k];
-      const u32x2 pk = pack4<T>(o);
-      *reinterpret_cast<u32x2*>(drow + lc.coff[ni]) = pk;
-      unpack4<T>(pk, o);
-      acc[mi][ni] = f32x4{o[0], o[1], o[2], o[3]};
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) s += (acc[mi][ni][0] + acc[mi][ni][1]) + (acc[mi][ni][2] + acc[mi][ni][3]);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mw = s * (1.0f / 64.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = acc[mi][ni][r] - mw;
-        q = fmaf(d, d, q);
-      }
-    q += __shfl_xor(q, 16, 64);
-    q += __shfl_xor(q, 32, 64);
-    if (lc.g == 0) *reinterpret_cast<float2*>(red + ((mi * 16 + lc.x) * 8 + w8) * 2) = make_float2(mw, q);
-  }
-}
 
 // A panel of input rows: 48 rows x spr = 16 ng sixteen-byte slots (slots beyond the row's k_in / 8 are zero), shared out among the 512
 // threads (<= 6 slots each), requested into registers and stored to the swizzled panel later - the request of the NEXT panel rides under
@@ -106,7 +62,7 @@ struct XRows {
       const int i = tid + 512 * k;
       if (i < n) {
         const int row = i / spr, slot = i % spr;
-        *reinterpret_cast<u32x4*>(buf + row * kRowBytes + ((slot ^ (row & 15)) << 4)) = v[k];
+        *reinterpret_cast<u32x4*>(panel_at(buf, row, slot)) = v[k];
       }
     }
   }
@@ -118,7 +74,7 @@ __global__ __launch_bounds__(512, 1) void gt_rowchain_kernel(RowChainArgs a) {
   unsigned char* const bufA = smem;
   unsigned char* const bufB = smem + kBufBytes;
   unsigned char* const bufC = smem + 2 * kBufBytes;
-  float* const red = reinterpret_cast<float*>(smem + kRcRedOff);
+  float* const red = reinterpret_cast<float*>(smem + kRedOff);
   const unsigned char* const vec = smem + kRcVecOff;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6), wq = w8 & 3, grp = w8 >> 2;  // waves wq and wq + 4 share a SIMD
@@ -153,11 +109,11 @@ __global__ __launch_bounds__(512, 1) void gt_rowchain_kernel(RowChainArgs a) {
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
     gemm64<T>(bufA, lane, ring, wes, mine_any ? wqc(grp) : wes, mine_any ? (int64_t)kSlab : (int64_t)8192, loff, acc, ng);
-    round_rows64_bias_stats<T>(acc, bufC, red, lane, w8, vec);
+    round_rows<T, 4, Add::Bias, true>(acc, bufC, red, lane, w8, vec);
     lds_barrier();  // y and the partials are complete; every wave is behind its last read of the x rows
     // L: LayerNorm (no affine) -> bufB; y -> global by group B (each wave its own 128 columns: the columns it will stage its chunk in)
-    normalise_rows64<T>(acc, red, a.eps, bufB, lane, w8);
-    if (a.xout != nullptr && grp == 1) store_staged<T>(bufC, (T*)a.xout + (int64_t)r0 * a.ld_out, a.ld_out, nr, lane, wq);
+    normalise_rows<T, 4>(acc, red, a.eps, bufB, lane, w8);
+    if (a.xout != nullptr && grp == 1) store_staged<T, 8>(bufC, (T*)a.xout + (int64_t)r0 * a.ld_out, a.ld_out, nr, lane, wq);
     const int tile_next = tile + (int)gridDim.x;
     const bool more = tile_next < a.n_tiles;
     if (more) {
@@ -168,11 +124,11 @@ __global__ __launch_bounds__(512, 1) void gt_rowchain_kernel(RowChainArgs a) {
     // Q: this group's chunks of the projection
     unsigned char* const stage = grp == 0 ? bufA : bufC;
     for (int k = grp; k < qc; k += 2) {
-      init_acc<T, false>(acc, vec, 512 + 512 * k, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 512 + 512 * k, nullptr, lane, wq);
       const bool last = k + 2 >= qc;
       gemm128<T>(bufB, lane, ring, wqc(k), kSlab, last ? wes : wqc(k + 2), last ? (int64_t)8192 : (int64_t)kSlab, loff, acc);
-      round_rows<T, false>(acc, stage, nullptr, lane, wq);
-      store_staged<T>(stage, (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, stage, nullptr, lane, wq);
+      store_staged<T, 8>(stage, (T*)a.qout + (int64_t)r0 * a.ld_q + k * kCh, a.ld_q, nr, lane, wq);
     }
     lds_barrier();  // every wave is behind its last read of bufB and of its staging columns
     if (!more) break;
@@ -193,8 +149,7 @@ __global__ __launch_bounds__(512, 1) void gt_rowchain_kernel(RowChainArgs a) {
 //
 // one s_barrier behind each phase (both groups: the hardware barrier counts all eight waves), n + 1 steps for n panels.  LDS: bufX, bufN, group B's
 // staging buffer (48 KB each) + the partials + the vectors.  in_features <= 256 (the parked rows of x(s+1) are 6 registers per lane).
-constexpr int kRc2Red = 3 * kBufBytes;                  // [48 rows][4 waves][2] fp32
-constexpr int kRc2Vec = kRc2Red + kPanel * 4 * 2 * 4;
+constexpr int kRc2Vec = vec_off(4);  // (four waves' partials)
 constexpr int kRowChain2Smem = kRc2Vec + kRcVecMax * 2;
 static_assert(kRowChain2Smem <= 160 * 1024, "LDS budget");
 
@@ -221,7 +176,7 @@ struct XRowsA {  // a panel of input rows shared out among group A's 256 threads
       const int i = t + 256 * k;
       if (i < n) {
         const int row = i / spr, slot = i % spr;
-        *reinterpret_cast<u32x4*>(buf + row * kRowBytes + ((slot ^ (row & 15)) << 4)) = v[k];
+        *reinterpret_cast<u32x4*>(panel_at(buf, row, slot)) = v[k];
       }
     }
   }
@@ -242,7 +197,7 @@ template <typename T>
 __device__ __forceinline__ void pipe_role_a(const RowChainArgs& a, const PipeCtx& c, unsigned char* smem) {
   unsigned char* const bufX = smem;
   unsigned char* const bufN = smem + kBufBytes;
-  float* const red = reinterpret_cast<float*>(smem + kRc2Red);
+  float* const red = reinterpret_cast<float*>(smem + kRedOff);
   const unsigned char* const vec = smem + kRc2Vec;
   const int lane = c.lane, wq = __builtin_amdgcn_readfirstlane(c.wq), ng = a.ng, n = c.n;
   const int64_t se = (int64_t)ng * 16384;  // one 64-column slab of the embedding image
@@ -261,7 +216,7 @@ __device__ __forceinline__ void pipe_role_a(const RowChainArgs& a, const PipeCtx
   for (int s = 0; s <= n; ++s) {
     // phase 1: LN(y)(s-1), parked in the accumulators -> bufN (rounded here); the rows of x(s) -> bufX
     if (s >= 1) {
-      round_rows<T, false>(acc, bufN, nullptr, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, bufN, nullptr, lane, wq);
       if (s < n) xr.store(bufX, ng, c.tid);
     }
     lds_barrier();
@@ -272,9 +227,9 @@ __device__ __forceinline__ void pipe_role_a(const RowChainArgs& a, const PipeCtx
         pipe_rows(a, c, s + 1, rn, nrn);
         xr.request(a.x, a.ld_x, a.k_in, ng, rn, nrn, c.tid, (int)sizeof(T));
       }
-      init_acc<T, false>(acc, vec, 0, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 0, nullptr, lane, wq);
       gemm128<T>(bufX, lane, ring, wes, se, wes, se, c.loff, acc, 2 * ng);
-      round_rows<T, true, false, false>(acc, nullptr, red, lane, wq);
+      round_rows<T, 8, Add::None, true, false>(acc, nullptr, red, lane, wq);
     }
     lds_barrier();
     // phase 3: y -> global (staged through bufX: every wave of the group is behind its last read of the x rows); LN(y) in registers
@@ -282,10 +237,10 @@ __device__ __forceinline__ void pipe_role_a(const RowChainArgs& a, const PipeCtx
       if (a.xout != nullptr) {
         int r0, nr;
         pipe_rows(a, c, s, r0, nr);
-        round_rows<T, false>(acc, bufX, nullptr, lane, wq);
-        store_staged<T>(bufX, (T*)a.xout + (int64_t)r0 * a.ld_out, a.ld_out, nr, lane, wq);
+        round_rows<T, 8, Add::None, false>(acc, bufX, nullptr, lane, wq);
+        store_staged<T, 8>(bufX, (T*)a.xout + (int64_t)r0 * a.ld_out, a.ld_out, nr, lane, wq);
       }
-      normalise_regs<T>(acc, red, a.eps, lane, wq);
+      normalise_regs<T, 8>(acc, red, a.eps, lane, wq);
     }
     lds_barrier();
   }
@@ -308,19 +263,19 @@ __device__ __forceinline__ void pipe_role_b(const RowChainArgs& a, const PipeCtx
     lds_barrier();  // phase 1 is group A's
     // phase 2: chunk 0 of the projection of panel s - 1
     if (s >= 1) {
-      init_acc<T, false>(acc, vec, 512, nullptr, lane, wq);
+      init_acc<T, 8, false>(acc, vec, 512, nullptr, lane, wq);
       gemm128<T>(bufN, lane, ring, wqc(0), kSlab, qc > 1 ? wqc(1) : wqc(0), kSlab, c.loff, acc);
-      round_rows<T, false>(acc, bufS, nullptr, lane, wq);
-      store_staged<T>(bufS, (T*)a.qout + (int64_t)rp * a.ld_q, a.ld_q, nrp, lane, wq);
+      round_rows<T, 8, Add::None, false>(acc, bufS, nullptr, lane, wq);
+      store_staged<T, 8>(bufS, (T*)a.qout + (int64_t)rp * a.ld_q, a.ld_q, nrp, lane, wq);
     }
     lds_barrier();
     // phase 3: its other chunks
     if (s >= 1) {
       for (int k = 1; k < qc; ++k) {
-        init_acc<T, false>(acc, vec, 512 + 512 * k, nullptr, lane, wq);
+        init_acc<T, 8, false>(acc, vec, 512 + 512 * k, nullptr, lane, wq);
         gemm128<T>(bufN, lane, ring, wqc(k), kSlab, k + 1 < qc ? wqc(k + 1) : wqc(0), kSlab, c.loff, acc);
-        round_rows<T, false>(acc, bufS, nullptr, lane, wq);
-        store_staged<T>(bufS, (T*)a.qout + (int64_t)rp * a.ld_q + k * kCh, a.ld_q, nrp, lane, wq);
+        round_rows<T, 8, Add::None, false>(acc, bufS, nullptr, lane, wq);
+        store_staged<T, 8>(bufS, (T*)a.qout + (int64_t)rp * a.ld_q + k * kCh, a.ld_q, nrp, lane, wq);
       }
     }
     lds_barrier();

@@ -7,9 +7,9 @@ cur=None
 for l in sys.stdin:
     m=re.search(r"Function Name: (\S+)",l)
     if m: cur={"name":m.group(1)}; continue
-    m=re.search(r"remark: [^ ]+\s+(VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)",l)
+    m=re.search(r"remark:\s+(TotalSGPRs|VGPRs|AGPRs|SGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)",l)
     if m and cur is not None:
         cur[m.group(1)]=m.group(2)
         if m.group(1).startswith("LDS"):
-            print("%-70s vgpr %s agpr %s sgpr %s scratch %s spill %s occ %s"%(cur["name"][:70],cur.get("VGPRs"),cur.get("AGPRs"),cur.get("SGPRs"),cur.get("ScratchSize [bytes/lane]"),cur.get("VGPRs Spill"),cur.get("Occupancy [waves/SIMD]")))
+            print("%-70s vgpr %s agpr %s sgpr %s scratch %s spill %s sgpr-spill %s occ %s"%(cur["name"][:70],cur.get("VGPRs"),cur.get("AGPRs"),cur.get("TotalSGPRs"),cur.get("ScratchSize [bytes/lane]"),cur.get("VGPRs Spill"),cur.get("SGPRs Spill"),cur.get("Occupancy [waves/SIMD]")))
 '
