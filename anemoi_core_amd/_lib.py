@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -17,6 +17,14 @@ ACT_NONE, ACT_GELU = 0, 1
 E_INVALID, E_UNSUPPORTED, E_LAUNCH = -1, -2, -3
 
 _p, _i64, _i32, _f = C.c_void_p, C.c_int64, C.c_int32, C.c_float
+
+
+
+class LinearPlan(C.Structure):
+    """anemoi_linear_plan_t: the plan of one GEMM (csrc/linear_plan.h), field for field."""
+    _fields_ = [(name, _i32) for name in ("kernel", "tile_m", "tile_n", "pingpong", "stage_k", "mi", "wr", "kg", "stages", "epi", "main_rows",
+                                          "tail_rows", "ln_tail_begin")]
+
 
 # name -> argtypes, exactly as in include/anemoi_hip.h
 SIGNATURES = {
@@ -57,6 +65,7 @@ SIGNATURES = {
     "anemoi_linear_splitk_f32": ([_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_linear_stats_fwd": ([_p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_linear_lnfold_fwd": ([_p, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _f, C.c_int, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
+    "anemoi_linear_plan": ([_i32, _i32, _i32, _i32, _i32, _i32, C.c_int, C.POINTER(LinearPlan)], C.c_int),
     "anemoi_linear_fwd": ([_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i32, _i32, C.c_int, C.c_int, _p], C.c_int),
     "anemoi_linear_fwd_pre": ([_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _i32, _i32,
                                C.c_int, C.c_int, _p], C.c_int),

@@ -15,9 +15,16 @@
 //    the fp32 parity path): 64x64 tile, fp32 FMA on the vector ALU.
 //
 // A = [x | x2] is a K-concatenation (GraphConv's cat[x, agg] / cat[x_i, x_j, e] never materialised).
+//
+// Which kernel a call gets - kernel, tile, wave schedule, and the trailing rows peeled onto the VALU - is decided in ONE host
+// function, plan_gemm() of linear_plan.h, from the shape, the epilogue and the environment switches; the entry points at the end
+// of this file build the problem, plan it and launch what the plan names.  To ask without launching: anemoi_linear_plan
+// (include/anemoi_hip.h), from Python ops.linear_plan(...); it needs no GPU.
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
+#include "linear_plan.h"
 
 namespace anemoi {
 
@@ -49,7 +56,7 @@ struct LinArgs {
   // normalisation of its INPUT rows in the epilogue:  LN(x) W^T = rstd (x (W gamma)^T - mean c) + d
   float* stats_out = nullptr;       // [n_rows][O / 64][2] fp32: sum and sum of squares of every 64-column strip (EPI_STATS)
   const float* stats_in = nullptr;  // [n_rows][ln_strips][2] of the input rows (EPI_LNFOLD)
-  int ln_tail_begin = 0x7fffffff;   // rows >= this carry NO strip sums (the one tail rule: n_rows % 320 <= 32): statistics from the row
+  int ln_tail_begin = 0x7fffffff;   // rows >= this carry NO strip sums (peeled_tail_rows, linear_plan.h): statistics from the row
   const float* ln_c = nullptr;      // [O] row sums of the gamma-scaled weight
   const float* ln_d = nullptr;      // [O] W beta + bias
   int ln_strips = 0, ln_D = 0;
@@ -340,8 +347,6 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(LinArgs a, int tile
 //    epilogue is a whole 128-byte line.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-enum : int { EPI_RES = 1, EPI_GATHER = 2, EPI_GELU = 4, EPI_STATS = 8, EPI_LNFOLD = 16, EPI_PRE = 32 };  // PRE: also store GELU's argument (training)
 
 // acc[mi][ni][r] = out[m0 + wr*64 + mi*16 + (lane & 15)][n0 + wc*64 + ni*16 + (lane>>4)*4 + r]
 // epi: this wave's 4 KiB LDS slice (16 rows x 256 B); one 16-row band (mi) at a time.  The band is written in the MFMA
@@ -1422,9 +1427,7 @@ __global__ __launch_bounds__(512, 1) void linear_mfma_bigtile_kernel(LinArgs a, 
 // ---------------------------------------------------------------------------------------------- dispatch
 static bool al(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-template <typename T>
-static bool mfma_eligible(const LinArgs& a) {
-  if (sizeof(T) != 2) return false;
+static bool mfma_eligible(const LinArgs& a) {  // of 16-bit operands
   if (a.K1 % 8 || a.K2 % 8 || a.O % 4) return false;
   if (a.ldx % 8 || a.ldw % 8 || (a.x2 && a.ldx2 % 8)) return false;                         // 16-byte operand rows
   if (a.ldy % 4 || (a.residual && a.ldr % 4) || (a.g1 && a.ldg1 % 4) || (a.g2 && a.ldg2 % 4)) return false;  // 8-byte epilogue
@@ -1438,7 +1441,6 @@ static int launch_generic(const LinArgs& a, hipStream_t st) {
   return check_launch("linear_generic_kernel");
 }
 
-template <typename T>
 static bool ring_eligible(const LinArgs& a) {
   // K-tiles are whole, and the per-lane 32-bit byte offsets of the DMA addressing (relative to a tile's first row) cover
   // one tile of each operand (at most 320 rows)
@@ -1502,109 +1504,8 @@ static int launch_bigtile(const LinArgs& a, hipStream_t st) {
   return check_launch("linear_mfma_bigtile_kernel");
 }
 
-// Estimated duration [us] of one launch on 256 CUs.  Both terms are measured rates: the K-loop moves (TBM + TBN) * 128 B
-// of operands per K-step at the ~44 GB/s per CU the LDS-DMA path sustains next to running MFMAs, the epilogue writes
-// TBM * TBN outputs at ~0.09 ns each; every round of tiles pays both.
-static double tile_cost_us(int tbm, int tbn, int rows, int O, int nk) {
-  const int64_t tiles = (int64_t)((rows + tbm - 1) / tbm) * ((O + tbn - 1) / tbn);
-  const double rounds = (double)((tiles + 255) / 256);
-  return rounds * (nk * (tbm + tbn) * 2.9e-3 + (double)tbm * tbn * 0.09e-3);
-}
-
-template <typename T, int EPI>
-static int launch_persistent(const LinArgs& a, hipStream_t st) {
-  const int nk = (a.K1 + a.K2) / BK;
-  const double c4 = tile_cost_us(256, 128, a.n_rows, a.O, nk), c3 = tile_cost_us(192, 128, a.n_rows, a.O, nk);
-  // 320 x 256 tiles; a few rows beyond a multiple of 320 (the icosphere's 10 * 4^r + 2 nodes) are computed on the VALU
-  // at the end of the same kernel (a column per wave) instead of costing a whole extra round of tiles
-  constexpr int kBigM = 320, kTail = 32;
-  const int rem = a.n_rows % kBigM;
-  const bool split = rem > 0 && rem <= kTail && a.n_rows > kBigM;
-  const int main_rows = split ? a.n_rows - rem : a.n_rows;
-  const double cb = tile_cost_us(kBigM, 256, main_rows, a.O, nk) + (split ? 0.5 : 0.0);
-  static const int force_big = [] { const char* e = getenv("ANEMOI_GEMM_BIG"); return e ? atoi(e) : -1; }();
-  const bool big = force_big >= 0 ? (force_big != 0 && a.O >= 64) : cb < 0.95 * (c3 < c4 ? c3 : c4);
-  if (big) {
-    LinArgs m = a;
-    m.n_rows = main_rows;
-    m.tail_rows = split ? rem : 0;
-    // Up to one round of 320 x 256 tiles: every CU ends its only tile at the same moment and the whole output (42 MB at
-    // [10242 x 512] -> 2048) is written behind the last K-step: ~8 us at the ~5 TB/s HBM takes writes, with nothing to overlap
-    // (tools/gemm_phase_timing.py).  160 x 256 tiles instead: two per CU, the first tile's output drains under the second
-    // tile's K-loop, whose rate is set by the MFMAs (power-limited clock: 1.9 us per 320-row K-step on random data against
-    // 0.7 us for its DMA, tools/dma_rate_probe.hip), not by the 44 % extra operand bytes.
-    static const int half_mi = [] { const char* e = getenv("ANEMOI_GEMM_BIG_MI"); return env_int(e, 5, 5, 10); }();
-    const int64_t t320 = (int64_t)((main_rows + 319) / 320) * ((a.O + 255) / 256);
-    // ... and up to two rounds of them (GraphConv's [81840 x 512] -> 512 edge GEMMs: 8.66 -> 8.36 ms per GNN forward); beyond
-    // that the drain is hidden anyway and the 320-row tile's lower operand traffic wins (N320: 15.5 against 15.85 ms)
-    static const int max_t320 = [] { const char* e = getenv("ANEMOI_GEMM_BIG_MI5_T320"); return env_int(e, 512, 0, 1 << 30); }();
-    if (half_mi == 5 && t320 <= max_t320) return launch_bigtile<T, EPI, 5>(m, st);
-    return launch_bigtile<T, EPI, 10>(m, st);
-  }
-  // narrow outputs with a long K in ONE round of 160 x 128 tiles (MLP-2 of the hidden mesh: [10242 x 2048] -> 512 = 64 x 4 tiles + 2
-  // tail rows): 128-wide K stages, K split over two wave groups (linear_mfma_splitwave_kernel<.., 5, 2, 2, 2>).  Measured on
-  // MI355X: 33.3 us against 34.5 on the 192 x 128 ring kernel; at K = 512 (projection) it is 1.2 us SLOWER, hence K >= 1024.
-  if constexpr ((EPI & (EPI_STATS | EPI_LNFOLD | EPI_PRE)) == 0) {
-    static const bool narrow = [] { const char* e = getenv("ANEMOI_GEMM_NARROW"); return !(e && e[0] == '0'); }();
-    constexpr int TM = 160;
-    const int rem160 = a.n_rows % TM;
-    const bool split160 = rem160 > 0 && rem160 <= 32 && a.n_rows > TM;
-    const int rows160 = split160 ? a.n_rows - rem160 : a.n_rows;
-    const int64_t t160 = (int64_t)((rows160 + TM - 1) / TM) * ((a.O + SN - 1) / SN);
-    if (narrow && t160 > 128 && t160 <= 256 && a.K2 == 0 && a.K1 >= 1024 && a.K1 % SK == 0 && a.splits == 1 && !a.f32_atomic && !big) {
-      LinArgs m = a;
-      m.n_rows = rows160;
-      m.tail_rows = split160 ? rem160 : 0;
-      static const int n64 = [] { const char* e = getenv("ANEMOI_GEMM_NARROW64"); return e ? atoi(e) : 0; }();
-      if (n64) return launch_splitwave<T, EPI, 5, 2, 2, 4, 64>(m, st);  // 64-wide stages, 4-deep ring
-      return launch_splitwave<T, EPI, 5, 2, 2, 2>(m, st);
-    }
-  }
-  // few tiles (small M, e.g. one rank's rows of a sharded mesh): 64 x 128 tiles on more CUs; the K-loop of a lone tile
-  // is bound by the ~40 cycles a CU needs per 1-KiB LDS-DMA piece, i.e. by the tile's operand bytes, like the model says
-  const double c1 = tile_cost_us(64, 128, a.n_rows, a.O, nk);
-  if (c1 < 0.9 * (c3 < c4 ? c3 : c4)) {
-    if constexpr ((EPI & EPI_LNFOLD) == 0) {
-      // at most one round of 64 x 128 tiles: give every tile 8 waves (K split over wave groups) instead of 2 (also with the
-      // row-statistics epilogue: the projection of a sharded mesh's block)
-      static const bool sw = [] { const char* e = getenv("ANEMOI_GEMM_SPLITWAVE"); return !(e && e[0] == '0'); }();
-      const int64_t t1 = (int64_t)((a.n_rows + SM - 1) / SM) * ((a.O + SN - 1) / SN);
-      if (sw && t1 <= 256 && a.K2 == 0 && a.K1 % SK == 0 && a.splits == 1 && !a.f32_atomic) return launch_splitwave<T, EPI>(a, st);
-    }
-    return launch_persistent_wm<T, EPI, 1, false, 2>(a, st);
-  }
-  static const bool pp = [] { const char* e = getenv("ANEMOI_GEMM_PP"); return !(e && e[0] == '0'); }();
-  if (pp) {
-    if (c3 < c4) return launch_persistent_wm<T, EPI, 3, true>(a, st);
-    return launch_persistent_wm<T, EPI, 4, true>(a, st);
-  }
-  if (c3 < c4) return launch_persistent_wm<T, EPI, 3, false>(a, st);
-  return launch_persistent_wm<T, EPI, 4, false>(a, st);
-}
-
 template <typename T>
-static int launch_mfma(const LinArgs& a, hipStream_t st) {
-  if (ring_eligible<T>(a)) {
-    const int epi = (a.residual ? EPI_RES : 0) | (a.g1 ? EPI_GATHER : 0) | (a.act == ANEMOI_ACT_GELU ? EPI_GELU : 0);
-    if (a.y_pre != nullptr) {  // act == GELU checked by the caller
-      switch (epi) {
-        case 4: return launch_persistent<T, 4 | EPI_PRE>(a, st);
-        case 5: return launch_persistent<T, 5 | EPI_PRE>(a, st);
-        case 6: return launch_persistent<T, 6 | EPI_PRE>(a, st);
-        default: return launch_persistent<T, 7 | EPI_PRE>(a, st);
-      }
-    }
-    switch (epi) {
-      case 0: return launch_persistent<T, 0>(a, st);
-      case 1: return launch_persistent<T, 1>(a, st);
-      case 2: return launch_persistent<T, 2>(a, st);
-      case 3: return launch_persistent<T, 3>(a, st);
-      case 4: return launch_persistent<T, 4>(a, st);
-      case 5: return launch_persistent<T, 5>(a, st);
-      case 6: return launch_persistent<T, 6>(a, st);
-      default: return launch_persistent<T, 7>(a, st);
-    }
-  }
+static int launch_mfma128(const LinArgs& a, hipStream_t st) {
   const int tiles_m = (a.n_rows + BM - 1) / BM, tiles_n = (a.O + BN - 1) / BN;
   const int num_tiles = tiles_m * tiles_n;
   static PerDeviceOnce attr_once;
@@ -1615,80 +1516,93 @@ static int launch_mfma(const LinArgs& a, hipStream_t st) {
   return check_launch("linear_mfma_kernel");
 }
 
-template <typename T, bool RES = true>
-static int launch_stats_producer(const LinArgs& a, hipStream_t st) {
-  // y = x W^T + b + residual, plus the row statistics of y for the LayerNorm the next GEMM folds in (O = 512-class outputs):
-  // the kernel choice of launch_persistent for this shape, with the statistics epilogue
-  const int nk = (a.K1 + a.K2) / BK;
-  const double c4 = tile_cost_us(256, 128, a.n_rows, a.O, nk), c3 = tile_cost_us(192, 128, a.n_rows, a.O, nk);
-  constexpr int EPI = (RES ? EPI_RES : 0) | EPI_STATS;  // without a residual: the embedding in front of a mapper's LayerNorm
-  {
-    constexpr int TM = 160;
-    // ONE tail rule on both sides of the fold: the consumer (launch_lnfold_consumer) recomputes the statistics of a row
-    // from the row itself only for the rows beyond a multiple of 320 (at most 32 of them) - so only those may be peeled
-    // here without strip sums.  A remainder of 161..192 mod 320 (<= 32 mod 160) goes through a ragged last tile, which
-    // writes the strip sums of every valid row.
-    const int rem320 = a.n_rows % 320;
-    const bool split160 = rem320 > 0 && rem320 <= 32 && a.n_rows > 320;
-    const int rem160 = split160 ? rem320 : 0;
-    const int rows160 = a.n_rows - rem160;
-    const int64_t t160 = (int64_t)((rows160 + TM - 1) / TM) * ((a.O + SN - 1) / SN);
-    static const bool narrow = [] { const char* e = getenv("ANEMOI_GEMM_NARROW"); return !(e && e[0] == '0'); }();
-    if (narrow && t160 > 128 && t160 <= 256 && a.K2 == 0 && a.K1 >= 1024 && a.K1 % SK == 0) {
-      LinArgs m = a;  // tail rows: computed a column per wave, WITHOUT strip sums (the consumer takes their statistics from the rows)
-      m.n_rows = rows160;
-      m.tail_rows = split160 ? rem160 : 0;
-      static const int n64 = [] { const char* e = getenv("ANEMOI_GEMM_NARROW64"); return e ? atoi(e) : 0; }();
-      if (n64) return launch_splitwave<T, EPI, 5, 2, 2, 4, 64>(m, st);
-      return launch_splitwave<T, EPI, 5, 2, 2, 2>(m, st);
-    }
-  }
-  (void)c3;
-  (void)c4;
-  return launch_persistent<T, EPI>(a, st);  // the kernel choice of the same shape without statistics (big tiles at 40 320 rows)
+// From here on: the plan of linear_plan.h mapped onto the leaf launchers above.
+static const GemmSwitches& gemm_switches() {
+  static const GemmSwitches sw = [] {  // read once per process; parsing, defaults and ranges are part of the switches' contract
+    const auto env = [](const char* name) { return getenv(name); };
+    const auto off = [&](const char* name) { const char* e = env(name); return e && e[0] == '0'; };
+    GemmSwitches s;
+    if (const char* e = env("ANEMOI_GEMM_BIG")) s.big = atoi(e);
+    s.big_mi = env_int(env("ANEMOI_GEMM_BIG_MI"), 5, 5, 10);
+    s.big_mi5_t320 = env_int(env("ANEMOI_GEMM_BIG_MI5_T320"), 512, 0, 1 << 30);
+    s.pp = !off("ANEMOI_GEMM_PP");
+    s.splitwave = !off("ANEMOI_GEMM_SPLITWAVE");
+    s.narrow = !off("ANEMOI_GEMM_NARROW");
+    s.narrow64 = ANEMOI_EXPERIMENT_ENV("ANEMOI_GEMM_NARROW64", 0, 0, 1 << 30) != 0;
+    s.fast_epi = off("ANEMOI_GEMM_FAST_EPI") ? 0 : 1;
+    s.lnfold_small_rows = env_int(env("ANEMOI_LNFOLD_SMALL_ROWS"), 4096, 0, 1 << 30);
+    if (const char* e = env("ANEMOI_LNFOLD_MI5")) s.lnfold_mi5 = atoi(e);
+    return s;
+  }();
+  return sw;
 }
 
-template <typename T>
-static int launch_lnfold_consumer(const LinArgs& a, hipStream_t st) {
-  constexpr int kBigM = 320, kTail = 32;
-  const int rem = a.n_rows % kBigM;
-  LinArgs m = a;
-  if (rem > 0 && rem <= kTail && a.n_rows > kBigM) {  // as in launch_persistent: tail rows on the VALU, in the same kernel
-    m.n_rows = a.n_rows - rem;
-    m.tail_rows = rem;
-  }
-  const int64_t t320 = (int64_t)((m.n_rows + 319) / 320) * ((a.O + 255) / 256);
-  // few rows (one rank's share of a sharded mesh, small meshes): a round of big tiles leaves most of the chip idle (642 rows =
-  // 3 x 8 tiles on 256 CUs) - the 64 x 128 kernels take the fold through their epilogue, statistics read from L1
-  static const int small_rows = [] { return env_int(getenv("ANEMOI_LNFOLD_SMALL_ROWS"), 4096, 0, 1 << 30); }();
-  if (a.n_rows < small_rows) {
-    LinArgs a2 = a;
-    if (rem > 0 && rem <= kTail && a.n_rows > kBigM) a2.ln_tail_begin = a.n_rows - rem;
-    const LinArgs& a = a2;
-    const double c34 = [&] { const int nk = a.K1 / BK; const double c4 = tile_cost_us(256, 128, a.n_rows, a.O, nk), c3 = tile_cost_us(192, 128, a.n_rows, a.O, nk); return c3 < c4 ? c3 : c4; }();
-    if (tile_cost_us(64, 128, a.n_rows, a.O, a.K1 / BK) < 0.9 * c34) {
-      const int64_t t1 = (int64_t)((a.n_rows + SM - 1) / SM) * ((a.O + SN - 1) / SN);
-      const bool gelu = a.act == ANEMOI_ACT_GELU;
-      if (t1 <= 256 && a.K1 % SK == 0)
-        return gelu ? launch_splitwave<T, EPI_LNFOLD | EPI_GELU>(a, st) : launch_splitwave<T, EPI_LNFOLD>(a, st);
-      return gelu ? launch_persistent_wm<T, EPI_LNFOLD | EPI_GELU, 1, false, 2>(a, st) : launch_persistent_wm<T, EPI_LNFOLD, 1, false, 2>(a, st);
-    }
-    // in between (a few thousand rows: the res-4 mesh, 2 562): the 192 x 128 kernel of the plain GEMM of the shape, lock-step schedule (the ping-pong one spills 80 registers with the fold)
-    const bool gelu = a.act == ANEMOI_ACT_GELU;
-    return gelu ? launch_persistent_wm<T, EPI_LNFOLD | EPI_GELU, 3, false, 2>(a, st) : launch_persistent_wm<T, EPI_LNFOLD, 3, false, 2>(a, st);
-  }
-  // 160-row tiles also beyond one round (40 320-row mapper GEMMs): the fold's epilogue has no registers to spare at 160
-  // accumulators per lane (MI = 10: +7 us on [40320 x 512] -> 1024), at 80 it is free; ANEMOI_LNFOLD_MI5=0 restores the rule
-  static const int always5 = [] { const char* e = getenv("ANEMOI_LNFOLD_MI5"); return e ? atoi(e) : 1; }();
-  if ((t320 <= 256 || always5) && m.n_rows % 160 == 0)  // two 160 x 256 tiles per CU (see launch_persistent)
-    return a.act == ANEMOI_ACT_GELU ? launch_bigtile<T, EPI_LNFOLD | EPI_GELU, 5>(m, st) : launch_bigtile<T, EPI_LNFOLD, 5>(m, st);
-  return a.act == ANEMOI_ACT_GELU ? launch_bigtile<T, EPI_LNFOLD | EPI_GELU, 10>(m, st) : launch_bigtile<T, EPI_LNFOLD, 10>(m, st);
+// Calls f with the runtime EPI bits as a compile-time constant.  The list is every epilogue the entry points can ask for: a
+// kernel is instantiated for these and for no other.
+template <int... E, typename F>
+static int with_epi(std::integer_sequence<int, E...>, int epi, F&& f) {
+  int rc = ANEMOI_E_INVALID;
+  if (!((epi == E && (rc = f(std::integral_constant<int, E>{}), true)) || ...)) set_error("linear: no kernel with epilogue %d", epi);
+  return rc;
 }
+using PlannedEpilogues = std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 7, 4 | EPI_PRE, 5 | EPI_PRE, 6 | EPI_PRE, 7 | EPI_PRE, EPI_STATS,
+                                               EPI_STATS | EPI_RES, EPI_LNFOLD, EPI_LNFOLD | EPI_GELU>;
 
 template <typename T>
-static int launch_splitk(const LinArgs& a, hipStream_t st) {
-  // 64 x 128 tiles (many tiles from a small output), lock-step schedule, plain epilogue
-  return launch_persistent_wm<T, 0, 1, false, 2>(a, st);
+static int launch_as(const GemmPlan& p, const LinArgs& a, hipStream_t st) {
+  if (p.kernel == GemmKernel::Generic) return launch_generic<T>(a, st);
+  if (p.kernel == GemmKernel::Mfma128) return launch_mfma128<T>(a, st);
+  return with_epi(PlannedEpilogues{}, p.epi, [&](auto epi) {
+    constexpr int EPI = decltype(epi)::value;
+    switch (p.kernel) {
+      case GemmKernel::BigTile:
+        return p.mi == 5 ? launch_bigtile<T, EPI, 5>(a, st) : launch_bigtile<T, EPI, 10>(a, st);
+      case GemmKernel::SplitWave:
+        if (p.tile_m == SM) return launch_splitwave<T, EPI>(a, st);
+        if constexpr ((EPI & (EPI_LNFOLD | EPI_PRE)) == 0) {  // the narrow 160 x 128 tile
+          if constexpr (kExperiments)
+            if (p.stage_k == 64) return launch_splitwave<T, EPI, 5, 2, 2, 4, 64>(a, st);
+          return launch_splitwave<T, EPI, 5, 2, 2, 2>(a, st);
+        }
+        break;
+      case GemmKernel::Ring:
+        if (p.tile_m == 64) return launch_persistent_wm<T, EPI, 1, false, 2>(a, st);
+        if (p.tile_m == 192 && !p.pingpong) return launch_persistent_wm<T, EPI, 3, false>(a, st);
+        if constexpr ((EPI & EPI_LNFOLD) == 0) {  // the fold runs lock-step on 192 rows only
+          if (p.tile_m == 192) return launch_persistent_wm<T, EPI, 3, true>(a, st);
+          return p.pingpong ? launch_persistent_wm<T, EPI, 4, true>(a, st) : launch_persistent_wm<T, EPI, 4, false>(a, st);
+        }
+        break;
+      default:
+        break;
+    }
+    set_error("linear: the plan names a kernel that is not built (kernel %d, %d rows, epilogue %d)", (int)p.kernel, p.tile_m, EPI);
+    return (int)ANEMOI_E_INVALID;
+  });
+}
+
+static GemmProblem problem_of(const LinArgs& a, GemmRole role, anemoi_dtype_t dtype) {
+  GemmProblem p;
+  p.role = role;
+  p.n_rows = a.n_rows, p.O = a.O, p.K1 = a.K1, p.K2 = a.K2;
+  p.residual = a.residual != nullptr, p.gather = a.g1 != nullptr, p.gelu = a.act == ANEMOI_ACT_GELU;
+  p.splits = a.splits, p.f32_atomic = a.f32_atomic != 0;
+  p.mfma_eligible = (dtype == ANEMOI_BF16 || dtype == ANEMOI_F16) && mfma_eligible(a);
+  p.ring_eligible = ring_eligible(a);
+  return p;
+}
+
+static int launch(const GemmProblem& p, LinArgs a, anemoi_dtype_t dtype, hipStream_t st) {
+  const GemmPlan plan = plan_gemm(p, gemm_switches());
+  a.n_rows = plan.main_rows;
+  a.tail_rows = plan.tail_rows;
+  a.ln_tail_begin = plan.ln_tail_begin;
+  switch (dtype) {
+    case ANEMOI_F32: return launch_generic<float>(a, st);  // never MFMA-eligible: the plan is the generic kernel
+    case ANEMOI_BF16: return launch_as<bf16_t>(plan, a, st);
+    case ANEMOI_F16: return launch_as<f16_t>(plan, a, st);
+    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
+  }
 }
 
 }  // namespace anemoi
@@ -1706,8 +1620,7 @@ extern "C" int anemoi_linear_splitk_f32(const void* x, int64_t ldx, const void* 
   LinArgs a{x, ldx, K, nullptr, 0, 0, w, ldw, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, y, ldy, n_rows, O, (int)ANEMOI_ACT_NONE};
   a.splits = splits;
   a.f32_atomic = 1;
-  hipStream_t st = as_stream(stream);
-  return dtype == ANEMOI_BF16 ? launch_splitk<bf16_t>(a, st) : launch_splitk<f16_t>(a, st);
+  return launch(problem_of(a, GemmRole::SplitK, dtype), a, dtype, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_stats_fwd(const void* x, int64_t ldx, int32_t K, const void* w, int64_t ldw, const void* bias,
@@ -1718,14 +1631,12 @@ extern "C" int anemoi_linear_stats_fwd(const void* x, int64_t ldx, int32_t K, co
   ANEMOI_REQUIRE(O % 64 == 0 && K % BK == 0, "linear_stats_fwd: O=%d and K=%d must be multiples of 64", O, K);
   LinArgs a{x, ldx, K, nullptr, 0, 0, w, ldw, bias, nullptr, 0, nullptr, nullptr, 0, nullptr, residual, ldr, y, ldy, n_rows, O, (int)ANEMOI_ACT_NONE};
   a.stats_out = stats_out;
-  const bool ok = dtype == ANEMOI_BF16 ? (mfma_eligible<bf16_t>(a) && ring_eligible<bf16_t>(a)) : (mfma_eligible<f16_t>(a) && ring_eligible<f16_t>(a));
-  if (!ok) {
+  const GemmProblem p = problem_of(a, GemmRole::StatsProducer, dtype);
+  if (!(p.mfma_eligible && p.ring_eligible)) {
     set_error("linear_stats_fwd: operands not eligible for the ring kernel (alignment)");
     return ANEMOI_E_UNSUPPORTED;
   }
-  hipStream_t st = as_stream(stream);
-  if (residual == nullptr) return dtype == ANEMOI_BF16 ? launch_stats_producer<bf16_t, false>(a, st) : launch_stats_producer<f16_t, false>(a, st);
-  return dtype == ANEMOI_BF16 ? launch_stats_producer<bf16_t>(a, st) : launch_stats_producer<f16_t>(a, st);
+  return launch(p, a, dtype, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_lnfold_fwd(const void* x, int64_t ldx, int32_t K, const void* w_scaled, int64_t ldw, const float* ln_c,
@@ -1742,15 +1653,12 @@ extern "C" int anemoi_linear_lnfold_fwd(const void* x, int64_t ldx, int32_t K, c
   a.ln_strips = strips;
   a.ln_D = K;
   a.ln_eps = eps;
-  const bool ok = dtype == ANEMOI_BF16 ? (mfma_eligible<bf16_t>(a) && ring_eligible<bf16_t>(a)) : (mfma_eligible<f16_t>(a) && ring_eligible<f16_t>(a));
-  if (!ok || (reinterpret_cast<uintptr_t>(ln_c) & 15) || (reinterpret_cast<uintptr_t>(ln_d) & 15)) {
+  const GemmProblem p = problem_of(a, GemmRole::FoldConsumer, dtype);
+  if (!(p.mfma_eligible && p.ring_eligible) || !al(ln_c, 16) || !al(ln_d, 16)) {
     set_error("linear_lnfold_fwd: operands not eligible for the big-tile kernel (alignment)");
     return ANEMOI_E_UNSUPPORTED;
   }
-  hipStream_t st = as_stream(stream);
-  const int rc = dtype == ANEMOI_BF16 ? launch_lnfold_consumer<bf16_t>(a, st) : launch_lnfold_consumer<f16_t>(a, st);
-  if (rc == ANEMOI_E_UNSUPPORTED) set_error("linear_lnfold_fwd: n_rows=%d leaves tail rows (not a multiple of 320 within 32)", n_rows);
-  return rc;
+  return launch(p, a, dtype, as_stream(stream));
 }
 
 static int linear_fwd_impl(const void* x, int64_t ldx, int32_t K1, const void* x2, int64_t ldx2, int32_t K2,
@@ -1766,26 +1674,16 @@ static int linear_fwd_impl(const void* x, int64_t ldx, int32_t K1, const void* x
   ANEMOI_REQUIRE((g1 == nullptr) == (idx1 == nullptr) && (g2 == nullptr) == (idx2 == nullptr), "linear_fwd: gather term needs both table and index");
   ANEMOI_REQUIRE(act == ANEMOI_ACT_NONE || act == ANEMOI_ACT_GELU, "linear_fwd: unknown activation %d", (int)act);
   LinArgs a{x, ldx, K1, x2, ldx2, K2, w, ldw, bias, g1, ldg1, idx1, g2, ldg2, idx2, residual, ldr, y, ldy, n_rows, O, (int)act};
-  static const int fast_epi = [] { const char* e = getenv("ANEMOI_GEMM_FAST_EPI"); return (e && e[0] == '0') ? 0 : 1; }();
-  a.fast_epi = fast_epi;
-  hipStream_t st = as_stream(stream);
-  if (y_pre != nullptr) {  // only the DMA-ring kernels (shared epilogue) store the pre-activation
-    a.y_pre = y_pre;
-    a.ldy_pre = ldy_pre;
-    const bool ok = act == ANEMOI_ACT_GELU && ldy_pre >= O && ldy_pre % 8 == 0 && al(y_pre, 16) &&
-                    ((dtype == ANEMOI_BF16 && mfma_eligible<bf16_t>(a) && ring_eligible<bf16_t>(a)) ||
-                     (dtype == ANEMOI_F16 && mfma_eligible<f16_t>(a) && ring_eligible<f16_t>(a)));
-    if (!ok) {
-      set_error("linear_fwd_pre: the pre-activation output needs act = GELU on a DMA-ring GEMM shape (16-bit, K %% 64 == 0)");
-      return ANEMOI_E_UNSUPPORTED;
-    }
+  a.fast_epi = gemm_switches().fast_epi;
+  a.y_pre = y_pre;
+  a.ldy_pre = y_pre ? ldy_pre : 0;
+  const GemmProblem p = problem_of(a, y_pre ? GemmRole::PlainPre : GemmRole::Plain, dtype);
+  // only the DMA-ring kernels (shared epilogue) store the pre-activation
+  if (y_pre && !(act == ANEMOI_ACT_GELU && ldy_pre >= O && ldy_pre % 8 == 0 && al(y_pre, 16) && p.mfma_eligible && p.ring_eligible)) {
+    set_error("linear_fwd_pre: the pre-activation output needs act = GELU on a DMA-ring GEMM shape (16-bit, K %% 64 == 0)");
+    return ANEMOI_E_UNSUPPORTED;
   }
-  switch (dtype) {
-    case ANEMOI_F32: return launch_generic<float>(a, st);
-    case ANEMOI_BF16: return mfma_eligible<bf16_t>(a) ? launch_mfma<bf16_t>(a, st) : launch_generic<bf16_t>(a, st);
-    case ANEMOI_F16: return mfma_eligible<f16_t>(a) ? launch_mfma<f16_t>(a, st) : launch_generic<f16_t>(a, st);
-    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
-  }
+  return launch(p, a, dtype, as_stream(stream));
 }
 
 extern "C" int anemoi_linear_fwd(const void* x, int64_t ldx, int32_t K1, const void* x2, int64_t ldx2, int32_t K2,
@@ -1805,4 +1703,37 @@ extern "C" int anemoi_linear_fwd_pre(const void* x, int64_t ldx, int32_t K1, con
   ANEMOI_REQUIRE(y_pre != nullptr, "linear_fwd_pre: null y_pre");
   return linear_fwd_impl(x, ldx, K1, x2, ldx2, K2, w, ldw, bias, g1, ldg1, idx1, g2, ldg2, idx2, residual, ldr, y, ldy, y_pre, ldy_pre,
                          n_rows, O, act, dtype, stream);
+}
+
+extern "C" int anemoi_linear_plan(int32_t role, int32_t n_rows, int32_t O, int32_t K1, int32_t K2, int32_t epilogue_bits, anemoi_dtype_t dtype,
+                                  anemoi_linear_plan_t* out) {
+  ANEMOI_REQUIRE(out != nullptr, "linear_plan: null out");
+  ANEMOI_REQUIRE(role >= (int)GemmRole::Plain && role <= (int)GemmRole::SplitK, "linear_plan: unknown role %d", role);
+  ANEMOI_REQUIRE(n_rows > 0 && O > 0 && K1 > 0 && K2 >= 0, "linear_plan: bad sizes n_rows=%d O=%d K1=%d K2=%d", n_rows, O, K1, K2);
+  ANEMOI_REQUIRE((epilogue_bits & ~(EPI_RES | EPI_GATHER | EPI_GELU)) == 0, "linear_plan: unknown epilogue bits %d", epilogue_bits);
+  ANEMOI_REQUIRE(dtype == ANEMOI_F32 || dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "unknown dtype %d", (int)dtype);
+  // contiguous, 16-byte aligned operands: never dereferenced, only their alignment is looked at
+  const void* const p = reinterpret_cast<const void*>(uintptr_t{16});
+  const auto given = [&](int bit) { return (epilogue_bits & bit) ? p : nullptr; };
+  LinArgs a{p, K1, K1, K2 ? p : nullptr, K2, K2, p, (int64_t)K1 + K2, nullptr, given(EPI_GATHER), O, nullptr, nullptr, 0, nullptr, given(EPI_RES), O,
+            const_cast<void*>(p), O, n_rows, O, (epilogue_bits & EPI_GELU) ? (int)ANEMOI_ACT_GELU : (int)ANEMOI_ACT_NONE};
+  GemmProblem g = problem_of(a, (GemmRole)role, dtype);
+  g.f32_atomic = g.role == GemmRole::SplitK;
+  // what the entry point of the role asks of the shape before it plans
+  const bool one_k = K2 == 0 && K1 % BK == 0, dma = g.mfma_eligible && g.ring_eligible;
+  bool ok = true;
+  switch (g.role) {
+    case GemmRole::Plain: break;
+    case GemmRole::PlainPre: ok = g.gelu && dma; break;
+    case GemmRole::StatsProducer: ok = one_k && O % 64 == 0 && dma; break;
+    case GemmRole::FoldConsumer: ok = one_k && O % 8 == 0 && dma; break;
+    case GemmRole::SplitK: ok = one_k && O % 4 == 0 && dtype != ANEMOI_F32; break;
+  }
+  if (!ok) {
+    set_error("linear_plan: the entry point of role %d does not take this shape (n_rows=%d O=%d K1=%d K2=%d dtype=%d)", role, n_rows, O, K1, K2, (int)dtype);
+    return ANEMOI_E_UNSUPPORTED;
+  }
+  const GemmPlan q = plan_gemm(g, gemm_switches());
+  *out = {(int32_t)q.kernel, q.tile_m, q.tile_n, q.pingpong, q.stage_k, q.mi, q.wr, q.kg, q.stages, q.epi, q.main_rows, q.tail_rows, q.ln_tail_begin};
+  return ANEMOI_OK;
 }

@@ -12,7 +12,7 @@ The op-level mirror of the reference boundary is at the bottom:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import os
 
@@ -952,6 +952,44 @@ def linear_ln_folded(x: Tensor, w_scaled: Tensor, c: Tensor, d: Tensor, stats: T
         return None
     _lib.check(rc, "linear_lnfold_fwd")
     return y
+
+
+GEMM_ROLES = ("plain", "plain_pre", "stats_producer", "fold_consumer", "split_k")  # which entry point: GemmRole of csrc/linear_plan.h
+GEMM_KERNELS = ("generic", "mfma128", "ring", "splitwave", "bigtile")                # GemmKernel
+
+
+class GemmPlan(NamedTuple):
+    """What a GEMM entry point launches for a shape: ``kernel`` (one of GEMM_KERNELS) on ``tile_m`` x ``tile_n`` output tiles, rows
+    [0, main_rows) on the tiles and ``tail_rows`` more on the VALU; the other fields as in anemoi_linear_plan_t (include/anemoi_hip.h)."""
+    kernel: str
+    tile_m: int
+    tile_n: int
+    pingpong: bool
+    stage_k: int
+    mi: int
+    wr: int
+    kg: int
+    stages: int
+    epi: int
+    main_rows: int
+    tail_rows: int
+    ln_tail_begin: int
+
+
+def linear_plan(role: str, n_rows: int, K: int, O: int, *, K2: int = 0, residual: bool = False, gather: bool = False, gelu: bool = False,
+                dtype: torch.dtype = torch.bfloat16) -> Optional[GemmPlan]:
+    """The kernel choice of ``linear`` / ``linear_with_row_stats`` / ``linear_ln_folded`` / the split-K GEMM (``role``: one of
+    GEMM_ROLES) for contiguous operands of this shape, under the environment switches of this process.  Host-only: nothing is
+    launched and no GPU is needed.  None where the entry point of the role does not take the shape."""
+    out = _lib.LinearPlan()
+    bits = (1 if residual else 0) | (2 if gather else 0) | (4 if gelu else 0)
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}[dtype]
+    rc = _lib.load().anemoi_linear_plan(GEMM_ROLES.index(role), n_rows, O, K, K2, bits, code, out)
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "linear_plan")
+    f = {name: getattr(out, name) for name, _ in out._fields_}
+    return GemmPlan(**{**f, "kernel": GEMM_KERNELS[out.kernel], "pingpong": bool(out.pingpong)})
 
 
 # ------------------------------------------------------------------------------------------ row-resident layer chain

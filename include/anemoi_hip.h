@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 16
+#define ANEMOI_HIP_ABI_VERSION 17
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -221,10 +221,11 @@ int anemoi_gelu_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t n_
  *    no atomics, no zeroing, deterministic.  O and K multiples of 64.
  *  - anemoi_linear_lnfold_fwd: y = act(LN(x) W^T + b) from raw x [n_rows, K], w_scaled = W diag(gamma) [O, K], fp32 c, d [O]
  *    and stats_in = the producer's statistics of x (strips * 64 == K).  Partials are added in a fixed order.
- *  The pair is a two-kernel protocol with ONE tail rule on both sides: when n_rows exceeds a multiple of 320 by at most 32
- *  (the "+ 2" of an icosphere's 10 * 4^r + 2 nodes) the producer may compute those trailing rows outside its tiles and
- *  leaves their stats_out entries UNWRITTEN; the consumer never reads them - it takes the statistics of exactly those rows
- *  (n_rows % 320 <= 32) from the rows themselves.  Every other row has its strip sums written (ragged last tiles included).
+ *  The pair is a two-kernel protocol with ONE tail rule on both sides (peeled_tail_rows in csrc/linear_plan.h: the "+ 2" of an
+ *  icosphere's 10 * 4^r + 2 nodes): the producer may compute the rows that rule names outside its tiles and leaves their
+ *  stats_out entries UNWRITTEN; the consumer never reads them - it takes the statistics of exactly those rows from the rows
+ *  themselves.  Every other row has its strip sums written (ragged last tiles included).  anemoi_linear_plan tells which rows:
+ *  [main_rows, n_rows) of the producer's plan.
  * Replaces the two LayerNorm launches of a GraphTransformerProcessorBlock (layer_norm_attention / layer_norm_mlp_dst,
  * layers/block.py:1237, 1271) and layer_norm_attention_src / _dest of a GraphTransformerMapperBlock (layers/block.py:979-984)
  * in the unsharded inference path.  Returns ANEMOI_E_UNSUPPORTED for shapes / alignments the
@@ -270,6 +271,23 @@ int anemoi_linear_fwd_pre(const void* x, int64_t ldx, int32_t K1, const void* x2
                           int64_t ldw, const void* bias, const void* g1, int64_t ldg1, const int32_t* idx1, const void* g2,
                           int64_t ldg2, const int32_t* idx2, const void* residual, int64_t ldr, void* y, int64_t ldy, void* y_pre,
                           int64_t ldy_pre, int32_t n_rows, int32_t O, anemoi_act_t act, anemoi_dtype_t dtype, void* stream);
+
+/* Which kernel the GEMM entry points above run for a shape, and how they split its rows: the decision of csrc/linear_plan.h, asked
+ * without launching anything.  HOST-ONLY: no HIP call, no device needed.  role: 0 anemoi_linear_fwd, 1 anemoi_linear_fwd_pre,
+ * 2 anemoi_linear_stats_fwd, 3 anemoi_linear_lnfold_fwd, 4 anemoi_linear_splitk_f32;  epilogue_bits: 1 residual, 2 gather-add, 4 GELU.
+ * The operands are taken to be contiguous and 16-byte aligned (ldx = K1, ldx2 = K2, ldw = K1 + K2, every other ld = O), and the
+ * environment switches are those of the calling process.  ANEMOI_E_UNSUPPORTED where the entry point itself would refuse the shape.
+ *   kernel: 0 generic (VALU), 1 128 x 128 register-staged MFMA, 2 DMA ring, 3 split-wave (K split over wave groups), 4 big tile;
+ *   tile_m x tile_n: the output tile; stage_k: K elements per LDS stage; mi, wr, kg, stages: the template arguments of the kernels
+ *   that have them (0 otherwise); epi: the epilogue the kernel is instantiated with (1 residual, 2 gather-add, 4 GELU, 8 row
+ *   statistics, 16 LayerNorm fold, 32 pre-activation store);  rows [0, main_rows) run on the tiles, [main_rows, main_rows +
+ *   tail_rows) on the VALU at the end of the same kernel; a fold consumer on the small tiles takes the statistics of the rows from
+ *   ln_tail_begin on from the rows themselves (INT32_MAX: of none). */
+typedef struct {
+  int32_t kernel, tile_m, tile_n, pingpong, stage_k, mi, wr, kg, stages, epi, main_rows, tail_rows, ln_tail_begin;
+} anemoi_linear_plan_t;
+int anemoi_linear_plan(int32_t role, int32_t n_rows, int32_t O, int32_t K1, int32_t K2, int32_t epilogue_bits, anemoi_dtype_t dtype,
+                       anemoi_linear_plan_t* out);
 
 /* GraphConv edge epilogue + aggregation, one pass over the dst-sorted edges (no atomics).
  * Replaces: MLP.layer_norm + "+ edge_attr" + scatter(sum) (layers/conv.py:73-81, layers/mlp.py:176-178).

@@ -51,7 +51,7 @@ def test_product_library_carries_no_experiment_switches():
         build_library(verbose=False)
     blob = open(_lib.LIB_PATH, "rb").read()
     for name in (b"_DBG", b"ANEMOI_CHAIN2_PRIO", b"ANEMOI_CHAIN2_B_DELAY", b"ANEMOI_CHAIN2_WARM", b"ANEMOI_GNN_CHAIN_V2", b"ANEMOI_CHAIN_PRIO_YOUNG",
-                 b"anemoi_gt_chain_fwd", b"anemoi_gnn_edge_chain_timeline", b"gnn_edge_chain2_kernel", b"gt_chain_kernel"):
+                 b"anemoi_gt_chain_fwd", b"anemoi_gnn_edge_chain_timeline", b"gnn_edge_chain2_kernel", b"gt_chain_kernel", b"ANEMOI_GEMM_NARROW64"):
         assert name not in blob, name
     lib = _lib.load()
     for name in _lib.EXPERIMENT_SIGNATURES:

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import gt_oracle as O
+from tests.linear_shapes import CONCAT_GATHER_SHAPES, EPILOGUE_SHAPES, FOLD_D, FOLD_HIDDEN, FOLD_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -263,11 +264,7 @@ def _lin_ref(x, w, b=None, act=None, res=None, x2=None, g1=None, i1=None, g2=Non
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("N,K,O", [(300, 512, 512), (1000, 512, 2048), (257, 2048, 512), (129, 64, 128), (70, 20, 64), (50, 11, 7), (333, 512, 100), (5, 64, 64),
-                                   (1300, 512, 2048), (2100, 2048, 512), (1111, 512, 512), (1030, 64, 100), (1500, 72, 512),
-                                   (4200, 512, 2048), (3000, 192, 3072),  # > 256 tiles: several tiles per persistent workgroup
-                                   (10242, 512, 512),  # 192-row tile variant (216 tiles instead of 164 of 256 rows)
-                                   (10242, 512, 2048), (10242, 192, 2048)])  # 320x256 big tile, one per CU, + 2 tail rows on the VALU
+@pytest.mark.parametrize("N,K,O", EPILOGUE_SHAPES)
 def test_linear_epilogues(ops, dtype, N, K, O):
     gen = torch.Generator().manual_seed(N + K + O)
     x = torch.randn(N, K, generator=gen).to(dtype)
@@ -283,8 +280,7 @@ def test_linear_epilogues(ops, dtype, N, K, O):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("N,K1,K2,O", [(400, 512, 512, 512), (90, 32, 32, 32), (200, 128, 64, 256), (1400, 512, 512, 512), (1200, 128, 64, 256),
-                                       (10242, 256, 256, 2048)])  # big tile + tail rows with the K-concat / gather-add epilogue
+@pytest.mark.parametrize("N,K1,K2,O", CONCAT_GATHER_SHAPES)
 def test_linear_concat_and_gather(ops, dtype, N, K1, K2, O):
     gen = torch.Generator().manual_seed(N + K1)
     x, x2 = torch.randn(N, K1, generator=gen).to(dtype), torch.randn(N, K2, generator=gen).to(dtype)
@@ -390,14 +386,12 @@ def test_cpu_tensor_fails_loudly(ops):
 
 # ------------------------------------------------------------------------------------------ LayerNorm fold
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-# 320-row tiles + 2 tail rows / whole tiles / partial last tile / tail of 10 / 320 k + 162 and 320 k + 192: <= 32 rows beyond a multiple
-# of 160 but NOT of 320 (the producer used to peel them without strip sums while the consumer expected sums)
-@pytest.mark.parametrize("N", [10242, 640, 4000, 330, 5282, 5312, 642, 1469, 2562])  # the last three: small-tile consumers (< 4096 rows)
+@pytest.mark.parametrize("N", FOLD_ROWS)  # what each row count is there for: tests/linear_shapes.py
 def test_layernorm_folded_into_neighbouring_gemms(ops, dtype, N):
     """anemoi_linear_stats_fwd + anemoi_linear_lnfold_fwd: y = h W2^T + b2 + res with row statistics, then
     act(LN(y) W1^T + b1) from the raw y — against fp32 torch, and the producer's y equal to the plain GEMM's to rounding."""
     gen = torch.Generator().manual_seed(N)
-    D, Hd = 512, 2048
+    D, Hd = FOLD_D, FOLD_HIDDEN
     h = torch.randn(N, Hd, generator=gen).to(dtype)
     w2, b2 = (torch.randn(D, Hd, generator=gen) / 45).to(dtype), (0.1 * torch.randn(D, generator=gen)).to(dtype)
     res = (2.0 * torch.randn(N, D, generator=gen) + 0.5).to(dtype)
@@ -412,8 +406,8 @@ def test_layernorm_folded_into_neighbouring_gemms(ops, dtype, N):
     yf = y.float()
     # a few rows beyond a multiple of the 320-row tile (the icosphere's "+ 2") are computed a column per wave and carry NO strip
     # sums (include/anemoi_hip.h): the folding consumer takes the statistics of such rows from the rows themselves - ONE rule
-    # (n_rows % 320 <= 32) on both sides
-    nst = N - N % 320 if 0 < N % 320 <= 32 and N > 320 else N
+    # on both sides (peeled_tail_rows, csrc/linear_plan.h); the producer's plan says which rows it is for this N
+    nst = ops.linear_plan("stats_producer", N, Hd, D, residual=True, dtype=dtype).main_rows
     s = stats[:nst].sum(1)
     assert float((s[:, 0] - yf[:nst].sum(1)).abs().max()) < 1e-3
     assert float((s[:, 1] - (yf[:nst] * yf[:nst]).sum(1)).abs().max()) < 1e-3 * float((yf * yf).sum(1).max())
