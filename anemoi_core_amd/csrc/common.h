@@ -55,6 +55,24 @@ __device__ __forceinline__ f16_t from_float<f16_t>(float v) {
   return r;
 }
 
+// Runtime dtype -> element type: calls f with a tag whose ::type is float / bf16_t / f16_t and returns f's int, e.g.
+//   return dispatch_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type; return launch_x<T>(...); });
+// f is instantiated once per element type, so function-local statics belong in the named templates it calls, not in f.
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+
+template <typename F>
+inline int dispatch_dtype(anemoi_dtype_t dtype, F&& f) {
+  switch (dtype) {
+    case ANEMOI_F32: return f(type_tag<float>{});
+    case ANEMOI_BF16: return f(type_tag<bf16_t>{});
+    case ANEMOI_F16: return f(type_tag<f16_t>{});
+    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
+  }
+}
+
 // Vector of N elements of T moved with the widest possible instructions (N*sizeof(T) in {2,4,8,16,32,64}).
 template <typename T, int N>
 struct alignas(sizeof(T) * N >= 16 ? 16 : sizeof(T) * N) Vec {

@@ -608,12 +608,7 @@ static int launch(const AttnArgs& a) {
 }
 
 static int dispatch(const AttnArgs& a, anemoi_dtype_t dtype) {
-  switch (dtype) {
-    case ANEMOI_F32: return launch<float>(a);
-    case ANEMOI_BF16: return launch<bf16_t>(a);
-    case ANEMOI_F16: return launch<f16_t>(a);
-    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) { return launch<typename decltype(t)::type>(a); });
 }
 
 }  // namespace anemoi
@@ -685,13 +680,11 @@ extern "C" int anemoi_pack_edge_weights(const void* w_edge, const void* b_edge, 
   ANEMOI_REQUIRE(w_edge && out, "pack_edge_weights: null pointer");
   const int n = D * fe_pad;
   const dim3 grid((n + 255) / 256), block(256);
-  switch (dtype) {
-    case ANEMOI_F32: hipLaunchKernelGGL((pack_edge_weights_kernel<float>), grid, block, 0, as_stream(stream), (const float*)w_edge, (const float*)b_edge, out, D, fe, fe_pad); break;
-    case ANEMOI_BF16: hipLaunchKernelGGL((pack_edge_weights_kernel<bf16_t>), grid, block, 0, as_stream(stream), (const bf16_t*)w_edge, (const bf16_t*)b_edge, out, D, fe, fe_pad); break;
-    case ANEMOI_F16: hipLaunchKernelGGL((pack_edge_weights_kernel<f16_t>), grid, block, 0, as_stream(stream), (const f16_t*)w_edge, (const f16_t*)b_edge, out, D, fe, fe_pad); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-  return check_launch("pack_edge_weights_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((pack_edge_weights_kernel<T>), grid, block, 0, as_stream(stream), (const T*)w_edge, (const T*)b_edge, out, D, fe, fe_pad);
+    return check_launch("pack_edge_weights_kernel");
+  });
 }
 
 extern "C" int anemoi_pack_edge_features(const void* edge_attr, int64_t ld, float* out, int32_t M, int32_t fe,
@@ -701,11 +694,9 @@ extern "C" int anemoi_pack_edge_features(const void* edge_attr, int64_t ld, floa
   ANEMOI_REQUIRE(edge_attr && out, "pack_edge_features: null pointer");
   const int64_t n = (int64_t)M * fe_pad;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  switch (dtype) {
-    case ANEMOI_F32: hipLaunchKernelGGL((pack_edge_features_kernel<float>), grid, block, 0, as_stream(stream), (const float*)edge_attr, ld, out, M, fe, fe_pad); break;
-    case ANEMOI_BF16: hipLaunchKernelGGL((pack_edge_features_kernel<bf16_t>), grid, block, 0, as_stream(stream), (const bf16_t*)edge_attr, ld, out, M, fe, fe_pad); break;
-    case ANEMOI_F16: hipLaunchKernelGGL((pack_edge_features_kernel<f16_t>), grid, block, 0, as_stream(stream), (const f16_t*)edge_attr, ld, out, M, fe, fe_pad); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-  return check_launch("pack_edge_features_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((pack_edge_features_kernel<T>), grid, block, 0, as_stream(stream), (const T*)edge_attr, ld, out, M, fe, fe_pad);
+    return check_launch("pack_edge_features_kernel");
+  });
 }

@@ -725,12 +725,7 @@ extern "C" int anemoi_gt_attention_dropout_bwd(const void* q, int64_t ldq, const
             dq, dk, dv, de, lddq, lddk, lddv, ldde, p_ws, ds_ws, n_dst, n_src, H, C, as_stream(stream)};
   a.drop_p = drop_p;
   a.drop_seed = drop_seed;
-  switch (dtype) {
-    case ANEMOI_F32: return launch<float>(a);
-    case ANEMOI_BF16: return launch<bf16_t>(a);
-    case ANEMOI_F16: return launch<f16_t>(a);
-    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) { return launch<typename decltype(t)::type>(a); });
 }
 
 extern "C" int anemoi_gt_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
@@ -771,10 +766,5 @@ extern "C" int anemoi_gt_attention_fused_edge_bwd(const void* q, int64_t ldq, co
                  edge_feat, w_packed, fe_pad, d_w_packed, d_edge_feat, sf_ws, d_edge_feat ? qg_ws : nullptr, part_ws, n_edges,
                  addend, ldadd, d_addend, lddadd};
   ANEMOI_REQUIRE((addend == nullptr || ldadd >= D) && (d_addend == nullptr || lddadd >= D), "gt_attention_fused_edge_bwd: addend stride");
-  switch (dtype) {
-    case ANEMOI_F32: return launch_fused<float>(f);
-    case ANEMOI_BF16: return launch_fused<bf16_t>(f);
-    case ANEMOI_F16: return launch_fused<f16_t>(f);
-    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) { return launch_fused<typename decltype(t)::type>(f); });
 }

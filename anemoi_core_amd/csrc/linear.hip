@@ -1597,12 +1597,14 @@ static int launch(const GemmProblem& p, LinArgs a, anemoi_dtype_t dtype, hipStre
   a.n_rows = plan.main_rows;
   a.tail_rows = plan.tail_rows;
   a.ln_tail_begin = plan.ln_tail_begin;
-  switch (dtype) {
-    case ANEMOI_F32: return launch_generic<float>(a, st);  // never MFMA-eligible: the plan is the generic kernel
-    case ANEMOI_BF16: return launch_as<bf16_t>(plan, a, st);
-    case ANEMOI_F16: return launch_as<f16_t>(plan, a, st);
-    default: set_error("unknown dtype %d", (int)dtype); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if constexpr (sizeof(T) == 4) {
+      return launch_generic<T>(a, st);  // fp32 is never MFMA-eligible: the plan is the generic kernel
+    } else {
+      return launch_as<T>(plan, a, st);
+    }
+  });
 }
 
 }  // namespace anemoi

@@ -5,31 +5,18 @@
 // Reference semantics: torch.nn.LayerNorm (eps inside sqrt, biased variance, affine) as instantiated by
 // layer_kernels.LayerNorm (models/src/anemoi/models/layers/utils.py:107-121); GraphConv's
 // "edge_mlp(...) + edge_attr" followed by scatter-sum (models/src/anemoi/models/layers/conv.py:73-81).
+//
+// rowwise_common.h holds what this file shares with rowwise_bwd.hip: load_row / store_row, the (VEC, CH) pick rule and the
+// dispatchers from the picked values to template arguments; the dtype switch is dispatch_dtype (common.h).
 #include <stdlib.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "rowwise_common.h"
 
 namespace anemoi {
 
 constexpr int kRowWaves = 4;   // waves (rows) per block
-constexpr int kMaxChunksLimit = 8;  // register-resident chunks per lane (template CH): D <= 64*VEC*CH
-
-// Load a row into registers as float: x[lane*VEC + t*64*VEC + j], t < nchunks.
-template <typename T, int VEC, int CH>
-__device__ __forceinline__ void load_row(const T* __restrict__ p, int D, int lane, float (&r)[CH][VEC]) {
-#pragma unroll
-  for (int t = 0; t < CH; ++t) {
-    const int c = (t * 64 + lane) * VEC;
-    if (c < D) {
-      load_vec<T, VEC>(p + c, r[t]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) r[t][j] = 0.f;
-    }
-  }
-}
 
 // In-register LayerNorm of one row held across the wave: two-pass (mean, then centred variance).
 template <typename T, int VEC, int CH>
@@ -69,15 +56,6 @@ __device__ __forceinline__ void normalise_row(float (&r)[CH][VEC], int D, int la
 #pragma unroll
       for (int j = 0; j < VEC; ++j) r[t][j] = fmaf((r[t][j] - mean) * rstd, g[j] + gadd, b[j]);
     }
-  }
-}
-
-template <typename T, int VEC, int CH>
-__device__ __forceinline__ void store_row(T* __restrict__ p, int D, int lane, const float (&r)[CH][VEC]) {
-#pragma unroll
-  for (int t = 0; t < CH; ++t) {
-    const int c = (t * 64 + lane) * VEC;
-    if (c < D) store_vec<T, VEC>(p + c, r[t]);
   }
 }
 
@@ -646,57 +624,27 @@ __global__ void affine_columns_kernel(const T* __restrict__ x, int64_t ldx, T* _
   y[(int64_t)r * ldy + c] = from_float<T>(o);
 }
 
-// Pick the widest vector width (in elements) such that rows stay 16-byte-or-narrower aligned and D % VEC == 0.
-template <typename T>
-static int pick_vec(int D, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
-  int vec = 16 / (int)sizeof(T);  // 16-byte accesses
-  auto ok = [&](int v) {
-    if (D % v) return false;
-    for (int64_t ld : lds)
-      if (ld % v) return false;
-    for (const void* p : ptrs)
-      if (p && (reinterpret_cast<uintptr_t>(p) % (v * sizeof(T)))) return false;
-    return true;
-  };
-  while (vec > 1 && !ok(vec)) vec >>= 1;
-  return vec;
-}
-
-// smallest power-of-two chunk count covering D, or 0 if the row does not fit in registers
-static int pick_chunks(int D, int vec) {
-  for (int ch = 1; ch <= kMaxChunksLimit; ch *= 2)
-    if (D <= 64 * vec * ch) return ch;
-  return 0;
-}
-
-#define ALL_VEC_CH(M) \
-  M(1, 1) M(1, 2) M(1, 4) M(1, 8) M(2, 1) M(2, 2) M(2, 4) M(2, 8) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 1) M(8, 2) M(8, 4) M(8, 8)
-
 template <typename T>
 static int layernorm_launch(const void* x, int64_t ldx, const void* gamma, const void* beta, const void* residual,
                             int64_t ldr, void* y, int64_t ldy, int n_rows, int D, float eps, hipStream_t st) {
   const int vec = pick_vec<T>(D, {ldx, ldy, residual ? ldr : (int64_t)0}, {x, y, gamma, beta, residual});
   const int ch = pick_chunks(D, vec);
-  ANEMOI_REQUIRE(ch > 0, "layernorm_fwd: D=%d too large for the register-resident row (max %d at vector width %d)", D, 64 * vec * kMaxChunksLimit, vec);
+  ANEMOI_REQUIRE(ch > 0, "layernorm_fwd: D=%d too large for the register-resident row (max %d at vector width %d)", D, 64 * vec * kMaxChunks, vec);
   static const int quarter = [] { const char* e = getenv("ANEMOI_LN_QUARTER"); return e ? atoi(e) : 1; }();
-  if (quarter && sizeof(T) == 2 && vec == 8 && D == 512 && n_rows > 0) {  // the 512-channel rows of the hot path (8 rows per wave,
-    // 8 lanes per row, measured slower: +55 us per forward)
+  if (quarter && sizeof(T) == 2 && vec == 8 && D == 512 && n_rows > 0) {
+    // The 512-channel rows of the hot path: the quarter-wave kernel, 4 rows per wave and 16 lanes per row.  (The variant with
+    // 8 rows per wave and 8 lanes per row was measured slower, +55 us per forward, and is not built.)
     const int rows_per_block = 4 * kRowWaves;
     hipLaunchKernelGGL((layernorm_fwd_q_kernel<T, 4>), dim3((n_rows + rows_per_block - 1) / rows_per_block), dim3(64 * kRowWaves), 0, st,
                        (const T*)x, ldx, (const T*)gamma, (const T*)beta, (const T*)residual, ldr, (T*)y, ldy, n_rows, eps);
     return check_launch("layernorm_fwd_q_kernel");
   }
   const dim3 grid((n_rows + kRowWaves - 1) / kRowWaves), block(64 * kRowWaves);
-#define LN_CASE(V, C)                                                                                                   \
-  case V * 16 + C:                                                                                                      \
-    hipLaunchKernelGGL((layernorm_fwd_kernel<T, V, C>), grid, block, 0, st, (const T*)x, ldx, (const T*)gamma,          \
-                       (const T*)beta, (const T*)residual, ldr, (T*)y, ldy, n_rows, D, eps);                            \
-    break;
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(LN_CASE)
-    default: set_error("layernorm_fwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef LN_CASE
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto C) {
+    hipLaunchKernelGGL((layernorm_fwd_kernel<T, V(), C()>), grid, block, 0, st, (const T*)x, ldx, (const T*)gamma, (const T*)beta,
+                       (const T*)residual, ldr, (T*)y, ldy, n_rows, D, eps);
+  });
+  ANEMOI_REQUIRE(hit, "layernorm_fwd: bad vector width");
   return check_launch("layernorm_fwd_kernel");
 }
 
@@ -707,16 +655,11 @@ static int cond_layernorm_launch(const void* x, int64_t ldx, const void* scale, 
   const int ch = pick_chunks(D, vec);
   ANEMOI_REQUIRE(ch > 0, "cond_layernorm_fwd: D=%d too large for the register-resident row", D);
   const dim3 grid((n_rows + kRowWaves - 1) / kRowWaves), block(64 * kRowWaves);
-#define CLN_CASE(V, C)                                                                                                      \
-  case V * 16 + C:                                                                                                         \
-    hipLaunchKernelGGL((cond_layernorm_fwd_kernel<T, V, C>), grid, block, 0, st, (const T*)x, ldx, (const T*)scale, lds,   \
-                       (const T*)shift, ldsh, (T*)y, ldy, n_rows, D, eps);                                                 \
-    break;
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(CLN_CASE)
-    default: set_error("cond_layernorm_fwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef CLN_CASE
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto C) {
+    hipLaunchKernelGGL((cond_layernorm_fwd_kernel<T, V(), C()>), grid, block, 0, st, (const T*)x, ldx, (const T*)scale, lds,
+                       (const T*)shift, ldsh, (T*)y, ldy, n_rows, D, eps);
+  });
+  ANEMOI_REQUIRE(hit, "cond_layernorm_fwd: bad vector width");
   return check_launch("cond_layernorm_fwd_kernel");
 }
 
@@ -775,15 +718,13 @@ static int cond_layernorm_proj_launch(const void* x, int64_t ldx, const void* co
   const int vec = pick_vec<T>(D, {ldx, ldy, residual ? ldr : (int64_t)0}, {x, y, residual, w, bias});
   const int ch = pick_chunks(D, vec);
   ANEMOI_REQUIRE(ch > 0, "cond_layernorm_proj_fwd: D=%d too large for the register-resident row", D);
-#define CLNP_CASE(V, CC)                                                                                                                      \
-  case V * 16 + CC:                                                                                                                           \
-    return cond_proj_launch_vc<T, V, CC>((const T*)x, ldx, (const T*)cond, ldc, (const T*)w, (const T*)bias, (const T*)residual, ldr, (T*)y, ldy, \
-                                         n_rows, D, C, eps, st);
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(CLNP_CASE)
-    default: set_error("cond_layernorm_proj_fwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef CLNP_CASE
+  int rc = ANEMOI_E_INVALID;
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto CC) {
+    rc = cond_proj_launch_vc<T, V(), CC()>((const T*)x, ldx, (const T*)cond, ldc, (const T*)w, (const T*)bias, (const T*)residual, ldr, (T*)y, ldy,
+                                           n_rows, D, C, eps, st);
+  });
+  ANEMOI_REQUIRE(hit, "cond_layernorm_proj_fwd: bad vector width");
+  return rc;
 }
 
 template <typename T>
@@ -792,7 +733,7 @@ static int edge_launch(const void* z, int64_t ldz, const void* e_old, int64_t ld
                        int D, hipStream_t st) {
   const int vec = pick_vec<T>(D, {ldz, lde, ldn, ldagg}, {z, e_old, e_new, agg, gamma, beta});
   const int ch = pick_chunks(D, vec);
-  ANEMOI_REQUIRE(ch > 0, "edge_ln_residual_segment_sum_fwd: D=%d too large (max %d)", D, 64 * vec * kMaxChunksLimit);
+  ANEMOI_REQUIRE(ch > 0, "edge_ln_residual_segment_sum_fwd: D=%d too large (max %d)", D, 64 * vec * kMaxChunks);
   const dim3 grid((n_dst + kRowWaves - 1) / kRowWaves), block(64 * kRowWaves);
   static const int quarter = env_int(getenv("ANEMOI_SEGSUM_QUARTER"), 2, 0, 3);  // rows per wave at a time: 1 -> four, 2 -> two, 3 -> one
   if constexpr (sizeof(T) == 2) {
@@ -809,16 +750,11 @@ static int edge_launch(const void* z, int64_t ldz, const void* e_old, int64_t ld
       return check_launch("edge_ln_res_segsum_kernel_mr");
     }
   }
-#define E_CASE(V, C)                                                                                                    \
-  case V * 16 + C:                                                                                                      \
-    hipLaunchKernelGGL((edge_ln_res_segsum_kernel<T, V, C>), grid, block, 0, st, (const T*)z, ldz, (const T*)e_old,     \
-                       lde, (const T*)gamma, (const T*)beta, eps, colptr, (T*)e_new, ldn, (T*)agg, ldagg, n_dst, D);    \
-    break;
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(E_CASE)
-    default: set_error("edge_ln_residual_segment_sum_fwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef E_CASE
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto C) {
+    hipLaunchKernelGGL((edge_ln_res_segsum_kernel<T, V(), C()>), grid, block, 0, st, (const T*)z, ldz, (const T*)e_old, lde, (const T*)gamma,
+                       (const T*)beta, eps, colptr, (T*)e_new, ldn, (T*)agg, ldagg, n_dst, D);
+  });
+  ANEMOI_REQUIRE(hit, "edge_ln_residual_segment_sum_fwd: bad vector width");
   return check_launch("edge_ln_res_segsum_kernel");
 }
 
@@ -827,15 +763,10 @@ static int gather_launch(const void* x, int64_t ldx, const int32_t* idx, void* o
                          hipStream_t st) {
   const int vec = pick_vec<T>(D, {ldx, ldo}, {x, out});
   const dim3 grid((n_out + kRowWaves - 1) / kRowWaves), block(64 * kRowWaves);
-#define G_CASE(V)                                                                                                       \
-  case V:                                                                                                               \
-    hipLaunchKernelGGL((gather_rows_kernel<T, V>), grid, block, 0, st, (const T*)x, ldx, idx, (T*)out, ldo, n_out, D);  \
-    break;
-  switch (vec) {
-    G_CASE(1) G_CASE(2) G_CASE(4) G_CASE(8)
-    default: set_error("gather_rows: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef G_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((gather_rows_kernel<T, V()>), grid, block, 0, st, (const T*)x, ldx, idx, (T*)out, ldo, n_out, D);
+  });
+  ANEMOI_REQUIRE(hit, "gather_rows: bad vector width");
   return check_launch("gather_rows_kernel");
 }
 
@@ -849,12 +780,10 @@ extern "C" int anemoi_layernorm_fwd(const void* x, int64_t ldx, const void* gamm
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D && ldy >= D && (!residual || ldr >= D), "layernorm_fwd: bad sizes n_rows=%d D=%d", n_rows, D);
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && y && gamma, "layernorm_fwd: null pointer");
-  switch (dtype) {
-    case ANEMOI_F32: return layernorm_launch<float>(x, ldx, gamma, beta, residual, ldr, y, ldy, n_rows, D, eps, as_stream(stream));
-    case ANEMOI_BF16: return layernorm_launch<bf16_t>(x, ldx, gamma, beta, residual, ldr, y, ldy, n_rows, D, eps, as_stream(stream));
-    case ANEMOI_F16: return layernorm_launch<f16_t>(x, ldx, gamma, beta, residual, ldr, y, ldy, n_rows, D, eps, as_stream(stream));
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return layernorm_launch<T>(x, ldx, gamma, beta, residual, ldr, y, ldy, n_rows, D, eps, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_edge_ln_residual_segment_sum_fwd(const void* z, int64_t ldz, const void* e_old, int64_t lde,
@@ -865,12 +794,10 @@ extern "C" int anemoi_edge_ln_residual_segment_sum_fwd(const void* z, int64_t ld
   ANEMOI_REQUIRE(n_dst >= 0 && D > 0 && ldz >= D && lde >= D && ldn >= D && ldagg >= D, "edge_ln_residual_segment_sum_fwd: bad sizes");
   if (n_dst == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(z && e_old && e_new && agg && colptr, "edge_ln_residual_segment_sum_fwd: null pointer");
-  switch (dtype) {
-    case ANEMOI_F32: return edge_launch<float>(z, ldz, e_old, lde, gamma, beta, eps, colptr, e_new, ldn, agg, ldagg, n_dst, D, as_stream(stream));
-    case ANEMOI_BF16: return edge_launch<bf16_t>(z, ldz, e_old, lde, gamma, beta, eps, colptr, e_new, ldn, agg, ldagg, n_dst, D, as_stream(stream));
-    case ANEMOI_F16: return edge_launch<f16_t>(z, ldz, e_old, lde, gamma, beta, eps, colptr, e_new, ldn, agg, ldagg, n_dst, D, as_stream(stream));
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return edge_launch<T>(z, ldz, e_old, lde, gamma, beta, eps, colptr, e_new, ldn, agg, ldagg, n_dst, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_gather_rows(const void* x, int64_t ldx, const int32_t* idx, void* out, int64_t ldo, int32_t n_out,
@@ -878,12 +805,10 @@ extern "C" int anemoi_gather_rows(const void* x, int64_t ldx, const int32_t* idx
   ANEMOI_REQUIRE(n_out >= 0 && D > 0 && ldx >= D && ldo >= D, "gather_rows: bad sizes");
   if (n_out == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && idx && out, "gather_rows: null pointer");
-  switch (dtype) {
-    case ANEMOI_F32: return gather_launch<float>(x, ldx, idx, out, ldo, n_out, D, as_stream(stream));
-    case ANEMOI_BF16: return gather_launch<bf16_t>(x, ldx, idx, out, ldo, n_out, D, as_stream(stream));
-    case ANEMOI_F16: return gather_launch<f16_t>(x, ldx, idx, out, ldo, n_out, D, as_stream(stream));
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return gather_launch<T>(x, ldx, idx, out, ldo, n_out, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_cond_layernorm_fwd(const void* x, int64_t ldx, const void* scale, int64_t lds, const void* shift, int64_t ldsh,
@@ -891,13 +816,10 @@ extern "C" int anemoi_cond_layernorm_fwd(const void* x, int64_t ldx, const void*
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D && ldy >= D && (lds == 0 || lds >= D) && (ldsh == 0 || ldsh >= D), "cond_layernorm_fwd: bad sizes");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && y && scale && shift, "cond_layernorm_fwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return cond_layernorm_launch<float>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
-    case ANEMOI_BF16: return cond_layernorm_launch<bf16_t>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
-    case ANEMOI_F16: return cond_layernorm_launch<f16_t>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return cond_layernorm_launch<T>(x, ldx, scale, lds, shift, ldsh, y, ldy, n_rows, D, eps, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_cond_layernorm_proj_fwd(const void* x, int64_t ldx, const void* cond, int64_t ldc, const void* w, const void* bias,
@@ -911,13 +833,10 @@ extern "C" int anemoi_cond_layernorm_proj_fwd(const void* x, int64_t ldx, const 
   }
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && cond && w && bias && y, "cond_layernorm_proj_fwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return cond_layernorm_proj_launch<float>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
-    case ANEMOI_BF16: return cond_layernorm_proj_launch<bf16_t>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
-    case ANEMOI_F16: return cond_layernorm_proj_launch<f16_t>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return cond_layernorm_proj_launch<T>(x, ldx, cond, ldc, w, bias, residual, ldr, y, ldy, n_rows, D, C, eps, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_bound_columns(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params,
@@ -927,13 +846,11 @@ extern "C" int anemoi_bound_columns(void* x, int64_t ldx, int32_t n_rows, int32_
   ANEMOI_REQUIRE(x && ops && params, "bound_columns: null pointer");
   const dim3 grid((n_rows + 255) / 256), block(256);
   hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: hipLaunchKernelGGL((bound_columns_kernel<float>), grid, block, 0, st, (float*)x, ldx, n_rows, ops, params, n_ops); break;
-    case ANEMOI_BF16: hipLaunchKernelGGL((bound_columns_kernel<bf16_t>), grid, block, 0, st, (bf16_t*)x, ldx, n_rows, ops, params, n_ops); break;
-    case ANEMOI_F16: hipLaunchKernelGGL((bound_columns_kernel<f16_t>), grid, block, 0, st, (f16_t*)x, ldx, n_rows, ops, params, n_ops); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-  return check_launch("bound_columns_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bound_columns_kernel<T>), grid, block, 0, st, (T*)x, ldx, n_rows, ops, params, n_ops);
+    return check_launch("bound_columns_kernel");
+  });
 }
 
 extern "C" int anemoi_assemble_output(const void* x_out, int64_t ldx, const void* x_skip, int64_t lds, const int32_t* col_map, void* out,
@@ -947,17 +864,14 @@ extern "C" int anemoi_assemble_output(const void* x_out, int64_t ldx, const void
   const int64_t n = (int64_t)n_rows * (n_cols / (q4 ? 4 : 1));
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipStream_t st = as_stream(stream);
-#define AO_LAUNCH(TT, QQ)                                                                                                              \
-  hipLaunchKernelGGL((assemble_output_kernel<TT, QQ>), grid, block, 0, st, (const TT*)x_out, ldx, (const TT*)x_skip, lds, col_map, (TT*)out, \
-                     ldo, n_rows, n_cols)
-  switch (dtype) {
-    case ANEMOI_F32: if (q4) AO_LAUNCH(float, 4); else AO_LAUNCH(float, 1); break;
-    case ANEMOI_BF16: if (q4) AO_LAUNCH(bf16_t, 4); else AO_LAUNCH(bf16_t, 1); break;
-    case ANEMOI_F16: if (q4) AO_LAUNCH(f16_t, 4); else AO_LAUNCH(f16_t, 1); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-#undef AO_LAUNCH
-  return check_launch("assemble_output_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_one_of<1, 4>(q4 ? 4 : 1, [&](auto Q) {
+      hipLaunchKernelGGL((assemble_output_kernel<T, Q()>), grid, block, 0, st, (const T*)x_out, ldx, (const T*)x_skip, lds, col_map, (T*)out,
+                         ldo, n_rows, n_cols);
+    });
+    return check_launch("assemble_output_kernel");
+  });
 }
 
 extern "C" int anemoi_assemble_input(const void* x, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V, const void* attrs, int64_t lda,
@@ -974,19 +888,18 @@ extern "C" int anemoi_assemble_input(const void* x, int64_t ld_t, int64_t ldx, i
   const int64_t n = (int64_t)n_rows * (W / q);
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipStream_t st = as_stream(stream);
-#define AI_LAUNCH(TT, QQ)                                                                                                        \
-  hipLaunchKernelGGL((assemble_input_kernel<TT, QQ>), grid, block, 0, st, (const TT*)x, ld_t, ldx, T_steps, V, (const TT*)attrs, lda, A, \
-                     (TT*)out, ldo, W, n_rows)
-  switch (dtype) {
-    case ANEMOI_F32: if (q4) AI_LAUNCH(float, 4); else AI_LAUNCH(float, 1); break;
-    case ANEMOI_BF16: if (q4) AI_LAUNCH(bf16_t, 4); else AI_LAUNCH(bf16_t, 1); break;
-    case ANEMOI_F16: if (q4) AI_LAUNCH(f16_t, 4); else AI_LAUNCH(f16_t, 1); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-#undef AI_LAUNCH
-  return check_launch("assemble_input_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    dispatch_one_of<1, 4>(q, [&](auto Q) {
+      hipLaunchKernelGGL((assemble_input_kernel<T, Q()>), grid, block, 0, st, (const T*)x, ld_t, ldx, T_steps, V, (const T*)attrs, lda, A,
+                         (T*)out, ldo, W, n_rows);
+    });
+    return check_launch("assemble_input_kernel");
+  });
 }
 
+// The two entry points below take TWO dtypes and build exactly the pairs a caller can ask for - the model dtype with itself or
+// with fp32 data - so the second type is chosen inside one dispatch_dtype instead of by nesting two.
 extern "C" int anemoi_assemble_input_norm(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
                                           const float* col_mul, const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out,
                                           int64_t ldo, int32_t W, int32_t n_rows, anemoi_dtype_t dtype, void* stream) {
@@ -997,33 +910,32 @@ extern "C" int anemoi_assemble_input_norm(const void* x, anemoi_dtype_t x_dtype,
   ANEMOI_REQUIRE(x && out && (A == 0 || attrs), "assemble_input_norm: null pointer");
   ANEMOI_REQUIRE(x_dtype == dtype || x_dtype == ANEMOI_F32, "assemble_input_norm: the input is in the model dtype or fp32");
   hipStream_t st = as_stream(stream);
-  if (dtype != ANEMOI_F32 && W % 8 == 0 && ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-    const int64_t n8 = (int64_t)n_rows * (W / 8);
-    const dim3 grid8((unsigned)((n8 + 255) / 256)), block8(256);
-#define AIN8_LAUNCH(TI, TO)                                                                                                                    \
-  hipLaunchKernelGGL((assemble_input_norm_vec8_kernel<TI, TO>), grid8, block8, 0, st, (const TI*)x, ld_t, ldx, T_steps, V, col_mul, col_add,  \
-                     (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows)
-    if (dtype == ANEMOI_BF16) {
-      if (x_dtype == ANEMOI_F32) AIN8_LAUNCH(float, bf16_t); else AIN8_LAUNCH(bf16_t, bf16_t);
-    } else {
-      if (x_dtype == ANEMOI_F32) AIN8_LAUNCH(float, f16_t); else AIN8_LAUNCH(f16_t, f16_t);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using TO = typename decltype(t)::type;
+    const bool wide_in = x_dtype == ANEMOI_F32;  // TI = float, else TI = TO
+    if constexpr (sizeof(TO) == 2) {
+      if (W % 8 == 0 && ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        const int64_t n8 = (int64_t)n_rows * (W / 8);
+        const dim3 grid8((unsigned)((n8 + 255) / 256)), block8(256);
+        if (wide_in)
+          hipLaunchKernelGGL((assemble_input_norm_vec8_kernel<float, TO>), grid8, block8, 0, st, (const float*)x, ld_t, ldx, T_steps, V, col_mul,
+                             col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        else
+          hipLaunchKernelGGL((assemble_input_norm_vec8_kernel<TO, TO>), grid8, block8, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, col_mul,
+                             col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        return check_launch("assemble_input_norm_vec8_kernel");
+      }
     }
-#undef AIN8_LAUNCH
-    return check_launch("assemble_input_norm_vec8_kernel");
-  }
-  const int64_t n = (int64_t)n_rows * W;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define AIN_LAUNCH(TI, TO)                                                                                                             \
-  hipLaunchKernelGGL((assemble_input_norm_kernel<TI, TO>), grid, block, 0, st, (const TI*)x, ld_t, ldx, T_steps, V, col_mul, col_add,  \
-                     (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows)
-  switch (dtype) {
-    case ANEMOI_F32: AIN_LAUNCH(float, float); break;
-    case ANEMOI_BF16: if (x_dtype == ANEMOI_F32) AIN_LAUNCH(float, bf16_t); else AIN_LAUNCH(bf16_t, bf16_t); break;
-    case ANEMOI_F16: if (x_dtype == ANEMOI_F32) AIN_LAUNCH(float, f16_t); else AIN_LAUNCH(f16_t, f16_t); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-#undef AIN_LAUNCH
-  return check_launch("assemble_input_norm_kernel");
+    const int64_t n = (int64_t)n_rows * W;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (wide_in)
+      hipLaunchKernelGGL((assemble_input_norm_kernel<float, TO>), grid, block, 0, st, (const float*)x, ld_t, ldx, T_steps, V, col_mul, col_add,
+                         (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    else
+      hipLaunchKernelGGL((assemble_input_norm_kernel<TO, TO>), grid, block, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, col_mul, col_add,
+                         (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    return check_launch("assemble_input_norm_kernel");
+  });
 }
 
 extern "C" int anemoi_assemble_output_norm(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
@@ -1037,17 +949,16 @@ extern "C" int anemoi_assemble_output_norm(const void* x_out, int64_t ldx, anemo
   const int64_t n = (int64_t)n_rows * n_cols;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipStream_t st = as_stream(stream);
-#define AON_LAUNCH(TM, TS)                                                                                                              \
-  hipLaunchKernelGGL((assemble_output_norm_kernel<TM, TS>), grid, block, 0, st, (const TM*)x_out, ldx, (const TS*)x_skip, lds, col_map, \
-                     col_mul, col_add, (TS*)out, ldo, n_rows, n_cols)
-  switch (model_dtype) {
-    case ANEMOI_F32: AON_LAUNCH(float, float); break;
-    case ANEMOI_BF16: if (dtype == ANEMOI_F32) AON_LAUNCH(bf16_t, float); else AON_LAUNCH(bf16_t, bf16_t); break;
-    case ANEMOI_F16: if (dtype == ANEMOI_F32) AON_LAUNCH(f16_t, float); else AON_LAUNCH(f16_t, f16_t); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-#undef AON_LAUNCH
-  return check_launch("assemble_output_norm_kernel");
+  return dispatch_dtype(model_dtype, [&](auto t) {
+    using TM = typename decltype(t)::type;
+    if (dtype == ANEMOI_F32)  // TS = float, else TS = TM
+      hipLaunchKernelGGL((assemble_output_norm_kernel<TM, float>), grid, block, 0, st, (const TM*)x_out, ldx, (const float*)x_skip, lds, col_map,
+                         col_mul, col_add, (float*)out, ldo, n_rows, n_cols);
+    else
+      hipLaunchKernelGGL((assemble_output_norm_kernel<TM, TM>), grid, block, 0, st, (const TM*)x_out, ldx, (const TM*)x_skip, lds, col_map,
+                         col_mul, col_add, (TM*)out, ldo, n_rows, n_cols);
+    return check_launch("assemble_output_norm_kernel");
+  });
 }
 
 extern "C" int anemoi_affine_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const float* col_mul, const float* col_add,
@@ -1058,11 +969,9 @@ extern "C" int anemoi_affine_columns(const void* x, int64_t ldx, void* y, int64_
   const int64_t n = (int64_t)n_rows * V;
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: hipLaunchKernelGGL((affine_columns_kernel<float>), grid, block, 0, st, (const float*)x, ldx, (float*)y, ldy, col_mul, col_add, inverse, n_rows, V); break;
-    case ANEMOI_BF16: hipLaunchKernelGGL((affine_columns_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, ldx, (bf16_t*)y, ldy, col_mul, col_add, inverse, n_rows, V); break;
-    case ANEMOI_F16: hipLaunchKernelGGL((affine_columns_kernel<f16_t>), grid, block, 0, st, (const f16_t*)x, ldx, (f16_t*)y, ldy, col_mul, col_add, inverse, n_rows, V); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-  return check_launch("affine_columns_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((affine_columns_kernel<T>), grid, block, 0, st, (const T*)x, ldx, (T*)y, ldy, col_mul, col_add, inverse, n_rows, V);
+    return check_launch("affine_columns_kernel");
+  });
 }

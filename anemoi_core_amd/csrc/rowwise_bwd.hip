@@ -7,7 +7,10 @@
 // Column sums are deterministic: a persistent grid of kPartialBlocks x kBwdWaves waves walks the rows, each wave keeps its
 // partial column sums in registers, the waves of a block add theirs in LDS in wave order and the block writes one row of an
 // fp32 workspace [kPartialBlocks][2][D]; a second tiny kernel adds the partials in a fixed order (no atomics).
-#include "common.h"
+//
+// rowwise_common.h holds what this file shares with rowwise.hip: load_row, the (VEC, CH) pick rule and the dispatchers from the
+// picked values to template arguments; the dtype switch is dispatch_dtype (common.h).
+#include "rowwise_common.h"
 
 namespace anemoi {
 namespace {
@@ -15,21 +18,6 @@ namespace {
 constexpr int kWaves = 4;             // waves per block
 constexpr int kBwdWaves = 8;          // waves per block of the persistent row-walking kernels (16 waves per CU hide the
 constexpr int kPartialBlocks = 512;   // four dependent wave reductions of a LayerNorm-backward row): two blocks per CU
-constexpr int kMaxChunks = 8;
-
-template <typename T, int VEC, int CH>
-__device__ __forceinline__ void load_row(const T* __restrict__ p, int D, int lane, float (&r)[CH][VEC]) {
-#pragma unroll
-  for (int t = 0; t < CH; ++t) {
-    const int c = (t * 64 + lane) * VEC;
-    if (c < D) {
-      load_vec<T, VEC>(p + c, r[t]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) r[t][j] = 0.f;
-    }
-  }
-}
 
 // MODE 0: LayerNorm backward (dx + partial dgamma/dbeta).  MODE 1: column sums of x only (bias gradient).
 template <typename T, int VEC, int CH, int MODE>
@@ -383,30 +371,6 @@ __global__ __launch_bounds__(256) void glu_kernel(const T* __restrict__ gv, int6
   }
 }
 
-template <typename T>
-int pick_vec(int D, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
-  int vec = 16 / (int)sizeof(T);
-  auto ok = [&](int v) {
-    if (D % v) return false;
-    for (int64_t ld : lds)
-      if (ld % v) return false;
-    for (const void* p : ptrs)
-      if (p && (reinterpret_cast<uintptr_t>(p) % (v * sizeof(T)))) return false;
-    return true;
-  };
-  while (vec > 1 && !ok(vec)) vec >>= 1;
-  return vec;
-}
-
-int pick_chunks(int D, int vec) {
-  for (int ch = 1; ch <= kMaxChunks; ch *= 2)
-    if (D <= 64 * vec * ch) return ch;
-  return 0;
-}
-
-#define ALL_VEC_CH(M) \
-  M(1, 1) M(1, 2) M(1, 4) M(1, 8) M(2, 1) M(2, 2) M(2, 4) M(2, 8) M(4, 1) M(4, 2) M(4, 4) M(4, 8) M(8, 1) M(8, 2) M(8, 4) M(8, 8)
-
 template <typename T, int MODE>
 int launch_rowwise_bwd(const void* x, int64_t ldx, const void* gamma, const void* dy, int64_t lddy, void* dx, int64_t lddx,
                        float* out0, float* out1, float* ws, int n_rows, int D, float eps, hipStream_t st) {
@@ -421,16 +385,11 @@ int launch_rowwise_bwd(const void* x, int64_t ldx, const void* gamma, const void
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((2 * D + 15) / 16), dim3(1024), 0, st, ws, 0, D, out0, out1);
     return check_launch("reduce_partials_kernel");
   }
-#define RB_CASE(V, C)                                                                                                          \
-  case V * 16 + C:                                                                                                             \
-    hipLaunchKernelGGL((rowwise_bwd_kernel<T, V, C, MODE>), dim3(blocks), dim3(64 * kBwdWaves), 2 * D * sizeof(float), st, (const T*)x, ldx, \
-                       (const T*)gamma, (const T*)dy, lddy, (T*)dx, lddx, want_sums ? ws : nullptr, n_rows, D, eps);           \
-    break;
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(RB_CASE)
-    default: set_error("rowwise backward: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef RB_CASE
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto C) {
+    hipLaunchKernelGGL((rowwise_bwd_kernel<T, V(), C(), MODE>), dim3(blocks), dim3(64 * kBwdWaves), 2 * D * sizeof(float), st, (const T*)x, ldx,
+                       (const T*)gamma, (const T*)dy, lddy, (T*)dx, lddx, want_sums ? ws : nullptr, n_rows, D, eps);
+  });
+  ANEMOI_REQUIRE(hit, "rowwise backward: bad vector width");
   int rc = check_launch("rowwise_bwd_kernel");
   if (rc != ANEMOI_OK || !want_sums) return rc;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((2 * D + 15) / 16), dim3(1024), 0, st, ws, blocks, D, out0, out1);
@@ -442,15 +401,10 @@ int launch_gelu_bwd(const void* pre, int64_t ldp, const void* dy, int64_t lddy, 
   const int vec = pick_vec<T>(D, {ldp, lddy, lddp}, {pre, dy, dpre});
   const int64_t n = (int64_t)n_rows * (D / vec);
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define GB_CASE(V)                                                                                                          \
-  case V:                                                                                                                   \
-    hipLaunchKernelGGL((gelu_bwd_kernel<T, V>), grid, block, 0, st, (const T*)pre, ldp, (const T*)dy, lddy, (T*)dpre, lddp, n_rows, D); \
-    break;
-  switch (vec) {
-    GB_CASE(1) GB_CASE(2) GB_CASE(4) GB_CASE(8)
-    default: set_error("gelu_bwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef GB_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((gelu_bwd_kernel<T, V()>), grid, block, 0, st, (const T*)pre, ldp, (const T*)dy, lddy, (T*)dpre, lddp, n_rows, D);
+  });
+  ANEMOI_REQUIRE(hit, "gelu_bwd: bad vector width");
   return check_launch("gelu_bwd_kernel");
 }
 
@@ -459,15 +413,10 @@ int launch_gelu_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int n_rows
   const int vec = pick_vec<T>(D, {ldx, ldy}, {x, y});
   const int64_t n = (int64_t)n_rows * (D / vec);
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define GF_CASE(V)                                                                                            \
-  case V:                                                                                                     \
-    hipLaunchKernelGGL((gelu_fwd_kernel<T, V>), grid, block, 0, st, (const T*)x, ldx, (T*)y, ldy, n_rows, D); \
-    break;
-  switch (vec) {
-    GF_CASE(1) GF_CASE(2) GF_CASE(4) GF_CASE(8)
-    default: set_error("gelu_fwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef GF_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((gelu_fwd_kernel<T, V()>), grid, block, 0, st, (const T*)x, ldx, (T*)y, ldy, n_rows, D);
+  });
+  ANEMOI_REQUIRE(hit, "gelu_fwd: bad vector width");
   return check_launch("gelu_fwd_kernel");
 }
 
@@ -475,15 +424,10 @@ template <typename T>
 int launch_segment_sum(const void* x, int64_t ldx, const int32_t* ptr, const int32_t* ids, void* out, int64_t ldo, int n_out, int D, hipStream_t st) {
   const int vec = pick_vec<T>(D, {ldx, ldo}, {x, out});
   const dim3 grid((n_out + kWaves - 1) / kWaves), block(64 * kWaves);
-#define SS_CASE(V)                                                                                                          \
-  case V:                                                                                                                   \
-    hipLaunchKernelGGL((segment_sum_rows_kernel<T, V>), grid, block, 0, st, (const T*)x, ldx, ptr, ids, (T*)out, ldo, n_out, D); \
-    break;
-  switch (vec) {
-    SS_CASE(1) SS_CASE(2) SS_CASE(4) SS_CASE(8)
-    default: set_error("segment_sum_rows: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef SS_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((segment_sum_rows_kernel<T, V()>), grid, block, 0, st, (const T*)x, ldx, ptr, ids, (T*)out, ldo, n_out, D);
+  });
+  ANEMOI_REQUIRE(hit, "segment_sum_rows: bad vector width");
   return check_launch("segment_sum_rows_kernel");
 }
 
@@ -492,15 +436,10 @@ int launch_gather_add(const void* a, int64_t lda, const void* b, int64_t ldb, co
                       hipStream_t st) {
   const int vec = pick_vec<T>(D, {lda, ldb, ldo}, {a, b, out});
   const dim3 grid((n_out + kWaves - 1) / kWaves), block(64 * kWaves);
-#define GA_CASE(V)                                                                                                          \
-  case V:                                                                                                                   \
-    hipLaunchKernelGGL((gather_add_rows_kernel<T, V>), grid, block, 0, st, (const T*)a, lda, (const T*)b, ldb, idx, (T*)out, ldo, n_out, D); \
-    break;
-  switch (vec) {
-    GA_CASE(1) GA_CASE(2) GA_CASE(4) GA_CASE(8)
-    default: set_error("gather_add_rows: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef GA_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((gather_add_rows_kernel<T, V()>), grid, block, 0, st, (const T*)a, lda, (const T*)b, ldb, idx, (T*)out, ldo, n_out, D);
+  });
+  ANEMOI_REQUIRE(hit, "gather_add_rows: bad vector width");
   return check_launch("gather_add_rows_kernel");
 }
 
@@ -509,15 +448,10 @@ int launch_glu(const void* gv, int64_t ldgv, const void* d_out, int64_t lddo, vo
   const int vec = BWD ? pick_vec<T>(D, {ldgv, lddo, ldo}, {gv, d_out, out}) : pick_vec<T>(D, {ldgv, ldo}, {gv, out});
   const int64_t n = (int64_t)n_rows * (D / vec);
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-#define GLU_CASE(V)                                                                                                          \
-  case V:                                                                                                                    \
-    hipLaunchKernelGGL((glu_kernel<T, V, BWD>), grid, block, 0, st, (const T*)gv, ldgv, (const T*)d_out, lddo, (T*)out, ldo, n_rows, D, kind); \
-    break;
-  switch (vec) {
-    GLU_CASE(1) GLU_CASE(2) GLU_CASE(4) GLU_CASE(8)
-    default: set_error("glu: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef GLU_CASE
+  const bool hit = dispatch_vec(vec, [&](auto V) {
+    hipLaunchKernelGGL((glu_kernel<T, V(), BWD>), grid, block, 0, st, (const T*)gv, ldgv, (const T*)d_out, lddo, (T*)out, ldo, n_rows, D, kind);
+  });
+  ANEMOI_REQUIRE(hit, "glu: bad vector width");
   return check_launch("glu_kernel");
 }
 
@@ -528,16 +462,11 @@ int launch_cond_ln_bwd(const void* x, int64_t ldx, const void* scale, int64_t ld
   const int ch = pick_chunks(D, vec);
   ANEMOI_REQUIRE(ch > 0, "cond_layernorm_bwd: D=%d too large for the register-resident row", D);
   const dim3 grid((n_rows + kWaves - 1) / kWaves), block(64 * kWaves);
-#define CB_CASE(V, C)                                                                                                        \
-  case V * 16 + C:                                                                                                           \
-    hipLaunchKernelGGL((cond_layernorm_bwd_kernel<T, V, C>), grid, block, 0, st, (const T*)x, ldx, (const T*)scale, lds,     \
-                       (const T*)dy, lddy, (T*)dx, lddx, (T*)dscale, ldds, n_rows, D, eps);                                  \
-    break;
-  switch (vec * 16 + ch) {
-    ALL_VEC_CH(CB_CASE)
-    default: set_error("cond_layernorm_bwd: bad vector width"); return ANEMOI_E_INVALID;
-  }
-#undef CB_CASE
+  const bool hit = dispatch_vec_chunks(vec, ch, [&](auto V, auto C) {
+    hipLaunchKernelGGL((cond_layernorm_bwd_kernel<T, V(), C()>), grid, block, 0, st, (const T*)x, ldx, (const T*)scale, lds, (const T*)dy, lddy,
+                       (T*)dx, lddx, (T*)dscale, ldds, n_rows, D, eps);
+  });
+  ANEMOI_REQUIRE(hit, "cond_layernorm_bwd: bad vector width");
   return check_launch("cond_layernorm_bwd_kernel");
 }
 
@@ -555,26 +484,20 @@ extern "C" int anemoi_layernorm_bwd(const void* x, int64_t ldx, const void* gamm
   // no rows: nothing is read or written but the sums (zeros), and a zero-row tensor's data pointer is null
   ANEMOI_REQUIRE(n_rows == 0 || (x && gamma && d_y && d_x), "layernorm_bwd: null pointer");
   ANEMOI_REQUIRE(workspace || (!d_gamma && !d_beta), "layernorm_bwd: d_gamma/d_beta need the workspace (anemoi_reduce_workspace_bytes)");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_rowwise_bwd<float, 0>(x, ldx, gamma, d_y, lddy, d_x, lddx, d_gamma, d_beta, workspace, n_rows, D, eps, st);
-    case ANEMOI_BF16: return launch_rowwise_bwd<bf16_t, 0>(x, ldx, gamma, d_y, lddy, d_x, lddx, d_gamma, d_beta, workspace, n_rows, D, eps, st);
-    case ANEMOI_F16: return launch_rowwise_bwd<f16_t, 0>(x, ldx, gamma, d_y, lddy, d_x, lddx, d_gamma, d_beta, workspace, n_rows, D, eps, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rowwise_bwd<T, 0>(x, ldx, gamma, d_y, lddy, d_x, lddx, d_gamma, d_beta, workspace, n_rows, D, eps, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_colsum(const void* x, int64_t ldx, float* out, float* workspace, int32_t n_rows, int32_t D,
                              anemoi_dtype_t dtype, void* stream) {
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D, "colsum: bad sizes n_rows=%d D=%d", n_rows, D);
   ANEMOI_REQUIRE((x || n_rows == 0) && out && workspace, "colsum: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_rowwise_bwd<float, 1>(x, ldx, nullptr, nullptr, 0, nullptr, 0, nullptr, out, workspace, n_rows, D, 0.f, st);
-    case ANEMOI_BF16: return launch_rowwise_bwd<bf16_t, 1>(x, ldx, nullptr, nullptr, 0, nullptr, 0, nullptr, out, workspace, n_rows, D, 0.f, st);
-    case ANEMOI_F16: return launch_rowwise_bwd<f16_t, 1>(x, ldx, nullptr, nullptr, 0, nullptr, 0, nullptr, out, workspace, n_rows, D, 0.f, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_rowwise_bwd<T, 1>(x, ldx, nullptr, nullptr, 0, nullptr, 0, nullptr, out, workspace, n_rows, D, 0.f, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_gelu_bwd(const void* pre, int64_t ldp, const void* d_y, int64_t lddy, void* d_pre, int64_t lddp,
@@ -582,26 +505,20 @@ extern "C" int anemoi_gelu_bwd(const void* pre, int64_t ldp, const void* d_y, in
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldp >= D && lddy >= D && lddp >= D, "gelu_bwd: bad sizes");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(pre && d_y && d_pre, "gelu_bwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_gelu_bwd<float>(pre, ldp, d_y, lddy, d_pre, lddp, n_rows, D, st);
-    case ANEMOI_BF16: return launch_gelu_bwd<bf16_t>(pre, ldp, d_y, lddy, d_pre, lddp, n_rows, D, st);
-    case ANEMOI_F16: return launch_gelu_bwd<f16_t>(pre, ldp, d_y, lddy, d_pre, lddp, n_rows, D, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gelu_bwd<T>(pre, ldp, d_y, lddy, d_pre, lddp, n_rows, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_gelu_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t n_rows, int32_t D, anemoi_dtype_t dtype, void* stream) {
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D && ldy >= D, "gelu_fwd: bad sizes");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && y, "gelu_fwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_gelu_fwd<float>(x, ldx, y, ldy, n_rows, D, st);
-    case ANEMOI_BF16: return launch_gelu_fwd<bf16_t>(x, ldx, y, ldy, n_rows, D, st);
-    case ANEMOI_F16: return launch_gelu_fwd<f16_t>(x, ldx, y, ldy, n_rows, D, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gelu_fwd<T>(x, ldx, y, ldy, n_rows, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_segment_sum_rows(const void* x, int64_t ldx, const int32_t* ptr, const int32_t* ids, void* out, int64_t ldo,
@@ -609,13 +526,10 @@ extern "C" int anemoi_segment_sum_rows(const void* x, int64_t ldx, const int32_t
   ANEMOI_REQUIRE(n_out >= 0 && D > 0 && ldx >= D && ldo >= D, "segment_sum_rows: bad sizes");
   if (n_out == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && ptr && out, "segment_sum_rows: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_segment_sum<float>(x, ldx, ptr, ids, out, ldo, n_out, D, st);
-    case ANEMOI_BF16: return launch_segment_sum<bf16_t>(x, ldx, ptr, ids, out, ldo, n_out, D, st);
-    case ANEMOI_F16: return launch_segment_sum<f16_t>(x, ldx, ptr, ids, out, ldo, n_out, D, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_segment_sum<T>(x, ldx, ptr, ids, out, ldo, n_out, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_gather_add_rows(const void* a, int64_t lda, const void* b, int64_t ldb, const int32_t* idx, void* out, int64_t ldo,
@@ -623,13 +537,10 @@ extern "C" int anemoi_gather_add_rows(const void* a, int64_t lda, const void* b,
   ANEMOI_REQUIRE(n_out >= 0 && D > 0 && lda >= D && ldb >= D && ldo >= D, "gather_add_rows: bad sizes");
   if (n_out == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(a && b && idx && out, "gather_add_rows: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_gather_add<float>(a, lda, b, ldb, idx, out, ldo, n_out, D, st);
-    case ANEMOI_BF16: return launch_gather_add<bf16_t>(a, lda, b, ldb, idx, out, ldo, n_out, D, st);
-    case ANEMOI_F16: return launch_gather_add<f16_t>(a, lda, b, ldb, idx, out, ldo, n_out, D, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_gather_add<T>(a, lda, b, ldb, idx, out, ldo, n_out, D, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_transpose_pad(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols, int32_t n_pad,
@@ -639,13 +550,11 @@ extern "C" int anemoi_transpose_pad(const void* x, int64_t ldx, void* out, int64
   ANEMOI_REQUIRE(x && out, "transpose_pad: null pointer");
   const dim3 grid((n_pad + 63) / 64, (n_cols + 63) / 64), block(256);
   hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: hipLaunchKernelGGL((transpose_pad_kernel<float>), grid, block, 0, st, (const float*)x, ldx, (float*)out, ldo, n_rows, n_cols, n_pad); break;
-    case ANEMOI_BF16: hipLaunchKernelGGL((transpose_pad_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, ldx, (bf16_t*)out, ldo, n_rows, n_cols, n_pad); break;
-    case ANEMOI_F16: hipLaunchKernelGGL((transpose_pad_kernel<f16_t>), grid, block, 0, st, (const f16_t*)x, ldx, (f16_t*)out, ldo, n_rows, n_cols, n_pad); break;
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
-  return check_launch("transpose_pad_kernel");
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((transpose_pad_kernel<T>), grid, block, 0, st, (const T*)x, ldx, (T*)out, ldo, n_rows, n_cols, n_pad);
+    return check_launch("transpose_pad_kernel");
+  });
 }
 
 extern "C" int anemoi_glu_fwd(const void* gate_value, int64_t ldgv, void* out, int64_t ldo, int32_t n_rows, int32_t D, int32_t kind,
@@ -653,13 +562,10 @@ extern "C" int anemoi_glu_fwd(const void* gate_value, int64_t ldgv, void* out, i
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldgv >= 2 * D && ldo >= D && kind >= 0 && kind <= 3, "glu_fwd: bad sizes / kind");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(gate_value && out, "glu_fwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_glu<float, false>(gate_value, ldgv, nullptr, 0, out, ldo, n_rows, D, kind, st);
-    case ANEMOI_BF16: return launch_glu<bf16_t, false>(gate_value, ldgv, nullptr, 0, out, ldo, n_rows, D, kind, st);
-    case ANEMOI_F16: return launch_glu<f16_t, false>(gate_value, ldgv, nullptr, 0, out, ldo, n_rows, D, kind, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_glu<T, false>(gate_value, ldgv, nullptr, 0, out, ldo, n_rows, D, kind, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_glu_bwd(const void* gate_value, int64_t ldgv, const void* d_out, int64_t lddo, void* d_gate_value, int64_t lddgv,
@@ -667,13 +573,10 @@ extern "C" int anemoi_glu_bwd(const void* gate_value, int64_t ldgv, const void* 
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldgv >= 2 * D && lddo >= D && lddgv >= 2 * D && kind >= 0 && kind <= 3, "glu_bwd: bad sizes / kind");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(gate_value && d_out && d_gate_value, "glu_bwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_glu<float, true>(gate_value, ldgv, d_out, lddo, d_gate_value, lddgv, n_rows, D, kind, st);
-    case ANEMOI_BF16: return launch_glu<bf16_t, true>(gate_value, ldgv, d_out, lddo, d_gate_value, lddgv, n_rows, D, kind, st);
-    case ANEMOI_F16: return launch_glu<f16_t, true>(gate_value, ldgv, d_out, lddo, d_gate_value, lddgv, n_rows, D, kind, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_glu<T, true>(gate_value, ldgv, d_out, lddo, d_gate_value, lddgv, n_rows, D, kind, as_stream(stream));
+  });
 }
 
 extern "C" int anemoi_cond_layernorm_bwd(const void* x, int64_t ldx, const void* scale, int64_t lds, const void* d_y, int64_t lddy,
@@ -682,11 +585,8 @@ extern "C" int anemoi_cond_layernorm_bwd(const void* x, int64_t ldx, const void*
   ANEMOI_REQUIRE(n_rows >= 0 && D > 0 && ldx >= D && lds >= D && lddy >= D && lddx >= D && ldds >= D, "cond_layernorm_bwd: bad sizes");
   if (n_rows == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(x && scale && d_y && d_x && d_scale, "cond_layernorm_bwd: null pointer");
-  hipStream_t st = as_stream(stream);
-  switch (dtype) {
-    case ANEMOI_F32: return launch_cond_ln_bwd<float>(x, ldx, scale, lds, d_y, lddy, d_x, lddx, d_scale, ldds, n_rows, D, eps, st);
-    case ANEMOI_BF16: return launch_cond_ln_bwd<bf16_t>(x, ldx, scale, lds, d_y, lddy, d_x, lddx, d_scale, ldds, n_rows, D, eps, st);
-    case ANEMOI_F16: return launch_cond_ln_bwd<f16_t>(x, ldx, scale, lds, d_y, lddy, d_x, lddx, d_scale, ldds, n_rows, D, eps, st);
-    default: set_error("unknown dtype"); return ANEMOI_E_INVALID;
-  }
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_cond_ln_bwd<T>(x, ldx, scale, lds, d_y, lddy, d_x, lddx, d_scale, ldds, n_rows, D, eps, as_stream(stream));
+  });
 }

@@ -347,6 +347,40 @@ def test_edge_ln_residual_segment_sum_ragged_512(ops, dtype, with_beta):
     assert_close(agg, want_agg, dtype, "agg")
 
 
+# The forward row kernels are built for every (VEC, CH) in {1, 2, 4, 8}^2; the widths of the tests above reach only some.  This
+# ladder reaches each pair once per dtype: D = V * (64 * C - 1) is a multiple of V and not of 2 V (64 C - 1 is odd), so pick_vec
+# (csrc/rowwise_common.h) returns V for contiguous, freshly allocated tensors, and 64 V C / 2 < D <= 64 V C, so pick_chunks returns C.
+# A wrong CH drops whole 64 * V-column chunks of every row.  (8, 1) is D = 504, not the quarter-wave kernels' D = 512.
+VEC_CHUNK_LADDER = [(dt, V, C) for dt in (torch.float32, torch.bfloat16, torch.float16) for V in (1, 2, 4, 8) for C in (1, 2, 4, 8)
+                    if V * torch.empty((), dtype=dt).element_size() <= 16]
+
+
+@pytest.mark.parametrize("dtype,V,C", VEC_CHUNK_LADDER, ids=[f"{str(dt).split('.')[1]}-v{V}c{C}" for dt, V, C in VEC_CHUNK_LADDER])
+def test_rowwise_forward_every_vec_chunk_instantiation(ops, dtype, V, C):
+    D = V * (64 * C - 1)
+    vec = 16 // torch.empty((), dtype=dtype).element_size()
+    while vec > 1 and D % vec:
+        vec //= 2
+    assert (vec, next(c for c in (1, 2, 4, 8) if D <= 64 * vec * c)) == (V, C)  # pick_vec / pick_chunks restated
+    gen = torch.Generator().manual_seed(16 * V + C)
+    N = 5  # two blocks of four rows, the second ragged
+    x = (2.0 * torch.randn(N, D, generator=gen) + 0.5).to(dtype)
+    g, b = (1 + 0.3 * torch.randn(D, generator=gen)).to(dtype), (0.2 * torch.randn(D, generator=gen)).to(dtype)
+    ln = F.layer_norm(x.float(), (D,), g.float(), b.float())
+    assert_close(ops.layer_norm(x.to(DEV), g.to(DEV), b.to(DEV)), ln, dtype, "layer_norm")
+    scale, shift = (0.3 * torch.randn(N, D, generator=gen)).to(dtype), (0.2 * torch.randn(N, D, generator=gen)).to(dtype)
+    assert_close(ops.cond_layer_norm(x.to(DEV), scale.to(DEV), shift.to(DEV)),
+                 F.layer_norm(x.float(), (D,)) * (scale.float() + 1) + shift.float(), dtype, "cond_layer_norm")
+    deg = torch.tensor([0, 1, 3, 2, 1])  # five destinations: two blocks as well, one empty segment
+    dst = torch.repeat_interleave(torch.arange(deg.numel()), deg)
+    m = int(deg.sum())
+    ei = torch.stack([torch.randint(0, 9, (m,), generator=gen), dst])
+    z, e_old = (2.0 * torch.randn(m, D, generator=gen) + 0.5).to(dtype), torch.randn(m, D, generator=gen).to(dtype)
+    e_new, agg = ops.edge_ln_residual_segment_sum(z.to(DEV), e_old.to(DEV), g.to(DEV), b.to(DEV), 1e-5, ops.build_csc(ei.to(DEV), (9, deg.numel())))
+    assert_close(e_new, F.layer_norm(z.float(), (D,), g.float(), b.float()) + e_old.float(), dtype, "e_new")
+    assert_close(agg, torch.zeros(deg.numel(), D).index_add_(0, dst, e_new.float().cpu()), dtype, "agg")  # sum of what was stored
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_gather_rows(ops, dtype):
     gen = torch.Generator().manual_seed(1)

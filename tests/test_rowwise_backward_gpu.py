@@ -68,7 +68,8 @@ def _slab(t, off, fill=3.0):
 
 
 def _path(D, dtype, off):
-    """'v<VEC>c<CH>': the rowwise_bwd_kernel instantiation that pick_vec / pick_chunks select for this slab (for the test ids)."""
+    """'v<VEC>c<CH>': the rowwise_bwd_kernel instantiation that pick_vec / pick_chunks (csrc/rowwise_common.h, the one copy both
+    row-wise sources use) select for this slab (for the test ids)."""
     vec = 16 // torch.empty((), dtype=dtype).element_size() if off != 1 else 1
     ld = D if off is None else D + SLAB_PAD
     while vec > 1 and (D % vec or ld % vec):
