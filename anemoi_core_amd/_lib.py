@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -84,6 +84,8 @@ SIGNATURES = {
     "anemoi_gt_chain_rows_per_tile": ([_i32], C.c_int),
     "anemoi_gt_chain2_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_rowchain_fwd": ([_p, C.c_int, _p], C.c_int),
+    "anemoi_gt_rowchain_panels_fwd": ([_p, C.c_int32, C.c_int32, C.c_int, _p], C.c_int),
+    "anemoi_gt_chain2_side_fwd": ([_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int, _p], C.c_int),
     "anemoi_gt_cluster_chain_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_cluster_chain_workspace_bytes": ([], _i64),
     "anemoi_gnn_edge_chain_fwd": ([_p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),

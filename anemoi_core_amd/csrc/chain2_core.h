@@ -154,12 +154,13 @@ struct Warm {
 // my XCD share the segment's 4096 lines out among themselves - ALL of them (10 242 rows = 214 panels of 48: 26 or 27 CUs per XCD; with a
 // fixed 1/32 share each, 16 % of every weight stayed cold: the O96 forward 2.81 instead of 2.55 ms, profiles/r05_chain2_touch_coverage.txt).
 // Two waves per share (`half`), up to 192 lines per wave = full coverage from 11 workgroups per XCD on; the bounds are computed once per kernel.
-template <bool PART>
-__device__ __forceinline__ void warm_init(Warm& w, int half, int lane) {
+// GIVEN: the workgroups that share the weights are the first n_wg of the grid (the rest of the launch does other work), not all of it.
+template <bool PART, bool GIVEN = false>
+__device__ __forceinline__ void warm_init(Warm& w, int half, int lane, int n_wg = 0) {
   w.v[0] = w.v[1] = w.v[2] = 0u;
   if constexpr (PART) {
     const int xcd = (int)blockIdx.x & 7;
-    const int n_cu = ((int)gridDim.x - xcd + 7) >> 3;
+    const int n_cu = ((GIVEN ? n_wg : (int)gridDim.x) - xcd + 7) >> 3;
     const int s = (int)blockIdx.x >> 3;
     const int lo = (s * 4096) / n_cu, hi = ((s + 1) * 4096) / n_cu;
     const int mid = lo + ((hi - lo + 1) >> 1);

@@ -41,7 +41,10 @@
 // the model dtype, d = W beta + b): the GEMM then needs no epilogue arithmetic at all - its accumulators START at d.  Likewise the
 // projection's start at b_p + x and the second Linear's at b_2 + x1, so x1 never goes to global memory.  The per-column vectors
 // (b_p | d1 | b_2 | dq, model dtype) sit in LDS for the whole launch.
-#include "chain2_core.h"
+#include <type_traits>
+
+#include "chain2_side_plan.h"
+#include "rowchain_core.h"
 
 namespace anemoi {
 
@@ -66,6 +69,14 @@ struct Chain2Args {
   int warm;                                 // the L2 warm-up of the next step's weights (ANEMOI_CHAIN2_WARM=0: off, for the A/B)
   int b_delay;                              // group B's head start handicap in the dual MLP steps, units of ~0.5 us (ANEMOI_CHAIN2_B_DELAY)
   unsigned long long* timeline;             // developer aid (TL instantiation only): [workgroups][8 waves][kTl2Slots] s_memtime stamps
+};
+// The SIDE instantiation's launch: workgroups [0, host_grid) are the block tail's, workgroup host_grid + i walks the panels side_first + i,
+// side_first + i + side_blocks, ... < side_end of an independent row-chain job (rowchain_core.h) on a CU the tail leaves idle.
+struct Chain2SideArgs : Chain2Args {
+  int host_grid;
+  RowChainArgs side;
+  int side_first, side_end, side_blocks;
+  int side_pipe;  // the side job as a whole runs the pipelined schedule: so do its riders (rowchain_core.h rowchain_pipelined)
 };
 constexpr int kTl2Slots = 48;
 constexpr int kVecOff = vec_off(4);                       // the per-column vectors (16-bit), behind the [48 rows][4 waves][2] partials
@@ -116,10 +127,17 @@ __device__ __forceinline__ void set_chunk_prio(int on, int k) {
   else __builtin_amdgcn_s_setprio(0);
 }
 
+// the block tail's workgroup count: the whole grid, or - SIDE - its head
+template <bool SIDE>
+__device__ __forceinline__ int host_grid(int given) {
+  if constexpr (SIDE) return given;
+  else return (int)gridDim.x;
+}
+
 // Both roles execute the SAME number of s_barrier per panel (the hardware barrier counts arrivals, not program locations):
 // S0 | P GEMM | x1 | S2 | hc + 1 MLP steps | S8 | one behind the trailing projection (if any).
-template <typename T, bool TL, bool PART>
-__device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned char* smem) {
+template <typename T, bool TL, bool PART, bool SIDE>
+__device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned char* smem, int hgrid) {
   const int hc = a.hc, qc = a.qc, lane = c.lane, wq = __builtin_amdgcn_readfirstlane(c.wq);
   const int dbg = kExperiments ? a.dbg : 0;  // (timing experiments: compiled out of the product library)
   // bufA: the even hidden chunks (x2 / group A's staged projection outputs when hc is even); bufB: the A operand of P, M1 and the
@@ -141,7 +159,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
   const bool narrow_idle = a.qn > 0 && wq >= a.qn;  // a narrow trailing projection leaves this wave without a chunk
   auto seg_a = [&](int t) { return t < hc ? a.w1 + (int64_t)(8 * t) * kSlab : ((qc > 0 && a.qn == 0) ? a.wq : a.wp); };  // M1(t); behind the last chunk: Q0 / the next panel's P (a narrow Q is not a whole segment: not touched)
   Warm warm;
-  warm_init<PART>(warm, wq & 1, lane);
+  warm_init<PART, SIDE>(warm, wq & 1, lane, hgrid);
   auto touch = [&](const char* sa, const char* sb, int64_t pb) {
     touch_done<PART>(warm);
     if (!a.warm) return;
@@ -202,7 +220,7 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
     }
     stamp2<TL>(c, smem);
     if (qc > 1) touch(hc == 1 ? seg_a(hc) : nullptr, a.wq + (int64_t)8 * kSlab, kSlab);  // group B's first chunk of the trailing projection (Q0: behind M1(hc - 1))
-    const int tile_next = tile + (int)gridDim.x;
+    const int tile_next = tile + host_grid<SIDE>(hgrid);
     if (qc == 0 && tile_next < a.n_tiles) {
       // nothing to do in this step and bufB free (every wave of the group is behind its last M1 segment): the NEXT panel's attention rows
       const int rn = tile_next * a.rows_per_tile;
@@ -275,8 +293,8 @@ __device__ __forceinline__ void role_a(const Chain2Args& a, Ctx2& c, unsigned ch
   touch_done<PART>(warm);
 }
 
-template <typename T, bool TL>
-__device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned char* smem) {
+template <typename T, bool TL, bool SIDE>
+__device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned char* smem, int hgrid) {
   const int hc = a.hc, qc = a.qc, lane = c.lane, wq = __builtin_amdgcn_readfirstlane(c.wq);
   const int dbg = kExperiments ? a.dbg : 0;  // (timing experiments: compiled out of the product library)
   // bufA: the even hidden chunks (x2 / group A's staged projection outputs when hc is even); bufB: the A operand of P, M1 and the
@@ -374,7 +392,7 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
       stamp2<TL>(c, smem);
     }
     if (qc > 0) lds_barrier();
-    tile += (int)gridDim.x;
+    tile += host_grid<SIDE>(hgrid);
     if (tile >= a.n_tiles) break;
     if (qc > 0) lds_barrier();  // S0 of the next panel is group A's
   }
@@ -382,8 +400,11 @@ __device__ __forceinline__ void role_b(const Chain2Args& a, Ctx2& c, unsigned ch
 
 // PART: the launch has fewer than 256 workgroups (one round, not every CU busy): the L2 warm-up's shares follow the workgroup count.  Its own
 // instantiation, so that full-grid (multi-round) launches run the code they were tuned with (the general form costs them 1.5 %, same box).
-template <typename T, bool TL = false, bool PART = false>
-__global__ __launch_bounds__(512, 1) void gt_chain2_kernel(Chain2Args a) {
+// SIDE (with PART: the tail leaves CUs idle): the grid is host_grid + side_blocks, and the workgroups behind the tail's run the row chain's
+// schedule (the one the job as a whole has: single-panel or pipelined) on a slice of ANOTHER job's panels - work that does not depend on the tail (the decoder's destination side beside the
+// processor's tails).  The riders are ordinary independent workgroups: no flags, no spinning, no atomics, nothing assumed about their placement.
+template <typename T, bool TL = false, bool PART = false, bool SIDE = false>
+__global__ __launch_bounds__(512, 1) void gt_chain2_kernel(std::conditional_t<SIDE, Chain2SideArgs, Chain2Args> a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   Ctx2 c;
@@ -393,12 +414,22 @@ __global__ __launch_bounds__(512, 1) void gt_chain2_kernel(Chain2Args a) {
   c.loff = c.lane * 16;
   c.tl_n = 0;
   stamp2<TL>(c, smem);  // 0: entry
+  int hgrid = 0;
+  if constexpr (SIDE) {
+    hgrid = a.host_grid;
+    if ((int)blockIdx.x >= hgrid) {
+      const int first = a.side_first + ((int)blockIdx.x - hgrid);
+      if (a.side_pipe) rowchain_pipe_panels<T>(a.side, first, a.side_blocks, a.side_end);
+      else rowchain_panels<T>(a.side, SliceWalk{first, a.side_blocks, a.side_end});
+      return;
+    }
+  }
   if ((int)blockIdx.x >= a.n_tiles) return;
   if (c.wave < 4) {
     if (kExperiments && a.prio_a == 2) __builtin_amdgcn_s_setprio(2);
-    role_a<T, TL, PART>(a, c, smem);
+    role_a<T, TL, PART, SIDE>(a, c, smem, hgrid);
   } else {
-    role_b<T, TL>(a, c, smem);
+    role_b<T, TL, SIDE>(a, c, smem, hgrid);
   }
   if constexpr (TL) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -408,6 +439,15 @@ __global__ __launch_bounds__(512, 1) void gt_chain2_kernel(Chain2Args a) {
   }
 }
 
+// Several rounds: as many workgroups as make the rounds even (854 panels: 4 rounds of 214 instead of 3 of 256 + 86) - the CUs of an XCD share
+// that L2's bandwidth, so a round of 27 CUs per XCD is faster than one of 32 (ANEMOI_CHAIN2_EVEN_GRID=0: always 256)
+static int chain2_launch_grid(int n_tiles) {
+  static const int even_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_EVEN_GRID", 1, 0, 1);
+  static const int max_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_MAX_GRID", 256, 8, 256);  // (experiments: fewer CUs per round)
+  return chain2_grid(n_tiles, even_grid != 0, max_grid);
+}
+
+#ifndef ANEMOI_CHAIN2_SIDE_TU
 template <typename T>
 static int launch_chain2(const Chain2Args& a, hipStream_t st) {
   static PerDeviceOnce attr_once;
@@ -415,15 +455,7 @@ static int launch_chain2(const Chain2Args& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2Smem);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2Smem);
   });
-  // Several rounds: as many workgroups as make the rounds even (854 panels: 4 rounds of 214 instead of 3 of 256 + 86) - the CUs of an XCD share
-  // that L2's bandwidth, so a round of 27 CUs per XCD is faster than one of 32 (ANEMOI_CHAIN2_EVEN_GRID=0: always 256)
-  static const int even_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_EVEN_GRID", 1, 0, 1);
-  int grid = a.n_tiles < 256 ? a.n_tiles : 256;
-  static const int max_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_MAX_GRID", 256, 8, 256);  // (experiments: fewer CUs per round)
-  if (even_grid && a.n_tiles > 256) {
-    const int rounds = (a.n_tiles + max_grid - 1) / max_grid;
-    grid = (a.n_tiles + rounds - 1) / rounds;
-  }
+  const int grid = chain2_launch_grid(a.n_tiles);
 #ifdef ANEMOI_EXPERIMENTS
   if (a.timeline != nullptr) {
     static PerDeviceOnce tl_once;
@@ -441,9 +473,36 @@ static int launch_chain2(const Chain2Args& a, hipStream_t st) {
   return check_launch("gt_chain2_kernel");
 }
 
+#else  // ANEMOI_CHAIN2_SIDE_TU (gt_chain2_side.hip): the SIDE instantiation lives in a translation unit of its own - compiled beside it, the other
+// instantiations come out with other scalar register numbers than they were tuned and measured with
+constexpr int kSideMax2 = kRowChainSmem > kRowChain2Smem ? kRowChainSmem : kRowChain2Smem;
+constexpr int kChain2SideSmem = kChain2Smem > kSideMax2 ? kChain2Smem : kSideMax2;  // the tail's LDS or the riders', whichever is larger
+// the tail on the plan's host_grid workgroups with plan.riders workgroups of the side job behind them
+template <typename T>
+static int launch_chain2_side(const Chain2Args& a, const RowChainArgs& side, const Chain2SidePlan& plan, hipStream_t st) {
+  static PerDeviceOnce attr_once;
+  attr_once.run([&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2SideSmem);
+  });
+  Chain2SideArgs s{};
+  static_cast<Chain2Args&>(s) = a;
+  s.host_grid = plan.host_grid;
+  s.side = side;
+  s.side_first = plan.first;
+  s.side_end = plan.end;
+  s.side_blocks = plan.riders;
+  s.side_pipe = rowchain_pipelined(side.n_tiles, side.k_in) ? 1 : 0;
+  hipLaunchKernelGGL((gt_chain2_kernel<T, false, true, true>), dim3(plan.host_grid + plan.riders), dim3(512), kChain2SideSmem, st, s);
+  return check_launch("gt_chain2_kernel<side>");
+}
+
+#endif
+
 }  // namespace anemoi
 
 using namespace anemoi;
+
+#ifndef ANEMOI_CHAIN2_SIDE_TU
 
 extern "C" int anemoi_gt_chain_rows_per_tile(int32_t n_rows) {
   // Rows per LDS panel of the chain launch: always the TALLEST panels (48 rows), i.e. the fewest CUs - every busy CU streams the whole
@@ -455,7 +514,10 @@ extern "C" int anemoi_gt_chain_rows_per_tile(int32_t n_rows) {
   return forced > 0 ? forced : kPanel;
 }
 
-extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, void* stream) {
+#endif
+// The argument block of the C ABI -> the kernel's, behind every check of the entry points.  ANEMOI_OK with n_tiles = 0: nothing to do.
+static int chain2_args(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, Chain2Args& a) {
+  a = Chain2Args{};
   ANEMOI_REQUIRE(p != nullptr, "gt_chain2_fwd: null argument block");
   ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gt_chain2_fwd: 16-bit model dtypes only");
   ANEMOI_REQUIRE(p->n_rows >= 0 && p->channels == kCh, "gt_chain2_fwd: channels=%d (this kernel is built for %d)", p->channels, kCh);
@@ -476,7 +538,6 @@ extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t* p, anemoi_dty
                      (p->extra == nullptr || (p->ld_extra >= kCh && p->ld_extra % 8 == 0)) &&
                      (p->q_out_features == 0 || (p->ld_q >= p->q_out_features && p->ld_q % 8 == 0)),
                  "gt_chain2_fwd: leading dimensions too small or not multiples of 8 elements (rows move as 16-byte pieces)");
-  Chain2Args a{};
   a.attn = p->attn; a.ld_attn = p->ld_attn;
   a.xres = p->x_res; a.ld_x = p->ld_x;
   a.wp = (const char*)p->wp;
@@ -508,6 +569,40 @@ extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t* p, anemoi_dty
   a.rows_per_tile = p->rows_per_tile > 0 ? p->rows_per_tile : anemoi_gt_chain_rows_per_tile(p->n_rows);
   ANEMOI_REQUIRE(a.rows_per_tile <= kPanel, "gt_chain2_fwd: rows_per_tile=%d exceeds the %d-row panel", a.rows_per_tile, kPanel);
   a.n_tiles = (a.n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
+  return ANEMOI_OK;
+}
+
+#ifndef ANEMOI_CHAIN2_SIDE_TU
+extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, void* stream) {
+  Chain2Args a;
+  const int rc = chain2_args(p, dtype, a);
+  if (rc != ANEMOI_OK || a.n_tiles == 0) return rc;
   hipStream_t st = as_stream(stream);
   return dtype == ANEMOI_BF16 ? launch_chain2<bf16_t>(a, st) : launch_chain2<f16_t>(a, st);
 }
+
+#else
+extern "C" int anemoi_gt_chain2_side_fwd(const anemoi_gt_chain2_args_t* p, const anemoi_gt_rowchain_args_t* side, int32_t side_first_panel,
+                                         int32_t side_panels, int32_t side_blocks, anemoi_dtype_t dtype, void* stream) {
+  Chain2Args a;
+  int rc = chain2_args(p, dtype, a);
+  if (rc != ANEMOI_OK) return rc;
+  ANEMOI_REQUIRE(side != nullptr, "gt_chain2_side_fwd: null side job");
+  ANEMOI_REQUIRE(p->timeline == nullptr, "gt_chain2_side_fwd: no in-kernel timeline beside a side job");
+  ANEMOI_REQUIRE(side_first_panel >= 0 && side_panels >= 0 && side_blocks >= 0,
+                 "gt_chain2_side_fwd: side_first_panel=%d, side_panels=%d, side_blocks=%d must not be negative", side_first_panel, side_panels, side_blocks);
+  RowChainArgs r;
+  // (the side job's own preconditions: a job the row chain cannot take is the caller's to launch some other way)
+  if (rowchain_args(side, dtype, "gt_chain2_side_fwd (side job)", r) != ANEMOI_OK) return ANEMOI_E_UNSUPPORTED;
+  ANEMOI_REQUIRE((int64_t)side_first_panel + side_panels <= r.n_tiles, "gt_chain2_side_fwd: panels [%d, %d + %d) of a side job of %d panels",
+                 side_first_panel, side_first_panel, side_panels, r.n_tiles);
+  Chain2SidePlan plan;
+  if (!plan_chain2_side(a.n_tiles, chain2_launch_grid(a.n_tiles), side_first_panel, side_panels, side_blocks, plan)) {
+    set_error("gt_chain2_side_fwd: a tail of %d panels leaves no compute unit idle (launch the two pieces separately)", a.n_tiles);
+    return ANEMOI_E_UNSUPPORTED;
+  }
+  hipStream_t st = as_stream(stream);
+  if (plan.riders == 0) return anemoi_gt_chain2_fwd(p, dtype, stream);  // (no panels asked for)
+  return dtype == ANEMOI_BF16 ? launch_chain2_side<bf16_t>(a, r, plan, st) : launch_chain2_side<f16_t>(a, r, plan, st);
+}
+#endif

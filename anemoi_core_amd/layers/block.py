@@ -270,6 +270,11 @@ class BlockTail:
             nl, width = x_skip.shape[0], 2 * r.next_block.attn_channels
             buf = comm.recv_buffer(nl, plan.send_counts, plan.recv_counts, width, x_skip.dtype, x_skip.device, group)
             kw.update(q_out2=buf[:nl], q_split=width // ops.CHAIN_CHANNELS)
+        if r.kind == "chain2" and carrier is not None and carrier.side_job is not None:
+            # a tail of fewer than 256 panels per round leaves compute units idle: the next panels of the forward's side job run there
+            side = carrier.side_job.slice_for(attn.shape[0])
+            if side is not None:
+                kw["side"] = side
         res = (ops.gt_cluster_chain if r.kind == "cluster" else ops.gt_layer_chain2)(attn, x_skip, wp, w1g, w2, vec, hidden, ln.eps, **kw)
         return res if r.next_block is None else carrier.put(res[0], proj=res[1], kv=buf)
 

@@ -18,14 +18,73 @@ class Handoff:
     kv: Optional[Tensor] = None     # sharded: the [local + halo, 2A] k|v buffer, local rows filled, halo rows for the exchange
 
 
+def side_schedule(host_rows: int, side_panels_left: int, panels_per_rider: int) -> int:
+    """How many of a side job's remaining 48-row panels ride on a block-tail launch over ``host_rows`` rows: ``panels_per_rider`` for every
+    compute unit the launch leaves idle, per round of its panels (a tail of several rounds lasts that many times longer); 0 for a launch
+    that keeps every compute unit busy.  Pure: the hosting decision is this function and nothing else."""
+    from ..ops import CHAIN_PANEL_ROWS, CHIP_CUS, chain_idle_cus
+
+    idle = chain_idle_cus(host_rows)
+    if idle <= 0 or side_panels_left <= 0 or panels_per_rider <= 0:
+        return 0
+    rounds = -(-(-(-host_rows // CHAIN_PANEL_ROWS)) // (CHIP_CUS - idle))
+    return min(side_panels_left, idle * panels_per_rider * rounds)
+
+
+@dataclass
+class SideJob:
+    """A row-chain job (ops.gt_row_chain's operands, outputs preallocated) that does not depend on the launches between its creation and
+    its consumer: its panels ride on those launches' idle compute units (``ops.gt_layer_chain2(..., side=...)``), ``cursor`` panels so far."""
+    x: Tensor
+    we: Tensor
+    wqg: Tensor
+    vec: Tensor
+    q_out_features: int
+    ln_eps: float
+    y: Tensor
+    q: Tensor
+    panels_per_rider: int = 4
+    cursor: int = 0
+    hosted: int = 0  # panels that rode on other launches
+
+    @property
+    def n_panels(self) -> int:
+        from ..ops import CHAIN_PANEL_ROWS
+
+        return -(-self.x.shape[0] // CHAIN_PANEL_ROWS)
+
+    def slice_for(self, host_rows: int):
+        """The next panels for a block-tail launch over ``host_rows`` rows as an ``ops.ChainSide`` (None: none), taken off the job."""
+        from .. import ops
+
+        n = side_schedule(host_rows, self.n_panels - self.cursor, self.panels_per_rider)
+        if n <= 0:
+            return None
+        side = ops.ChainSide(self.x, self.we, self.wqg, self.vec, self.q_out_features, self.ln_eps, self.y, self.q, first_panel=self.cursor, panels=n)
+        self.cursor += n
+        self.hosted += n
+        return side
+
+    def finish(self) -> None:
+        """The panels no launch hosted, as one launch of their own."""
+        from .. import ops
+
+        if self.cursor < self.n_panels:
+            ops.gt_row_chain_panels(self.x, self.we, self.wqg, self.vec, self.q_out_features, self.ln_eps, self.y, self.q, self.cursor,
+                                    self.n_panels - self.cursor)
+        self.cursor = self.n_panels
+
+
 @dataclass
 class Carrier:
     """Per-forward: the next consumer of the rows a block produces, the decoder's extractor (LayerNorm, Linear) that may ride on its block's
-    tail and that tail's result, and the hand-offs not yet taken."""
+    tail and that tail's result, the hand-offs not yet taken, and a side job whose panels ride on the block tails."""
     next_block: Optional[nn.Module] = None
     tail_proj: Optional[tuple] = None
     tail_out: Optional[Tensor] = None
     handoffs: list = field(default_factory=list)
+    static_dst: Optional[Tensor] = None  # the encoder's destination rows when they are a static tensor (the hidden mesh's cached attributes)
+    side_job: Optional[SideJob] = None  # work for the idle compute units of the block tails on the way (the decoder's destination side)
 
     def put(self, rows: Tensor, **what) -> Tensor:
         self.handoffs.append(Handoff(rows, **what))

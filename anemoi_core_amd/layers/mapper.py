@@ -29,7 +29,7 @@ from ..distributed.partition import (
 )
 from ..distributed.shapes import BipartiteGraphShardInfo, comm_rank, comm_size, get_shard_sizes, model_is_distributed
 from .block import GraphConvMapperBlock, GraphTransformerMapperBlock
-from .handoff import Carrier, inference_in, plain_layer_norm
+from .handoff import Carrier, SideJob, inference_in, plain_layer_norm
 from .kernels import PaddedLinear
 from .mlp import MLP
 from .utils import compute_mlp_hidden_dim, load_layer_kernels
@@ -50,6 +50,9 @@ _ROW_CHAIN_MIN_ROWS = int(os.environ.get("ANEMOI_ROW_CHAIN_MIN_ROWS", "4096"))
 # The decoder's node_data_extractor (LayerNorm + Linear(512, out)) as the narrow trailing projection of the block's chain launch (inference, block
 # tails on the row-resident chain): ANEMOI_TAIL_PROJ=0 keeps its LayerNorm launch + GEMM.
 _TAIL_PROJ = os.environ.get("ANEMOI_TAIL_PROJ", "1") != "0"
+# The encoder's destination side embeds the hidden mesh's static attributes: at inference its rows and their q|self are the same every forward
+# and are kept, keyed like the derived weights (the input's and the parameters' identity and version).  ANEMOI_ENC_DST_CACHE=0: recomputed.
+_ENC_DST_CACHE = os.environ.get("ANEMOI_ENC_DST_CACHE", "1") != "0"
 _ROW_CHAIN_GEMM_BAND = tuple(int(v) for v in os.environ.get("ANEMOI_ROW_CHAIN_GEMM_BAND", "16384:262144").split(":"))
 
 
@@ -148,21 +151,22 @@ class GraphTransformerBaseMapper(BaseMapper):
         """(LayerNorm, Linear) of a post_process that is row-local and can ride at the end of the block's chain launch; None: there is none."""
         return None
 
-    def _row_chain_ok(self, x: Tensor, lin, ln, projs: list) -> bool:
+    def _row_chain_ok(self, x: Tensor, lin, ln, projs: list, band: bool = True) -> bool:
         """The embedding -> LayerNorm -> projection chain launch (ops.gt_row_chain) takes this side: inference, 16-bit, 512 channels, a
-        plain affine LayerNorm, rows whose width is a multiple of 8 (the model pads its inputs), enough rows to fill the chip."""
+        plain affine LayerNorm, rows whose width is a multiple of 8 (the model pads its inputs), enough rows to fill the chip.  ``band=False``:
+        without the row band in which a launch of its own loses to the GEMM pair (panels that ride on other launches cost no launch)."""
         return (_ROW_CHAIN and x.is_cuda and x.dim() == 2 and x.dtype != torch.float32 and x.shape[0] >= _ROW_CHAIN_MIN_ROWS
-                and not (_ROW_CHAIN_GEMM_BAND[0] < x.shape[0] < _ROW_CHAIN_GEMM_BAND[1])
+                and not (band and _ROW_CHAIN_GEMM_BAND[0] < x.shape[0] < _ROW_CHAIN_GEMM_BAND[1])
                 and self.hidden_dim == ops.CHAIN_CHANNELS and plain_layer_norm(ln) and lin.in_features <= x.shape[1] and lin.bias is not None
                 and ops.gt_row_chain_supported(x, sum(p.out_features for p in projs)) and all(p.in_features == ops.CHAIN_CHANNELS for p in projs)
                 and inference_in(x, lin, ln, *projs))
 
-    def _row_chain(self, x: Tensor, lin, side: str, want_x: bool):
-        """(embedded rows or None, the block's fused projection of that side) in one launch, or None if the shapes do not fit."""
+    def _row_chain_operands(self, x: Tensor, lin, side: str, band: bool = True):
+        """ops.gt_row_chain's operands behind ``x`` for that side - (we, wqg, vec, q_out_features, eps) - or None if the shapes do not fit."""
         blk = self.proc
         ln = blk.layer_norm_attention_src if side == "src" else blk.layer_norm_attention_dest
         projs = [blk.lin_key, blk.lin_value] if side == "src" else [blk.lin_query, blk.lin_self]
-        if not self._row_chain_ok(x, lin, ln, projs):
+        if not self._row_chain_ok(x, lin, ln, projs, band):
             return None
         params = [lin.weight, lin.bias, ln.weight, ln.bias] + [q for m in projs for q in (m.weight, m.bias)]
         K = x.shape[1]
@@ -174,8 +178,32 @@ class GraphTransformerBaseMapper(BaseMapper):
             wqg, dq = ops.fold_layer_norm(wq, bq, ln.weight, ln.bias)
             return ops.pack_embedding_frag(w), ops.pack_weight_frag(wqg), torch.cat([lin.bias.float(), dq]).to(x.dtype).contiguous(), wq.shape[0]
 
-        we, wqg, vec, q_out = blk._fused.derived(f"rowchain:{side}:{K}", params, build)
-        return ops.gt_row_chain(x, we, wqg, vec, q_out, ln.eps, want_x_out=want_x)
+        return (*blk._fused.derived(f"rowchain:{side}:{K}", params, build), ln.eps)
+
+    def _row_chain(self, x: Tensor, lin, side: str, want_x: bool):
+        """(embedded rows or None, the block's fused projection of that side) in one launch, or None if the shapes do not fit."""
+        operands = self._row_chain_operands(x, lin, side)
+        return None if operands is None else ops.gt_row_chain(x, *operands, want_x_out=want_x)
+
+    def _static_row_chain(self, x: Tensor, lin):
+        """``_row_chain`` of the destination side for rows that are the same tensor every forward (inference): computed once per version of the
+        rows and of the parameters.  (The entry keeps ``x`` alive: its address cannot come back as another tensor's.)"""
+        blk = self.proc
+        ln, projs = blk.layer_norm_attention_dest, [blk.lin_query, blk.lin_self]
+        params = [x, lin.weight, lin.bias, ln.weight, ln.bias] + [q for m in projs for q in (m.weight, m.bias)]
+        return blk._fused.derived(f"rowchain-static:dst:{x.shape[1]}", params, lambda: (self._row_chain(x, lin, "dst", True), x))[0]
+
+    def destination_side_job(self, x_dst: Tensor, panels_per_rider: int) -> Optional[SideJob]:
+        """This mapper's destination side (emb_nodes_dst -> layer_norm_attention_dest -> q|self) as a job whose 48-row panels can ride on
+        block-tail launches that run BEFORE this mapper (layers/handoff.py): it reads nothing but ``x_dst``.  None where the row chain
+        does not take the side."""
+        operands = self._row_chain_operands(x_dst, self.emb_nodes_dst, "dst", band=False)
+        if operands is None:
+            return None
+        we, wqg, vec, q_out, eps = operands
+        n, dt, dev = x_dst.shape[0], x_dst.dtype, x_dst.device
+        return SideJob(x=x_dst, we=we, wqg=wqg, vec=vec, q_out_features=q_out, ln_eps=eps, y=torch.empty((n, self.hidden_dim), dtype=dt, device=dev),
+                       q=torch.empty((n, q_out), dtype=dt, device=dev), panels_per_rider=panels_per_rider)
 
     def _embed(self, padded: PaddedLinear, x: Tensor, lin, side: str, carrier: Optional[Carrier]) -> Tensor:
         """The node embedding.  With a ``carrier`` (inference): where the shapes fit, embedding, the block's LayerNorm on that side and its
@@ -183,8 +211,16 @@ class GraphTransformerBaseMapper(BaseMapper):
         written unless the block updates them) - else the embedding hands over the row statistics of its output when the block's
         LayerNorm on that side can be folded into the GEMM behind it."""
         ln = self.proc.layer_norm_attention_src if side == "src" else self.proc.layer_norm_attention_dest
+        if carrier is not None and side == "dst" and carrier.side_job is not None and carrier.side_job.x is x:
+            # the rows and their q|self were computed beside the block tails that ran before this mapper; what no launch hosted, now
+            job, carrier.side_job = carrier.side_job, None
+            job.finish()
+            return carrier.put(job.y, proj=job.q)
         if carrier is not None:
-            r = self._row_chain(x, lin, side, want_x=side == "dst" or self.proc.update_src_nodes)
+            if _ENC_DST_CACHE and side == "dst" and carrier.static_dst is x and not torch.is_grad_enabled():
+                r = self._static_row_chain(x, lin)
+            else:
+                r = self._row_chain(x, lin, side, want_x=side == "dst" or self.proc.update_src_nodes)
             if r is not None:
                 y, proj = r
                 # (source rows nobody reads: an empty [N, 0] stand-in keeps the row count the block's graph plumbing looks at)

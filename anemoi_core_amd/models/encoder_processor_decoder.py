@@ -29,6 +29,13 @@ _FUSED_INPUT = os.environ.get("ANEMOI_FUSED_INPUT", "1") == "1"  # developer swi
 _PAD64 = os.environ.get("ANEMOI_PAD64", "1") == "1"  # developer switch: 0 = pad the input width to a multiple of 8 only
 # the decoder block's k|v projection of the hidden rows at the end of the last processor block's chain launch (ANEMOI_TAIL_KV=0: LayerNorm launch + GEMM)
 _TAIL_KV = os.environ.get("ANEMOI_TAIL_KV", "1") != "0"
+# The decoder's destination side (emb_nodes_dst -> layer_norm_attention_dest -> q|self over the data rows) reads nothing but the assembled input:
+# its 48-row panels ride on the compute units the encoder's and the processor's block tails leave idle (layers/handoff.py SideJob,
+# csrc/gt_chain2.hip SIDE) instead of standing as launches of their own behind the last processor layer.  ANEMOI_SIDE_JOB=0: off - the path is
+# then exactly the one without it.  ANEMOI_SIDE_PANELS_PER_RIDER: panels per idle compute unit and round of a hosting launch.
+_SIDE_JOB = os.environ.get("ANEMOI_SIDE_JOB", "1") != "0"
+_SIDE_PANELS_PER_RIDER = int(os.environ.get("ANEMOI_SIDE_PANELS_PER_RIDER", "4"))
+LAST_SIDE_JOB_PANELS = None  # developer aid / tests: (panels hosted, panels left over) of the last forward's side job; None: it had none
 from ..utils.config import DotDict, instantiate
 
 _REF_PREFIX = "anemoi.models.layers."
@@ -342,6 +349,10 @@ class AnemoiModelEncProcDec(nn.Module):
         if len(names) == 1 and isinstance(self.encoder[names[0]], GraphTransformerForwardMapper) and isinstance(self.processor, GraphTransformerProcessor):
             carrier = Carrier(next_block=self.processor.proc[0] if model_comm_group is None else None)
         chain_kw = {} if carrier is None else {"carrier": carrier}
+        global LAST_SIDE_JOB_PANELS
+        side_job = LAST_SIDE_JOB_PANELS = None
+        if carrier is not None and model_comm_group is None and not torch.is_grad_enabled():
+            carrier.static_dst = x_hidden_latent  # (inference: the cached static attribute tensor - the encoder may keep what it computes from it)
         for ds in names:
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
             norm_in, norm_out = (_fused_norm or {}).get(ds, (None, None))
@@ -349,6 +360,9 @@ class AnemoiModelEncProcDec(nn.Module):
             if self._truncated[ds]:  # once per dataset and forward: down (columns, normaliser), up; the skip is then normalised
                 x_skip, raw = self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data), False
             skips[ds], data_shards[ds] = (x_skip, raw, norm_in, norm_out), shard_sizes_data
+            if (_SIDE_JOB and carrier is not None and model_comm_group is None and not torch.is_grad_enabled()
+                    and isinstance(self.decoder[ds], GraphTransformerBackwardMapper)):
+                side_job = carrier.side_job = self.decoder[ds].destination_side_job(x_data_latent, _SIDE_PANELS_PER_RIDER)
             ea, ei, es = self.encoder_graph_provider[ds].get_edges(batch_size=batch_size, model_comm_group=model_comm_group)
             info = BipartiteGraphShardInfo(src_nodes=shard_sizes_data, dst_nodes=shard_sizes_hidden, edges=es)
             x_data_latent, x_latent = self.encoder[ds]((x_data_latent, x_hidden_latent.to(x_data_latent.dtype)), batch_size=batch_size,
@@ -381,6 +395,8 @@ class AnemoiModelEncProcDec(nn.Module):
             info = BipartiteGraphShardInfo(src_nodes=shard_sizes_hidden, dst_nodes=data_shards[ds], edges=es)
             x_out = self.decoder[ds]((x_latent_proc, data_latents[ds]), batch_size=batch_size, shard_info=info, edge_attr=ea,
                                      edge_index=ei, model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds], **chain_kw)
+            if side_job is not None:
+                LAST_SIDE_JOB_PANELS = (side_job.hosted, side_job.n_panels - side_job.hosted)
             x_skip, raw, norm_in, norm_out = skips[ds]
             out[ds] = self._assemble_output(x_out, x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=norm_in, skip_is_raw=raw,
                                             denorm=norm_out, compact=self._truncated[ds])

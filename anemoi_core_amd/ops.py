@@ -1041,7 +1041,7 @@ def gt_layer_chain2_supported(x: Tensor, hidden: int, q_out: int = 0) -> bool:
 
 def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Tensor, vec: Tensor, hidden: int, ln1_eps: float, *,
                     extra: Optional[Tensor] = None, wqg: Optional[Tensor] = None, q_out_features: int = 0, lnq_eps: float = 1e-5,
-                    rows_per_tile: int = 0, timeline: Optional[Tensor] = None, want_x_out: bool = True):
+                    rows_per_tile: int = 0, timeline: Optional[Tensor] = None, want_x_out: bool = True, side: Optional["ChainSide"] = None):
     """The row-local part of a GraphTransformer block in ONE launch with role-split waves (anemoi_gt_chain2_fwd, csrc/gt_chain2.hip):
 
         x1 = attn Wp^T + bp + x_res;  h = GELU(LN(x1; ln1) W1^T + b1);  x_out = h W2^T + b2 + x1 [+ extra]
@@ -1051,6 +1051,8 @@ def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Te
     ``W diag(gamma)``, ``vec = cat[bp, d1, b2, dq]`` in the model dtype with ``d = W beta + b``.  ``q_out_features`` may also be 128, 256 or
     384 (a narrow trailing projection, e.g. the decoder's ``node_data_extractor`` zero-padded to a multiple of 128 rows); with
     ``want_x_out=False`` (needs a trailing projection) x_out is not written and returned as None.  Returns ``x_out`` or ``(x_out, q_out)``.
+    ``side`` (a ``ChainSide``): panels of an independent row-chain job computed by the SAME launch on the compute units this tail leaves idle
+    (anemoi_gt_chain2_side_fwd); NotImplementedError, and nothing launched, where the tail leaves none idle (``chain_idle_cus``).
     Inference only (no autograd)."""
     _dev(attn, x_res, wp, w1g, w2, vec, extra, wqg)
     N, D = attn.shape
@@ -1078,8 +1080,58 @@ def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Te
     a = _Chain2Args(ap, lda, xp, ldx, wp.data_ptr(), w1g.data_ptr(), hidden, w2.data_ptr(), 0 if wqg is None else wqg.data_ptr(), q_out_features,
                     vec.data_ptr(), float(ln1_eps), float(lnq_eps), ep, lde, 0 if x_out is None else x_out.data_ptr(), D, 0 if q_out is None else q_out.data_ptr(),
                     q_out_features, N, D, int(rows_per_tile), 0 if timeline is None else timeline.data_ptr())
-    _lib.check(_lib.load().anemoi_gt_chain2_fwd(_lib.C.byref(a), _dt(attn), _stream()), "gt_chain2_fwd")
+    if side is None:
+        _lib.check(_lib.load().anemoi_gt_chain2_fwd(_lib.C.byref(a), _dt(attn), _stream()), "gt_chain2_fwd")
+    else:
+        if side.x.dtype != dt or side.x.device != attn.device:
+            raise ValueError("gt_layer_chain2: the side job's rows must have the tail's dtype and device")
+        n_panels = side.n_panels
+        count = n_panels - side.first_panel if side.panels is None else side.panels
+        if not (0 <= side.first_panel and 0 <= count and side.first_panel + count <= n_panels and side.max_riders >= 0):
+            raise ValueError(f"gt_layer_chain2: side panels [{side.first_panel}, +{count}) of {n_panels}, max_riders={side.max_riders}")
+        b = _row_chain_args(side.x, side.we, side.wqg, side.vec, side.q_out_features, side.ln_eps, side.y, side.q, 0)
+        _lib.check(_lib.load().anemoi_gt_chain2_side_fwd(_lib.C.byref(a), _lib.C.byref(b), side.first_panel, count, side.max_riders, _dt(attn),
+                                                         _stream()), "gt_chain2_side_fwd")
     return x_out if q_out is None else (x_out, q_out)
+
+
+CHAIN_PANEL_ROWS = 48  # rows of an LDS panel of the chain kernels
+CHIP_CUS = 256         # MI355X: one chain workgroup per compute unit
+
+
+def chain_idle_cus(n_rows: int) -> int:
+    """Compute units a ``gt_layer_chain2`` launch over ``n_rows`` rows leaves idle in every round of panels (csrc/chain2_side_plan.h: one
+    workgroup per 48-row panel up to 256; beyond, as many as make the rounds even)."""
+    tiles = -(-n_rows // CHAIN_PANEL_ROWS)
+    if tiles <= 0:
+        return 0
+    grid = tiles
+    if tiles > CHIP_CUS:
+        rounds = -(-tiles // CHIP_CUS)
+        grid = -(-tiles // rounds)
+    return CHIP_CUS - min(grid, CHIP_CUS)
+
+
+@dataclass
+class ChainSide:
+    """A row-chain job (``gt_row_chain``'s operands, outputs preallocated) whose panels ride on block-tail launches: ``gt_layer_chain2(...,
+    side=...)`` computes panels [first_panel, first_panel + panels) of it (``panels=None``: to the end); ``max_riders`` caps the workgroups
+    that do (0: every idle compute unit)."""
+    x: Tensor
+    we: Tensor
+    wqg: Tensor
+    vec: Tensor
+    q_out_features: int
+    ln_eps: float
+    y: Optional[Tensor]   # [N, 512] or None
+    q: Tensor             # [N, q_out_features]
+    first_panel: int = 0
+    panels: Optional[int] = None
+    max_riders: int = 0
+
+    @property
+    def n_panels(self) -> int:
+        return -(-self.x.shape[0] // CHAIN_PANEL_ROWS)
 
 
 class _ClusterChainArgs(_lib.C.Structure):
@@ -1180,7 +1232,27 @@ def gt_row_chain(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_features
 
     ``we``: ``pack_embedding_frag(We)``; ``wqg``: fragment-major image of ``Wq diag(gamma)``; ``vec = cat[be, Wq beta + bq]`` in the
     model dtype (``fold_layer_norm``).  Returns ``(y or None, q_out)``.  Inference only (no autograd)."""
-    _dev(x, we, wqg, vec)
+    N, dt, D = x.shape[0], x.dtype, CHAIN_CHANNELS
+    x_out = torch.empty((N, D), dtype=dt, device=x.device) if want_x_out else None
+    q_out = torch.empty((N, q_out_features), dtype=dt, device=x.device)
+    a = _row_chain_args(x, we, wqg, vec, q_out_features, ln_eps, x_out, q_out, rows_per_tile)
+    _lib.check(_lib.load().anemoi_gt_rowchain_fwd(_lib.C.byref(a), _dt(x), _stream()), "gt_rowchain_fwd")
+    return x_out, q_out
+
+
+def gt_row_chain_panels(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_features: int, ln_eps: float, y: Optional[Tensor], q: Tensor,
+                        first_panel: int, panels: int) -> None:
+    """48-row panels [first_panel, first_panel + panels) of the job ``gt_row_chain(x, ...)`` into the rows of ``y`` (or None) and ``q`` they
+    belong to, as one launch with the schedule the whole job's launch has (anemoi_gt_rowchain_panels_fwd): bit for bit the rows ``gt_row_chain``
+    writes, whichever launch computes them."""
+    a = _row_chain_args(x, we, wqg, vec, q_out_features, ln_eps, y, q, 0)
+    _lib.check(_lib.load().anemoi_gt_rowchain_panels_fwd(_lib.C.byref(a), int(first_panel), int(panels), _dt(x), _stream()), "gt_rowchain_panels_fwd")
+
+
+def _row_chain_args(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_features: int, ln_eps: float, x_out: Optional[Tensor], q_out: Tensor,
+                    rows_per_tile: int) -> _RowChainArgs:
+    """The argument block of a row-chain job behind the operand checks (``gt_row_chain``; the side job of ``gt_layer_chain2``)."""
+    _dev(x, we, wqg, vec, x_out, q_out)
     N, K = x.shape
     dt, D = x.dtype, CHAIN_CHANNELS
     if not gt_row_chain_supported(x, q_out_features):
@@ -1191,13 +1263,12 @@ def gt_row_chain(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_features
             raise ValueError(f"gt_row_chain: {name} must be the contiguous fragment-major image ({numel} x {dt})")
     if vec.dim() != 1 or vec.numel() != D + q_out_features or vec.dtype != dt or not vec.is_contiguous():
         raise ValueError(f"gt_row_chain: vec must be contiguous [{D + q_out_features}] {dt} = cat[be, dq]")
-    x_out = torch.empty((N, D), dtype=dt, device=x.device) if want_x_out else None
-    q_out = torch.empty((N, q_out_features), dtype=dt, device=x.device)
+    for name, t, cols in (("x_out", x_out, D), ("q_out", q_out, q_out_features)):
+        if t is not None and (tuple(t.shape) != (N, cols) or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"gt_row_chain: {name} must be contiguous [{N}, {cols}] {dt}")
     xp, ldx = _rows(x, "x", dt)
-    a = _RowChainArgs(xp, ldx, K, we.data_ptr(), wqg.data_ptr(), q_out_features, vec.data_ptr(), float(ln_eps),
-                      0 if x_out is None else x_out.data_ptr(), D, q_out.data_ptr(), q_out_features, N, D, int(rows_per_tile))
-    _lib.check(_lib.load().anemoi_gt_rowchain_fwd(_lib.C.byref(a), _dt(x), _stream()), "gt_rowchain_fwd")
-    return x_out, q_out
+    return _RowChainArgs(xp, ldx, K, we.data_ptr(), wqg.data_ptr(), q_out_features, vec.data_ptr(), float(ln_eps),
+                         0 if x_out is None else x_out.data_ptr(), D, q_out.data_ptr(), q_out_features, N, D, int(rows_per_tile))
 
 
 def gnn_edge_chain(e: Tensor, g1: Tensor, idx1: Tensor, g2: Tensor, idx2: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor, w2: Tensor,

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 17
+#define ANEMOI_HIP_ABI_VERSION 18
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -464,6 +464,23 @@ typedef struct anemoi_gt_rowchain_args {
   int32_t n_rows;     int32_t channels;   int32_t rows_per_tile;  /* rows_per_tile = 0: 48 */
 } anemoi_gt_rowchain_args_t;
 int anemoi_gt_rowchain_fwd(const anemoi_gt_rowchain_args_t* args, anemoi_dtype_t dtype, void* stream);
+/* Panels [first_panel, first_panel + panels) of that job (48-row panels, or rows_per_tile) as a launch of their own, with the schedule the
+ * WHOLE job's launch has (more than one round of panels and in_features <= 256: the pipelined kernel, else the single-panel one; the two
+ * round differently), so that a row's bits do not depend on which launch computed it. */
+int anemoi_gt_rowchain_panels_fwd(const anemoi_gt_rowchain_args_t* args, int32_t first_panel, int32_t panels, anemoi_dtype_t dtype, void* stream);
+
+/* ---- a block tail that carries a side job (csrc/gt_chain2.hip, SIDE instantiation) ------------------------------------------------
+ * anemoi_gt_chain2_fwd(args) and, in the SAME launch, panels [side_first_panel, side_first_panel + side_panels) of the row chain
+ * `side` (48-row panels of its rows, rows_per_tile as in anemoi_gt_rowchain_fwd) on workgroups of their own behind the tail's: a tail of
+ * fewer than 256 panels per round leaves compute units idle, and work that does not depend on the tail can run there.  The two jobs
+ * share nothing but the launch; each computes exactly what its own entry point computes (the riders run the schedule the whole side job's
+ * launch has: anemoi_gt_rowchain_panels_fwd).  side_blocks = 0: one rider per idle compute
+ * unit (256 - the tail's workgroups per round); > 0: at most that many.  A rider walks its panels with stride riders.
+ * ANEMOI_E_UNSUPPORTED, nothing launched: the tail leaves no compute unit idle (256 workgroups per round, or no rows at all), or the
+ * side job fails anemoi_gt_rowchain_fwd's preconditions - the caller launches the two pieces separately.  Every argument check of the
+ * two entry points applies; side_panels = 0 launches the tail alone. */
+int anemoi_gt_chain2_side_fwd(const anemoi_gt_chain2_args_t* args, const anemoi_gt_rowchain_args_t* side, int32_t side_first_panel,
+                              int32_t side_panels, int32_t side_blocks, anemoi_dtype_t dtype, void* stream);
 
 /* ---- cluster chain: the block tail for FEW rows (round 6; csrc/gt_cluster_chain.hip) ----------------------------------------------
  * What anemoi_gt_chain2_fwd computes (same operands, same folded LayerNorms, same vec layout with hidden = 2048:

@@ -1,0 +1,149 @@
+"""The hosting decision of the side job (layers/handoff.py side_schedule) as a property, and the encoder's destination-side cache
+(layers/mapper.py _static_row_chain) with the launch replaced by a counter: both run without a GPU."""
+import random
+
+import pytest
+import torch
+
+
+def _panels_per_round(host_rows):
+    """csrc/chain2_side_plan.h chain2_grid, restated: workgroups of a tail over host_rows rows"""
+    tiles = -(-host_rows // 48)
+    if tiles <= 256:
+        return tiles
+    rounds = -(-tiles // 256)
+    return -(-tiles // rounds)
+
+
+def _cases():
+    rng = random.Random(13)
+    hosts = [1, 47, 48, 49, 149, 10242, 12240, 12241, 12287, 12288, 12289, 12336, 24576, 24577, 40320, 40962, 60000]
+    hosts += [256 * 48 * r for r in (1, 2, 3, 4)] + [rng.randint(1, 60000) for _ in range(300)]
+    sides = [0, 1, 7, 8, 41, 42, 43, 167, 168, 169, 840, 11294, 12000] + [rng.randint(0, 12000) for _ in range(40)]
+    return hosts, sides
+
+
+def test_side_schedule_assigns_every_panel_once_in_order():
+    from anemoi_core_amd.layers.handoff import side_schedule
+    from anemoi_core_amd.ops import chain_idle_cus
+
+    hosts, sides = _cases()
+    for ppr in range(1, 7):
+        for n_side in sides:
+            cursor, taken = 0, []
+            for host_rows in hosts:
+                n = side_schedule(host_rows, n_side - cursor, ppr)
+                grid = _panels_per_round(host_rows)
+                assert chain_idle_cus(host_rows) == 256 - grid
+                assert 0 <= n <= n_side - cursor
+                if grid == 256:
+                    assert n == 0, (host_rows, n)  # a launch that keeps every compute unit busy hosts nothing
+                else:
+                    rounds = -(-(-(-host_rows // 48)) // grid)
+                    # the riders of a launch get ppr panels each per round of the tail - or all that is left
+                    assert n == min(n_side - cursor, (256 - grid) * ppr * rounds), (host_rows, n_side, cursor, ppr, n)
+                taken.append((cursor, n))
+                cursor += n
+            # in order, no gap, no overlap; the leftovers are what remains
+            pos = 0
+            for first, n in taken:
+                assert first == pos
+                pos += n
+            assert pos == cursor <= n_side
+            assert n_side - cursor == n_side - sum(n for _, n in taken)
+
+
+@pytest.mark.parametrize("host_rows", range(1, 60001, 997))
+def test_side_schedule_over_host_rows(host_rows):
+    from anemoi_core_amd.layers.handoff import side_schedule
+
+    grid = _panels_per_round(host_rows)
+    for ppr in (1, 4, 6):
+        for left in (0, 1, 500, 12000):
+            n = side_schedule(host_rows, left, ppr)
+            assert (n == 0) if (grid == 256 or left == 0) else (0 < n <= left)
+
+
+def test_side_job_walks_its_panels_and_leaves_the_rest(monkeypatch):
+    """SideJob.slice_for hands out consecutive panel ranges; finish() launches exactly the remaining panels of the same job"""
+    from anemoi_core_amd import ops
+    from anemoi_core_amd.layers.handoff import SideJob
+
+    n = 840 * 48 - 5
+    t = torch.zeros(1)
+    job = SideJob(x=torch.zeros(n, 8), we=t, wqg=t, vec=t, q_out_features=1024, ln_eps=1e-5, y=torch.zeros(n, 2), q=torch.zeros(n, 4), panels_per_rider=4)
+    got = []
+    for host_rows in (10242, 10242, 256 * 48, 10242):
+        s = job.slice_for(host_rows)
+        got.append(None if s is None else (s.first_panel, s.panels))
+    assert got == [(0, 168), (168, 168), None, (336, 168)] and job.hosted == 504 and job.cursor == 504
+    calls = []
+    monkeypatch.setattr(ops, "gt_row_chain_panels", lambda x, we, wqg, vec, qf, eps, y, q, first, count: calls.append((x is job.x, y is job.y, q is job.q, first, count)))
+    job.finish()
+    assert calls == [(True, True, True, 504, 336)] and job.cursor == 840
+    job.finish()  # nothing left: no launch
+    assert len(calls) == 1
+
+
+def test_encoder_destination_cache_follows_parameter_and_input_versions(monkeypatch):
+    """an unchanged parameter does not recompute, an in-place update (version bump) of a parameter or of the input rows does, and the cached
+    result is the object a fresh computation returned"""
+    import anemoi_core_amd.layers.mapper as M
+
+    torch.manual_seed(0)
+    mapper = M.GraphTransformerForwardMapper(in_channels_src=16, in_channels_dst=8, hidden_dim=32, num_chunks=1, num_heads=4, mlp_hidden_ratio=2.0,
+                                             edge_dim=4).eval()
+    x = torch.randn(10, 8)
+    calls = []
+
+    def fake_row_chain(xx, lin, side, want_x):
+        calls.append(side)
+        y = torch.nn.functional.linear(xx, lin.weight, lin.bias)
+        return y, y * 2
+
+    monkeypatch.setattr(mapper, "_row_chain", fake_row_chain)
+    with torch.no_grad():
+        a = mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        b = mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        assert calls == ["dst"] and a[0] is b[0] and a[1] is b[1]
+        fresh = fake_row_chain(x, mapper.emb_nodes_dst, "dst", True)
+        assert torch.equal(a[0], fresh[0]) and torch.equal(a[1], fresh[1])  # bit-equal to a fresh one
+        n = len(calls)
+        mapper.emb_nodes_dst.weight.mul_(0.5)  # in place: the parameter's version moves
+        c = mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        assert len(calls) == n + 1 and not torch.equal(c[0], a[0])
+        mapper.proc.lin_query.bias.add_(1.0)
+        mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        assert len(calls) == n + 2
+        x.add_(1.0)  # the input rows change in place
+        d = mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        assert len(calls) == n + 3 and not torch.equal(d[0], c[0])
+        mapper._static_row_chain(x, mapper.emb_nodes_dst)
+        assert len(calls) == n + 3
+        other = x.clone()  # other rows: another tensor, recomputed
+        mapper._static_row_chain(other, mapper.emb_nodes_dst)
+        assert len(calls) == n + 4
+
+
+def test_static_rows_are_used_only_for_the_carriers_static_tensor(monkeypatch):
+    """_embed takes the cache only for the tensor the model marked static, only on the destination side, only without autograd"""
+    import anemoi_core_amd.layers.mapper as M
+    from anemoi_core_amd.layers.handoff import Carrier
+
+    torch.manual_seed(0)
+    mapper = M.GraphTransformerForwardMapper(in_channels_src=16, in_channels_dst=8, hidden_dim=32, num_chunks=1, num_heads=4, mlp_hidden_ratio=2.0,
+                                             edge_dim=4).eval()
+    x = torch.randn(10, 8)
+    used = []
+    monkeypatch.setattr(mapper, "_static_row_chain", lambda xx, lin: used.append("static") or (xx, xx))
+    monkeypatch.setattr(mapper, "_row_chain", lambda xx, lin, side, want_x: used.append("plain") or (xx, xx))
+    with torch.no_grad():
+        mapper._embed(mapper._emb_dst, x, mapper.emb_nodes_dst, "dst", Carrier(static_dst=x))
+        mapper._embed(mapper._emb_dst, x, mapper.emb_nodes_dst, "dst", Carrier(static_dst=x.clone()))
+        mapper._embed(mapper._emb_dst, x, mapper.emb_nodes_dst, "dst", Carrier())
+    mapper._embed(mapper._emb_dst, x, mapper.emb_nodes_dst, "dst", Carrier(static_dst=x))  # autograd on
+    assert used == ["static", "plain", "plain", "plain"]
+    monkeypatch.setattr(M, "_ENC_DST_CACHE", False)
+    with torch.no_grad():
+        mapper._embed(mapper._emb_dst, x, mapper.emb_nodes_dst, "dst", Carrier(static_dst=x))
+    assert used[-1] == "plain"
