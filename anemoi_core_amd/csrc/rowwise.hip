@@ -454,14 +454,17 @@ __global__ void bound_columns_kernel(T* __restrict__ x, int64_t ldx, int n_rows,
     float v = to_float(row[col]);
     auto leaky = [](float t) { return t > 0.f ? t : 0.01f * t; };
     auto lht = [&](float t) { return t < p0 ? p0 + 0.01f * (t - p0) : (t > p1 ? p1 + 0.01f * (t - p1) : t); };
+    // comparisons, not fmaxf / fminf (which return the non-NaN operand): a NaN stays a NaN, as through torch.relu / hardtanh / clamp
+    auto relu = [](float t) { return t < 0.f ? 0.f : t; };
+    auto clamp = [&](float t) { return t < p0 ? p0 : (t > p1 ? p1 : t); };
     switch (kind) {
-      case 1: v = fmaxf(v, 0.f); break;
+      case 1: v = relu(v); break;
       case 2: v = leaky(v); break;
-      case 3: v = fmaxf(v - p0, 0.f) + p0; break;
+      case 3: v = relu(v - p0) + p0; break;
       case 4: v = leaky(v - p0) + p0; break;
-      case 5: v = fminf(fmaxf(v, p0), p1); break;
+      case 5: v = clamp(v); break;
       case 6: v = lht(v); break;
-      case 7: v = to_float(from_float<T>(fminf(fmaxf(v, p0), p1))) * to_float(row[tot]); break;
+      case 7: v = to_float(from_float<T>(clamp(v))) * to_float(row[tot]); break;
       case 8: v = to_float(from_float<T>(lht(v))) * to_float(row[tot]); break;
       case 9: v = to_float(from_float<T>(v - p0)) / p1; break;  // InputNormalizer.inverse_transform: x.subtract_(add).div_(mul) (normalizer.py:246-252)
       default: break;
@@ -518,6 +521,16 @@ __device__ __forceinline__ float mul_then_add(float x, float m, float a) {
 #pragma clang fp contract(off)
   const float t = x * m;
   return t + a;
+}
+
+// x * m as an fp32 VALUE, whatever is done with it next.  A product that is then converted to fp16 is otherwise selected as one
+// v_fma_mixlo_f16 (with or without fp contraction), which rounds the exact product to fp16 once; torch rounds it to fp32 first, and
+// the two differ where that fp32 value is a tie between two fp16 values (one element in 2^14).  The empty asm pins the product in a
+// VGPR, so the conversion is an instruction of its own.
+__device__ __forceinline__ float mul_f32(float x, float m) {
+  float t = x * m;
+  asm("" : "+v"(t));
+  return t;
 }
 
 // Input assembly WITH the input normaliser as a column program (scope row f4): as assemble_input_kernel, and the time /
@@ -617,7 +630,7 @@ __global__ void affine_columns_kernel(const T* __restrict__ x, int64_t ldx, T* _
     if constexpr (sizeof(T) == 4) {
       o = mul_then_add(v, mul[c], add[c]);  // two fp32 roundings, never an FMA
     } else {
-      o = to_float(from_float<T>(v * mul[c]));  // mul_ rounds to T, then add_ rounds again
+      o = to_float(from_float<T>(mul_f32(v, mul[c])));  // mul_ rounds to T (through fp32, as torch does), then add_ rounds again
       o = o + add[c];
     }
   }
