@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -85,6 +85,7 @@ SIGNATURES = {
     "anemoi_gt_chain2_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_rowchain_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_rowchain_panels_fwd": ([_p, C.c_int32, C.c_int32, C.c_int, _p], C.c_int),
+    "anemoi_gt_embed_fold_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_chain2_side_fwd": ([_p, _p, C.c_int32, C.c_int32, C.c_int32, C.c_int, _p], C.c_int),
     "anemoi_gt_cluster_chain_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_cluster_chain_workspace_bytes": ([], _i64),

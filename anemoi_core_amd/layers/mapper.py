@@ -54,6 +54,11 @@ _TAIL_PROJ = os.environ.get("ANEMOI_TAIL_PROJ", "1") != "0"
 # and are kept, keyed like the derived weights (the input's and the parameters' identity and version).  ANEMOI_ENC_DST_CACHE=0: recomputed.
 _ENC_DST_CACHE = os.environ.get("ANEMOI_ENC_DST_CACHE", "1") != "0"
 _ROW_CHAIN_GEMM_BAND = tuple(int(v) for v in os.environ.get("ANEMOI_ROW_CHAIN_GEMM_BAND", "16384:262144").split(":"))
+# Inside that band the SOURCE side of a mapper that does not update its source rows (the encoder) computes its k|v from the raw rows with
+# the composed weight (W_kv diag(gamma)) W_emb in one launch on 80-row tiles (ops.gt_embed_fold, csrc/gt_embed_fold.hip): the embedded
+# rows are read by nobody and exist in accumulators only, for their LayerNorm statistics.  ANEMOI_EMBED_FOLD=0: the GEMM pair, as before.
+# (Outside the band the row chain keeps the side: not measured there.)
+_EMBED_FOLD = os.environ.get("ANEMOI_EMBED_FOLD", "1") != "0"
 
 
 class _LocalGraphCache:
@@ -185,6 +190,28 @@ class GraphTransformerBaseMapper(BaseMapper):
         operands = self._row_chain_operands(x, lin, side)
         return None if operands is None else ops.gt_row_chain(x, *operands, want_x_out=want_x)
 
+    def _embed_fold(self, x: Tensor, lin) -> Optional[Tensor]:
+        """The source side's k|v from the raw rows in one launch with the composed weight (ops.gt_embed_fold), or None where the route does
+        not take the side: inference, 16-bit, 512 channels, a plain affine LayerNorm, projections of 512 inputs, a row count in the band where
+        the GEMM pair would run, a shape the kernel is built for."""
+        blk = self.proc
+        ln, projs = blk.layer_norm_attention_src, [blk.lin_key, blk.lin_value]
+        q_out = sum(m.out_features for m in projs)
+        if not (_EMBED_FOLD and _ROW_CHAIN_GEMM_BAND[0] < x.shape[0] < _ROW_CHAIN_GEMM_BAND[1] and self.hidden_dim == ops.CHAIN_CHANNELS
+                and plain_layer_norm(ln) and lin.in_features <= x.shape[1] and all(m.in_features == ops.CHAIN_CHANNELS for m in projs)
+                and ops.gt_embed_fold_supported(x, q_out) and inference_in(x, lin, ln, *projs)):
+            return None
+        params = [lin.weight, lin.bias, ln.weight, ln.bias] + [q for m in projs for q in (m.weight, m.bias)]
+        K = x.shape[1]
+
+        def build():
+            w = lin.weight if lin.in_features == K else torch.nn.functional.pad(lin.weight, (0, K - lin.in_features))  # (rows that carry alignment zeros)
+            wq = torch.cat([m.weight for m in projs], dim=0)
+            bq = torch.cat([m.bias if m.bias is not None else m.weight.new_zeros(m.out_features) for m in projs])
+            return ops.compose_embedding_projection(w, lin.bias, wq, bq, ln.weight, ln.bias)
+
+        return ops.gt_embed_fold(x, *blk._fused.derived(f"embed-fold:src:{K}", params, build), q_out, ln.eps)
+
     def _static_row_chain(self, x: Tensor, lin):
         """``_row_chain`` of the destination side for rows that are the same tensor every forward (inference): computed once per version of the
         rows and of the parameters.  (The entry keeps ``x`` alive: its address cannot come back as another tensor's.)"""
@@ -217,6 +244,10 @@ class GraphTransformerBaseMapper(BaseMapper):
             job.finish()
             return carrier.put(job.y, proj=job.q)
         if carrier is not None:
+            if side == "src" and not self.proc.update_src_nodes:
+                kv = self._embed_fold(x, lin)
+                if kv is not None:  # (source rows nobody reads: the stand-in of the row-chain route below)
+                    return carrier.put(x.new_empty((x.shape[0], 0)), proj=kv)
             if _ENC_DST_CACHE and side == "dst" and carrier.static_dst is x and not torch.is_grad_enabled():
                 r = self._static_row_chain(x, lin)
             else:

@@ -1271,6 +1271,68 @@ def _row_chain_args(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_featu
                          0 if x_out is None else x_out.data_ptr(), D, q_out.data_ptr(), q_out_features, N, D, int(rows_per_tile))
 
 
+class _EmbedFoldArgs(_lib.C.Structure):
+    _p, _i64, _i32, _f = _lib.C.c_void_p, _lib.C.c_int64, _lib.C.c_int32, _lib.C.c_float
+    _fields_ = [("x", _p), ("ld_x", _i64), ("in_features", _i32), ("we", _p), ("wc", _p), ("q_out_features", _i32), ("vec", _p), ("ln_eps", _f),
+                ("q_out", _p), ("ld_q", _i64), ("n_rows", _i32), ("channels", _i32)]
+
+
+EMBED_FOLD_MAX_IN = 256  # widest input row of ``gt_embed_fold`` (csrc/gt_embed_fold.hip)
+
+
+def compose_embedding_projection(w_emb: Tensor, b_emb: Optional[Tensor], w_proj: Tensor, b_proj: Optional[Tensor], gamma: Tensor,
+                                 beta: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor]:
+    """The operands of ``gt_embed_fold`` for ``Linear(w_emb, b_emb) -> LayerNorm(gamma, beta) -> Linear(w_proj, b_proj)``.  With
+    ``W_g = w_proj diag(gamma)`` the chain is ``rstd (W_c x + u - mean s) + d`` with ``W_c = W_g w_emb``, ``u = W_g b_emb``,
+    ``s = rowsum(W_g)``, ``d = w_proj beta + b_proj`` and (mean, rstd) the LayerNorm statistics of ``w_emb x + b_emb``.  Everything is
+    composed in fp32 from the given weights; ``W_c`` is rounded ONCE to ``w_emb``'s dtype.  Returns (fragment-major image of ``w_emb``,
+    fragment-major image of ``W_c``, ``vec = cat[b_emb, u, s, d]``); both images have their columns zero-padded to a multiple of 64 and
+    ``vec`` stays in fp32 (the kernel reads it as fp32: the embedding bias is exact there, ``u``, ``s``, ``d`` are not rounded to the
+    model dtype as the chain kernels' vectors are).  Plain torch: runs wherever the weights live."""
+    dt = w_emb.dtype
+    we, wp = w_emb.detach().float(), w_proj.detach().float()
+    be = we.new_zeros(we.shape[0]) if b_emb is None else b_emb.detach().float()
+    bp = wp.new_zeros(wp.shape[0]) if b_proj is None else b_proj.detach().float()
+    wg = wp * gamma.detach().float()
+    d = bp if beta is None else wp @ beta.detach().float() + bp
+    pad = (-we.shape[1]) % 64
+    wc = torch.nn.functional.pad((wg @ we).to(dt), (0, pad))
+    we16 = torch.nn.functional.pad(w_emb.detach(), (0, pad))
+    return pack_weight_frag(we16), pack_weight_frag(wc), torch.cat([be, wg @ be, wg.sum(dim=1), d]).contiguous()
+
+
+def gt_embed_fold_supported(x: Tensor, q_out: int) -> bool:
+    return (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and 0 < x.shape[1] <= EMBED_FOLD_MAX_IN
+            and x.shape[1] % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and q_out > 0 and q_out % CHAIN_CHANNELS == 0
+            and q_out <= 4 * CHAIN_CHANNELS)
+
+
+def gt_embed_fold(x: Tensor, we: Tensor, wc: Tensor, vec: Tensor, q_out_features: int, ln_eps: float) -> Optional[Tensor]:
+    """``LayerNorm(x We^T + be) Wq^T + bq`` from the raw rows ``x`` in ONE launch that never stores the embedded rows
+    (anemoi_gt_embed_fold_fwd, csrc/gt_embed_fold.hip); ``we, wc, vec``: ``compose_embedding_projection``.  None where the shape is
+    not eligible (16-bit rows of at most 256 columns, a multiple of 8; q_out a multiple of 512 up to 2048): the caller keeps the GEMM
+    pair.  Inference only (no autograd)."""
+    _dev(x, we, wc, vec)
+    if not gt_embed_fold_supported(x, q_out_features):
+        return None
+    N, K = x.shape
+    dt, D = x.dtype, CHAIN_CHANNELS
+    kp = (K + 63) // 64 * 64
+    for name, w, numel in (("we", we, D * kp), ("wc", wc, q_out_features * kp)):
+        if w.dim() != 1 or w.numel() != numel or w.dtype != dt or not w.is_contiguous():
+            raise ValueError(f"gt_embed_fold: {name} must be the contiguous fragment-major image ({numel} x {dt}) made by compose_embedding_projection")
+    if vec.dim() != 1 or vec.numel() != D + 3 * q_out_features or vec.dtype != torch.float32 or not vec.is_contiguous():
+        raise ValueError(f"gt_embed_fold: vec must be contiguous fp32 [{D + 3 * q_out_features}] = cat[be, u, s, d]")
+    q_out = torch.empty((N, q_out_features), dtype=dt, device=x.device)
+    xp, ldx = _rows(x, "x", dt)
+    a = _EmbedFoldArgs(xp, ldx, K, we.data_ptr(), wc.data_ptr(), q_out_features, vec.data_ptr(), float(ln_eps), q_out.data_ptr(), q_out_features, N, D)
+    rc = _lib.load().anemoi_gt_embed_fold_fwd(_lib.C.byref(a), _dt(x), _stream())
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "gt_embed_fold_fwd")
+    return q_out
+
+
 def gnn_edge_chain(e: Tensor, g1: Tensor, idx1: Tensor, g2: Tensor, idx2: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor, w2: Tensor,
                    b2: Tensor, ln_w: Tensor, ln_b: Optional[Tensor], eps: float) -> Tensor:
     """GraphConv's edge MLP (three Linears, gather-add form) + LayerNorm + residual in ONE launch (anemoi_gnn_edge_chain_fwd):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 18
+#define ANEMOI_HIP_ABI_VERSION 19
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -468,6 +468,28 @@ int anemoi_gt_rowchain_fwd(const anemoi_gt_rowchain_args_t* args, anemoi_dtype_t
  * WHOLE job's launch has (more than one round of panels and in_features <= 256: the pipelined kernel, else the single-panel one; the two
  * round differently), so that a row's bits do not depend on which launch computed it. */
 int anemoi_gt_rowchain_panels_fwd(const anemoi_gt_rowchain_args_t* args, int32_t first_panel, int32_t panels, anemoi_dtype_t dtype, void* stream);
+
+/* ---- the source side of a mapper from raw rows with a composed weight (csrc/gt_embed_fold.hip) ------------------------------------
+ * q_out = LayerNorm(x W_e^T + b_e) [W_a; W_b]^T + b with the embedded rows e = x W_e^T + b_e kept in accumulators (nobody reads them: the
+ * forward mapper does not update its source rows).  With W_g = [W_a; W_b] diag(gamma) and d = [W_a; W_b] beta + b:
+ *     q_out[j] = rstd_j (W_c x_j + u - mean_j s) + d,   W_c = W_g W_e,  u = W_g b_e,  s = rowsum(W_g)
+ * (mean_j, rstd_j: the plain fp32 LayerNorm statistics of e_j ROUNDED to the model dtype, as the GEMM pair forms them).  Replaces the pair
+ * anemoi_linear_stats_fwd (emb_nodes_src, layers/mapper.py:556-566) + anemoi_linear_lnfold_fwd (layer_norm_attention_src + [lin_key;
+ * lin_value], layers/block.py:981-984) on that side: e is neither written nor read back, and the projection is one GEMM over K = in_features.
+ *   we, wc: fragment-major images (ops.pack_weight_frag) of W_e [512, Kp] and of W_c [q_out_features, Kp] rounded ONCE to the model dtype,
+ *           Kp = 64 ceil(in_features / 64), columns beyond in_features zero (ops.compose_embedding_projection);
+ *   vec = [b_e (512) | u | s | d (q_out_features each)] in fp32.
+ * ANEMOI_E_UNSUPPORTED (nothing launched, the caller keeps the pair) unless: 16-bit dtype, channels 512, in_features a multiple of 8 up to
+ * 256, q_out_features a multiple of 512 up to 2048.  Any n_rows >= 0; x, q_out rows 16-byte aligned (ld multiples of 8 elements). */
+typedef struct anemoi_gt_embed_fold_args {
+  const void* x;      int64_t ld_x;       int32_t in_features;
+  const void* we;                         /* fragment-major [channels, Kp] */
+  const void* wc;     int32_t q_out_features; /* fragment-major [q_out_features, Kp] */
+  const float* vec;   float ln_eps;
+  void* q_out;        int64_t ld_q;       /* [n_rows, q_out_features] */
+  int32_t n_rows;     int32_t channels;
+} anemoi_gt_embed_fold_args_t;
+int anemoi_gt_embed_fold_fwd(const anemoi_gt_embed_fold_args_t* args, anemoi_dtype_t dtype, void* stream);
 
 /* ---- a block tail that carries a side job (csrc/gt_chain2.hip, SIDE instantiation) ------------------------------------------------
  * anemoi_gt_chain2_fwd(args) and, in the SAME launch, panels [side_first_panel, side_first_panel + side_panels) of the row chain
