@@ -637,6 +637,196 @@ __global__ void affine_columns_kernel(const T* __restrict__ x, int64_t ldx, T* _
   y[(int64_t)r * ldy + c] = from_float<T>(o);
 }
 
+// ---- imputers at the model edges (reference preprocessing/imputer.py) ---------------------------------------------------------------
+// The imputation program is a per-column table over the V input columns: kind_src int32 [V][2] = (kind, source column), value fp32 [V].
+// kind 0: the column is not imputed; 1: a NaN becomes value[c] (rounded to the data dtype on the host, so the fp32 entry is exact);
+// 2: a NaN becomes the element of column `source` at the same position (CopyImputer).  A source column is never itself imputed (the host
+// refuses such programs), so an in-place launch reads no element another thread writes.
+template <typename T>
+__device__ __forceinline__ float impute_one(float v, bool is_nan, const T* __restrict__ row, int kind, int src, float value) {
+  if (kind == 0 || !is_nan) return v;
+  return kind == 1 ? value : to_float(row[src]);
+}
+
+// Stand-alone imputer over x [batch, time, ensemble, grid, V] (element strides ld_b, ld_t, ld_e, ld_n; columns contiguous): the NaN test of
+// an element is isnan of ensemble member 0 at the same (batch, time, grid, column) - imputer.py:116-134 keeps the first member's locations -
+// and applies to every member.  A thread owns one (batch, time, grid, column) and walks the members, member 0's test read before any store,
+// so y may alias x.  mask (may be null): bool [batch, grid, V], the NaN locations of time step 0, one byte per element.
+template <typename T>
+__global__ void impute_columns_kernel(const T* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, T* y, int64_t yd_b,  // (y may be x)
+                                      int64_t yd_t, int64_t yd_e, int64_t yd_n, const int32_t* __restrict__ kind_src, const float* __restrict__ value,
+                                      uint8_t* __restrict__ mask, int B, int T_steps, int E, int N, int V) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * T_steps * N * V) return;
+  const int c = (int)(i % V);
+  const int n = (int)((i / V) % N);
+  const int t = (int)((i / ((int64_t)V * N)) % T_steps);
+  const int b = (int)(i / ((int64_t)V * N * T_steps));
+  const T* xr = x + b * ld_b + t * ld_t + (int64_t)n * ld_n;
+  T* yr = y + b * yd_b + t * yd_t + (int64_t)n * yd_n;
+  const int kind = kind_src[2 * c], src = kind_src[2 * c + 1];
+  const float val = value[c];
+  const bool is_nan = isnan(to_float(xr[c]));
+  if (mask != nullptr && t == 0) mask[((int64_t)b * N + n) * V + c] = is_nan ? 1 : 0;
+  if (kind == 0 && x == y) return;
+  for (int e = 0; e < E; ++e) {
+    const T* xe = xr + e * ld_e;
+    const T in = xe[c];
+    yr[e * yd_e + c] = (kind == 0 || !is_nan) ? in : from_float<T>(impute_one<T>(0.f, true, xe, kind, src, val));
+  }
+}
+
+// BaseImputer.inverse_transform (imputer.py:243-279): y[b, m, n, c] = NaN where mask[b, n, src_of[c]] (src_of[c] >= 0), else x[b, m, n, c];
+// x / y [batch, M, grid, V_out] contiguous rows of ldx / ldy elements, mask bool [batch, grid, ldm].  In place (y == x) only the restored
+// elements are stored.
+template <typename T>
+__global__ void restore_nan_columns_kernel(const T* x, int64_t ldx, T* y, int64_t ldy, const uint8_t* __restrict__ mask,  // (y may be x)
+                                           int64_t ldm, int n_mask_cols, const int32_t* __restrict__ src_of, int B, int M, int N, int V) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * M * N * V) return;
+  const int c = (int)(i % V);
+  const int64_t row = i / V;
+  const int n = (int)(row % N);
+  const int b = (int)(row / ((int64_t)N * M));
+  const int s = src_of[c];
+  const bool hit = s >= 0 && s < n_mask_cols && mask[((int64_t)b * N + n) * ldm + s] != 0;
+  if (hit)
+    y[row * ldy + c] = from_float<T>(__builtin_nanf(""));
+  else if (x != y)
+    y[row * ldy + c] = x[row * ldx + c];
+}
+
+// assemble_input_norm_kernel with the imputation program in front of the normaliser: every raw element is tested and imputed within its OWN
+// time step (the copy source is read from the same step and row), then x * mul + add with the same two fp32 roundings; the NaN locations of
+// step 0 go to mask bool [N][ldm] in the same pass.
+template <typename TI, typename TO>
+__global__ void assemble_input_impute_kernel(const TI* __restrict__ x, int64_t ld_t, int64_t ldx, int T_steps, int V, const int32_t* __restrict__ kind_src,
+                                             const float* __restrict__ value, uint8_t* __restrict__ mask, int64_t ldm, const float* __restrict__ mul,
+                                             const float* __restrict__ add, const TO* __restrict__ attrs, int64_t lda, int A, TO* __restrict__ out,
+                                             int64_t ldo, int W, int n_rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * W) return;
+  const int n = (int)(i / W), c = (int)(i % W);
+  float v = 0.f;
+  if (c < T_steps * V) {
+    const int t = c / V, cv = c % V;
+    const TI* xr = x + t * ld_t + (int64_t)n * ldx;
+    v = to_float(xr[cv]);
+    const bool is_nan = isnan(v);
+    if (t == 0) mask[(int64_t)n * ldm + cv] = is_nan ? 1 : 0;
+    if (is_nan) v = impute_one<TI>(v, true, xr, kind_src[2 * cv], kind_src[2 * cv + 1], value[cv]);
+    if (mul != nullptr) v = mul_then_add(v, mul[cv], add[cv]);
+  } else if (c < T_steps * V + A) {
+    v = to_float(attrs[(int64_t)n * lda + (c - T_steps * V)]);
+  }
+  out[(int64_t)n * ldo + c] = from_float<TO>(v);
+}
+
+// The same for 16-bit outputs whose width is a multiple of 8 (one 16-byte store per thread), as assemble_input_norm_vec8_kernel.  A group
+// of 8 columns that lies within step 0 owns 8 consecutive mask bytes: they leave as two 4-byte stores where the mask rows allow it
+// (ldm % 4 == 0, base 4-byte aligned - then n * ldm + c0 is a multiple of 4), else byte by byte.  The program entry of a column is one
+// 8-byte load; its value is read only where a NaN is replaced.
+template <typename TI, typename TO>
+__global__ void assemble_input_impute_vec8_kernel(const TI* __restrict__ x, int64_t ld_t, int64_t ldx, int T_steps, int V,
+                                                  const int32_t* __restrict__ kind_src, const float* __restrict__ value, uint8_t* __restrict__ mask,
+                                                  int64_t ldm, const float* __restrict__ mul, const float* __restrict__ add,
+                                                  const TO* __restrict__ attrs, int64_t lda, int A, TO* __restrict__ out, int64_t ldo, int W, int n_rows) {
+  const int per_row = W >> 3;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * per_row) return;
+  const int n = (int)(i / per_row), c0 = (int)(i % per_row) << 3;
+  const bool packed = c0 + 8 <= V && (ldm & 3) == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  uint32_t bits[2] = {0u, 0u};
+  Vec<TO, 8> o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = c0 + j;
+    float v = 0.f;
+    if (c < T_steps * V) {
+      const int t = c / V, cv = c % V;
+      const TI* xr = x + t * ld_t + (int64_t)n * ldx;
+      v = to_float(xr[cv]);
+      const bool is_nan = isnan(v);
+      if (packed)
+        bits[j >> 2] |= (is_nan ? 1u : 0u) << (8 * (j & 3));
+      else if (t == 0)
+        mask[(int64_t)n * ldm + cv] = is_nan ? 1 : 0;
+      if (is_nan) {
+        const int2 ks = reinterpret_cast<const int2*>(kind_src)[cv];
+        if (ks.x != 0) v = ks.x == 1 ? value[cv] : to_float(xr[ks.y]);
+      }
+      if (mul != nullptr) v = mul_then_add(v, mul[cv], add[cv]);
+    } else if (c < T_steps * V + A) {
+      v = to_float(attrs[(int64_t)n * lda + (c - T_steps * V)]);
+    }
+    o.v[j] = from_float<TO>(v);
+  }
+  if (packed) {
+    uint32_t* m = reinterpret_cast<uint32_t*>(mask + (int64_t)n * ldm + c0);
+    m[0] = bits[0];
+    m[1] = bits[1];
+  }
+  *reinterpret_cast<Vec<TO, 8>*>(out + (int64_t)n * ldo + c0) = o;
+}
+
+// assemble_output_norm_kernel whose RAW skip is imputed by the same program before it is normalised.
+template <typename TM, typename TS>
+__global__ void assemble_output_impute_kernel(const TM* __restrict__ x_out, int64_t ldx, const TS* __restrict__ skip, int64_t lds,
+                                              const int32_t* __restrict__ col_map, const int32_t* __restrict__ kind_src, const float* __restrict__ value,
+                                              const float* __restrict__ mul, const float* __restrict__ add, TS* __restrict__ out, int64_t ldo, int n_rows,
+                                              int n_cols) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * n_cols) return;
+  const int n = (int)(i / n_cols), v = (int)(i % n_cols);
+  float val = to_float(from_float<TS>(to_float(x_out[(int64_t)n * ldx + v])));
+  const int m = col_map[v];
+  if (m >= 0) {
+    const TS* sr = skip + (int64_t)n * lds;
+    float sk = to_float(sr[m]);
+    if (isnan(sk)) sk = impute_one<TS>(sk, true, sr, kind_src[2 * m], kind_src[2 * m + 1], value[m]);
+    if (mul != nullptr) sk = to_float(from_float<TS>(mul_then_add(sk, mul[m], add[m])));
+    val += sk;
+  }
+  out[(int64_t)n * ldo + v] = from_float<TS>(val);
+}
+
+// bound_columns_kernel with one more kind, 10: NaN where mask[r, tot] (BaseImputer.inverse_transform as an op of the output column program,
+// appended after the op-9 de-normalisations; `tot` is the mask column).  The kinds 1..9 are those of bound_columns_kernel, statement for
+// statement; that kernel is kept as it is for the programs without a mask.
+template <typename T>
+__global__ void bound_columns_mask_kernel(T* __restrict__ x, int64_t ldx, int n_rows, const int32_t* __restrict__ ops, const float* __restrict__ params,
+                                          int n_ops, const uint8_t* __restrict__ mask, int64_t ldm, int n_mask_cols) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rows) return;
+  T* row = x + (int64_t)r * ldx;
+  for (int i = 0; i < n_ops; ++i) {
+    const int kind = ops[4 * i], col = ops[4 * i + 1], tot = ops[4 * i + 2];
+    const float p0 = params[2 * i], p1 = params[2 * i + 1];
+    float v = to_float(row[col]);
+    auto leaky = [](float t) { return t > 0.f ? t : 0.01f * t; };
+    auto lht = [&](float t) { return t < p0 ? p0 + 0.01f * (t - p0) : (t > p1 ? p1 + 0.01f * (t - p1) : t); };
+    auto relu = [](float t) { return t < 0.f ? 0.f : t; };
+    auto clamp = [&](float t) { return t < p0 ? p0 : (t > p1 ? p1 : t); };
+    switch (kind) {
+      case 1: v = relu(v); break;
+      case 2: v = leaky(v); break;
+      case 3: v = relu(v - p0) + p0; break;
+      case 4: v = leaky(v - p0) + p0; break;
+      case 5: v = clamp(v); break;
+      case 6: v = lht(v); break;
+      case 7: v = to_float(from_float<T>(clamp(v))) * to_float(row[tot]); break;
+      case 8: v = to_float(from_float<T>(lht(v))) * to_float(row[tot]); break;
+      case 9: v = to_float(from_float<T>(v - p0)) / p1; break;
+      case 10:
+        if ((unsigned)tot >= (unsigned)n_mask_cols || mask[(int64_t)r * ldm + tot] == 0) continue;  // every other bit of the row stays
+        v = __builtin_nanf("");
+        break;
+      default: break;
+    }
+    row[col] = from_float<T>(v);
+  }
+}
+
 template <typename T>
 static int layernorm_launch(const void* x, int64_t ldx, const void* gamma, const void* beta, const void* residual,
                             int64_t ldr, void* y, int64_t ldy, int n_rows, int D, float eps, hipStream_t st) {
@@ -986,5 +1176,121 @@ extern "C" int anemoi_affine_columns(const void* x, int64_t ldx, void* y, int64_
     using T = typename decltype(t)::type;
     hipLaunchKernelGGL((affine_columns_kernel<T>), grid, block, 0, st, (const T*)x, ldx, (T*)y, ldy, col_mul, col_add, inverse, n_rows, V);
     return check_launch("affine_columns_kernel");
+  });
+}
+
+// ---- imputers (see the kernels above) ------------------------------------------------------------------------------------------------------
+extern "C" int anemoi_impute_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, void* y, int64_t yd_b, int64_t yd_t,
+                                     int64_t yd_e, int64_t yd_n, const int32_t* kind_src, const float* value, void* mask, int32_t B, int32_t T_steps,
+                                     int32_t E, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(B >= 0 && T_steps >= 0 && E >= 0 && N >= 0 && V > 0 && ld_n >= V && yd_n >= V, "impute_columns: bad sizes");
+  const int64_t n = (int64_t)B * T_steps * N * V;
+  if (n == 0 || E == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && y && kind_src && value, "impute_columns: null pointer");
+  ANEMOI_REQUIRE((n + 255) / 256 <= 0x7fffffffLL, "impute_columns: too many elements for one launch");
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((impute_columns_kernel<T>), grid, block, 0, st, (const T*)x, ld_b, ld_t, ld_e, ld_n, (T*)y, yd_b, yd_t, yd_e, yd_n, kind_src,
+                       value, (uint8_t*)mask, B, T_steps, E, N, V);
+    return check_launch("impute_columns_kernel");
+  });
+}
+
+extern "C" int anemoi_restore_nan_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const void* mask, int64_t ldm, int32_t n_mask_cols,
+                                          const int32_t* src_of, int32_t B, int32_t M, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(B >= 0 && M >= 0 && N >= 0 && V > 0 && ldx >= V && ldy >= V && n_mask_cols > 0 && ldm >= n_mask_cols, "restore_nan_columns: bad sizes");
+  const int64_t n = (int64_t)B * M * N * V;
+  if (n == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && y && mask && src_of, "restore_nan_columns: null pointer");
+  ANEMOI_REQUIRE((n + 255) / 256 <= 0x7fffffffLL, "restore_nan_columns: too many elements for one launch");
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((restore_nan_columns_kernel<T>), grid, block, 0, st, (const T*)x, ldx, (T*)y, ldy, (const uint8_t*)mask, ldm, n_mask_cols, src_of, B, M, N, V);
+    return check_launch("restore_nan_columns_kernel");
+  });
+}
+
+extern "C" int anemoi_assemble_input_impute(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
+                                            const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const float* col_mul,
+                                            const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo, int32_t W,
+                                            int32_t n_rows, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && T_steps > 0 && V > 0 && A >= 0 && W >= T_steps * V + A && ldo >= W && ldx >= V && (A == 0 || lda >= A) && ldm >= V,
+                 "assemble_input_impute: bad sizes");
+  ANEMOI_REQUIRE((col_mul == nullptr) == (col_add == nullptr), "assemble_input_impute: col_mul and col_add go together");
+  if (n_rows == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && out && kind_src && value && mask && (A == 0 || attrs), "assemble_input_impute: null pointer");
+  ANEMOI_REQUIRE(x_dtype == dtype || x_dtype == ANEMOI_F32, "assemble_input_impute: the input is in the model dtype or fp32");
+  hipStream_t st = as_stream(stream);
+  uint8_t* mk = (uint8_t*)mask;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using TO = typename decltype(t)::type;
+    const bool wide_in = x_dtype == ANEMOI_F32;  // TI = float, else TI = TO
+    if constexpr (sizeof(TO) == 2) {
+      if (W % 8 == 0 && ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        const int64_t n8 = (int64_t)n_rows * (W / 8);
+        const dim3 grid8((unsigned)((n8 + 255) / 256)), block8(256);
+        if (wide_in)
+          hipLaunchKernelGGL((assemble_input_impute_vec8_kernel<float, TO>), grid8, block8, 0, st, (const float*)x, ld_t, ldx, T_steps, V, kind_src,
+                             value, mk, ldm, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        else
+          hipLaunchKernelGGL((assemble_input_impute_vec8_kernel<TO, TO>), grid8, block8, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, kind_src, value,
+                             mk, ldm, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        return check_launch("assemble_input_impute_vec8_kernel");
+      }
+    }
+    const int64_t n = (int64_t)n_rows * W;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (wide_in)
+      hipLaunchKernelGGL((assemble_input_impute_kernel<float, TO>), grid, block, 0, st, (const float*)x, ld_t, ldx, T_steps, V, kind_src, value, mk, ldm,
+                         col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    else
+      hipLaunchKernelGGL((assemble_input_impute_kernel<TO, TO>), grid, block, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, kind_src, value, mk, ldm,
+                         col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    return check_launch("assemble_input_impute_kernel");
+  });
+}
+
+extern "C" int anemoi_assemble_output_impute(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
+                                             const int32_t* col_map, const int32_t* kind_src, const float* value, const float* col_mul,
+                                             const float* col_add, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols, anemoi_dtype_t dtype,
+                                             void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && n_cols > 0 && ldx >= n_cols && ldo >= n_cols, "assemble_output_impute: bad sizes");
+  ANEMOI_REQUIRE((col_mul == nullptr) == (col_add == nullptr), "assemble_output_impute: col_mul and col_add go together");
+  if (n_rows == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x_out && x_skip && col_map && out && kind_src && value, "assemble_output_impute: null pointer");
+  ANEMOI_REQUIRE(model_dtype == dtype || dtype == ANEMOI_F32, "assemble_output_impute: the output is in the model dtype or fp32");
+  const int64_t n = (int64_t)n_rows * n_cols;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(model_dtype, [&](auto t) {
+    using TM = typename decltype(t)::type;
+    if (dtype == ANEMOI_F32)  // TS = float, else TS = TM
+      hipLaunchKernelGGL((assemble_output_impute_kernel<TM, float>), grid, block, 0, st, (const TM*)x_out, ldx, (const float*)x_skip, lds, col_map,
+                         kind_src, value, col_mul, col_add, (float*)out, ldo, n_rows, n_cols);
+    else
+      hipLaunchKernelGGL((assemble_output_impute_kernel<TM, TM>), grid, block, 0, st, (const TM*)x_out, ldx, (const TM*)x_skip, lds, col_map, kind_src,
+                         value, col_mul, col_add, (TM*)out, ldo, n_rows, n_cols);
+    return check_launch("assemble_output_impute_kernel");
+  });
+}
+
+extern "C" int anemoi_bound_columns_mask(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
+                                         const void* mask, int64_t ldm, int32_t n_mask_cols, int32_t n_nan_ops, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && n_cols > 0 && ldx >= n_cols && n_ops >= 0 && n_nan_ops >= 0 && n_nan_ops <= n_ops, "bound_columns_mask: bad sizes");
+  ANEMOI_REQUIRE(n_nan_ops == 0 || mask != nullptr, "bound_columns_mask: the program has ops of kind 10 (NaN where mask) but no mask was given");
+  if (mask == nullptr) return anemoi_bound_columns(x, ldx, n_rows, n_cols, ops, params, n_ops, dtype, stream);
+  ANEMOI_REQUIRE(n_mask_cols > 0 && ldm >= n_mask_cols, "bound_columns_mask: bad mask sizes");
+  if (n_rows == 0 || n_ops == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && ops && params, "bound_columns_mask: null pointer");
+  const dim3 grid((n_rows + 255) / 256), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bound_columns_mask_kernel<T>), grid, block, 0, st, (T*)x, ldx, n_rows, ops, params, n_ops, (const uint8_t*)mask, ldm, n_mask_cols);
+    return check_launch("bound_columns_mask_kernel");
   });
 }

@@ -5,7 +5,7 @@ tensor (``ops.bound_columns_``) instead of one indexed read-modify-write per bou
 program is evaluated with differentiable torch ops (the model edge is not a hot spot of the backward pass)."""
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor, nn
@@ -46,7 +46,27 @@ def apply_program_torch(x: Tensor, program: list) -> Tensor:
     return torch.stack(cols, dim=-1)
 
 
+NAN_WHERE_MASK = 10  # (10, dst column, mask column, 0, 0): NaN where mask[n, src] - the imputer's inverse transform; needs a mask
+
+
 def program_tables(program: list, device) -> tuple[Tensor, Tensor]:
+    if any(op[0] == NAN_WHERE_MASK for op in program):
+        raise ValueError("program_tables: the program has ops of kind 10 (NaN where mask), which need a mask: build it with masked_program_tables")
+    return _tables(program, device)
+
+
+class MaskedProgramTables(NamedTuple):
+    """Device tables of a column program that may hold ops of kind 10, with their count (``ops.bound_columns_masked_``)."""
+    ops: Tensor
+    params: Tensor
+    n_nan_ops: int
+
+
+def masked_program_tables(program: list, device) -> MaskedProgramTables:
+    return MaskedProgramTables(*_tables(program, device), sum(op[0] == NAN_WHERE_MASK for op in program))
+
+
+def _tables(program: list, device) -> tuple[Tensor, Tensor]:
     ops_t = torch.tensor([[k, c, t, 0] for k, c, t, _, _ in program], dtype=torch.int32, device=device).reshape(-1, 4)
     par_t = torch.tensor([[a, b] for _, _, _, a, b in program], dtype=torch.float32, device=device).reshape(-1, 2)
     return ops_t, par_t

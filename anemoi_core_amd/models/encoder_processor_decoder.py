@@ -12,7 +12,7 @@ eight classes of layers/bounding.py, run as one in-place column program.
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor, nn
@@ -40,6 +40,16 @@ from ..utils.config import DotDict, instantiate
 
 _REF_PREFIX = "anemoi.models.layers."
 _OUR_PREFIX = "anemoi_core_amd.layers."
+
+
+class _EdgeState(NamedTuple):
+    """What one dataset's input assembly hands to its output assembly within a forward."""
+    x_skip: Tensor
+    skip_is_raw: bool
+    norm_in: Optional[nn.Module]
+    norm_out: Optional[nn.Module]
+    imputer: Optional[nn.Module]
+    nan_mask: Optional[Tensor]  # bool [N, V] when the imputation program ran inside the assembly kernel, else None
 
 
 def _retarget(cfg) -> dict:
@@ -221,24 +231,41 @@ class AnemoiModelEncProcDec(nn.Module):
         return out
 
     # -- glue (encoder_processor_decoder.py:98-163) ---------------------------------------------------------
-    def _assemble_input(self, x: Tensor, batch_size: int, shard_sizes, group, ds: str, norm=None):
-        """``norm``: the dataset's InputNormalizer when ``predict_step`` fuses it (x is then the RAW batch).  Returns
-        (x_data_latent, x_skip, skip_is_raw)."""
+    def _assemble_input(self, x: Tensor, batch_size: int, shard_sizes, group, ds: str, norm=None, imputer=None):
+        """``norm``: the dataset's InputNormalizer when ``predict_step`` fuses it (x is then the RAW batch); ``imputer``: the imputer that
+        precedes it in the chain.  Returns (x_data_latent, x_skip, skip_is_raw, nan_mask): nan_mask bool [N, V], the NaN locations of the
+        first step, when the imputation program ran inside the assembly kernel (the skip is then raw AND not imputed), else None."""
         node_attr = self.node_attributes(ds, batch_size=batch_size)
         if shard_sizes is not None:
             node_attr = shard_tensor(node_attr, 0, shard_sizes, group)
         B, T, E, N, V = x.shape
         fusable = (_FUSED_INPUT and B == 1 and E == 1 and x.is_cuda and x.stride(4) == 1
                    and not (torch.is_grad_enabled() and (x.requires_grad or node_attr.requires_grad)))
+        if imputer is not None:
+            # the program rides in the assembly kernels for one sample, one output step, the step skip and a whole grid; everything else
+            # (a batch, several output steps, a truncated residual - whose down projection would need the program on every gathered value -,
+            # a sharded grid, training) imputes in ONE stand-alone pass first and goes on as if the chain were the normaliser alone
+            if not (fusable and self.n_step_output == 1 and not self._truncated[ds] and shard_sizes is None and not torch.is_grad_enabled()
+                    and (node_attr.dtype == x.dtype or x.dtype == torch.float32)):
+                x, imputer = imputer.transform(x, in_place=False), None
+            else:
+                width = T * V + node_attr.shape[1]
+                if node_attr.dtype != torch.float32 and self._prepad(ds):
+                    width += (-width) % 64 if (-width) % 64 <= 16 and _PAD64 else (-width) % 8
+                nan_mask = torch.empty((N, V), dtype=torch.bool, device=x.device)
+                mul, add = norm.column_program(V)
+                out = ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype,
+                                         impute=imputer.device_program(V, x.dtype, x.device), nan_mask=nan_mask)
+                return out, x[:, self._skip_step, ...], True, nan_mask
         if fusable and (node_attr.dtype == x.dtype or (norm is not None and x.dtype == torch.float32)):
             # inference, one member: permute + cat + alignment zeros (+ the input normaliser as a column program) in ONE kernel
             width = T * V + node_attr.shape[1]
             if node_attr.dtype != torch.float32 and self._prepad(ds):
                 width += (-width) % 64 if (-width) % 64 <= 16 and _PAD64 else (-width) % 8
             if norm is None:
-                return ops.assemble_input(x[0, :, 0], node_attr, width), x[:, self._skip_step, ...], False
+                return ops.assemble_input(x[0, :, 0], node_attr, width), x[:, self._skip_step, ...], False, None
             mul, add = norm.column_program(V)
-            return ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype), x[:, self._skip_step, ...], True
+            return ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype), x[:, self._skip_step, ...], True, None
         if norm is not None:  # not fusable: the normaliser's own kernel, then the generic path
             x = norm.transform(x, in_place=False).to(node_attr.dtype)
         x_skip = x[:, self._skip_step, ...]  # SkipConnection (layers/residual.py:60-81): last input step
@@ -253,7 +280,7 @@ class AnemoiModelEncProcDec(nn.Module):
             if self._pad_zeros is None or self._pad_zeros[0] != key:
                 self._pad_zeros = (key, torch.zeros((flat.shape[0], pad), dtype=flat.dtype, device=flat.device))
             cols.append(self._pad_zeros[1])
-        return torch.cat(cols, dim=-1), x_skip, False
+        return torch.cat(cols, dim=-1), x_skip, False, None
 
     def _prepad(self, ds: str) -> bool:
         """The GraphTransformer mappers embed their inputs through PaddedLinear, which accepts rows that already carry the
@@ -275,21 +302,25 @@ class AnemoiModelEncProcDec(nn.Module):
         return self._hidden_padded[1]
 
     def _assemble_output(self, x_out: Tensor, x_skip: Tensor, batch_size: int, ensemble_size: int, dtype, ds: str, norm=None,
-                         skip_is_raw: bool = False, denorm=None, compact: bool = False) -> Tensor:
+                         skip_is_raw: bool = False, denorm=None, compact: bool = False, imputer=None, nan_mask: Optional[Tensor] = None) -> Tensor:
         """``norm`` / ``skip_is_raw``: x_skip is the RAW input and is normalised inside the residual kernel; ``denorm``: the
         output InputNormalizer whose inverse transform is appended to the column program of the boundings; ``compact``: x_skip holds the
-        prognostic columns only, in their order (the truncated residual)."""
+        prognostic columns only, in their order (the truncated residual); ``imputer`` / ``nan_mask`` (from ``_assemble_input``): the raw skip
+        is imputed by the imputer's program as well, and its NaN restoration (op 10, reading nan_mask) closes the column program."""
         N = x_out.shape[0] // (batch_size * ensemble_size)
         in_idx, out_idx = getattr(self, f"_in_idx_{ds}"), getattr(self, f"_out_idx_{ds}")
         col_map = getattr(self, f"_col_map_c_{ds}" if compact else f"_col_map_{ds}")
         fusable = (col_map is not None and batch_size == 1 and ensemble_size == 1 and self.n_step_output == 1 and x_out.is_cuda
                    and not (torch.is_grad_enabled() and (x_out.requires_grad or x_skip.requires_grad)))
         fused_norm = fusable and skip_is_raw and x_skip.dtype == dtype and dtype in (x_out.dtype, torch.float32)
-        if skip_is_raw and not fused_norm:  # every path but the fused-normalisation kernel takes a NORMALISED skip
-            x_skip, skip_is_raw = norm.transform(x_skip, in_place=False), False
+        program = None if nan_mask is None else imputer.device_program(x_skip.shape[-1], x_skip.dtype, x_skip.device)
+        if skip_is_raw and not fused_norm:  # every path but the fused-normalisation kernel takes a NORMALISED (and imputed) skip
+            if program is not None:
+                x_skip = ops.impute_columns(x_skip.unsqueeze(1), program).squeeze(1)
+            x_skip, skip_is_raw = norm.transform(x_skip, in_place=program is not None), False
         if fused_norm:
             mul, add = norm.column_program(x_skip.shape[-1])
-            x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add).view(1, 1, 1, N, -1)
+            x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add, impute=program).view(1, 1, 1, N, -1)
         elif fusable and x_out.dtype == dtype and x_skip.dtype == dtype:
             # one kernel for cast / residual on the prognostic columns (instead of clone + index_select + index_add_)
             x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map).view(1, 1, 1, N, -1)
@@ -298,31 +329,41 @@ class AnemoiModelEncProcDec(nn.Module):
             # SkipConnection._expand_time (layers/residual.py:53-57): the skip is repeated over the output steps
             skip = x_skip.unsqueeze(1).expand(-1, self.n_step_output, -1, -1, -1)
             x_out.index_add_(-1, out_idx, (skip if compact else skip.index_select(-1, in_idx)).to(dtype))
-        if len(self.boundings[ds]) or denorm is not None:
+        nan_ops = [] if nan_mask is None else imputer.inverse_program(x_out.shape[-1])
+        if len(self.boundings[ds]) or denorm is not None or nan_ops:
             # all configured boundings (configuration order) and, fused, the output de-normalisation as ONE in-place column program
-            from ..layers.bounding import apply_program_torch, program_tables
+            from ..layers.bounding import apply_program_torch, masked_program_tables, program_tables
 
             if torch.is_grad_enabled() and x_out.requires_grad:
                 x_out = apply_program_torch(x_out, [op for b in self.boundings[ds] for op in b.program()])
                 if denorm is not None:
                     x_out = denorm.inverse_transform(x_out, in_place=False)
+                if nan_ops:
+                    x_out = imputer.inverse_transform(x_out, in_place=False)
             else:
                 # the column program and its device tables are built ONCE per (dataset, device, normaliser state): program() of
                 # the normalised boundings reads a registered buffer (.tolist() = a device->host sync, illegal under hipGraph capture)
                 key = (ds, str(x_out.device), None if denorm is None else (id(denorm), denorm._norm_mul._version, denorm._norm_add._version))
+                if nan_ops:
+                    key += (id(imputer),)
                 if key not in self._bound_tables:
                     prog = [op for b in self.boundings[ds] for op in b.program()]
                     if denorm is not None:
                         prog += denorm.inverse_program(x_out.shape[-1])
-                    self._bound_tables[key] = program_tables(prog, x_out.device)
-                ops.bound_columns_(x_out, *self._bound_tables[key])
+                    # (NaN restoration last: it follows the de-normalisation)
+                    self._bound_tables[key] = masked_program_tables(prog + nan_ops, x_out.device) if nan_ops else program_tables(prog, x_out.device)
+                tables = self._bound_tables[key]
+                if nan_ops:
+                    ops.bound_columns_(x_out, tables.ops, tables.params, nan_mask=nan_mask, n_nan_ops=tables.n_nan_ops)
+                else:
+                    ops.bound_columns_(x_out, *tables)
         return x_out
 
     @scoped_forward
     def forward(self, x: dict, *, model_comm_group=None, grid_shard_sizes: Optional[dict] = None, _fused_norm: Optional[dict] = None,
                 **kwargs) -> dict:
-        """``_fused_norm`` (set by ``predict_step`` only): {dataset: (input normaliser, output normaliser)} - x is then the RAW
-        batch and the output is de-normalised."""
+        """``_fused_norm`` (set by ``predict_step`` only): {dataset: (input normaliser, output normaliser[, imputer])} - x is then the RAW
+        batch and the output is de-normalised; with an imputer, NaN of its variables is imputed on the way in and restored on the way out."""
         names = list(x.keys())
         batch_size = x[names[0]].shape[0]
         ensemble_size = x[names[0]].shape[2]
@@ -355,11 +396,15 @@ class AnemoiModelEncProcDec(nn.Module):
             carrier.static_dst = x_hidden_latent  # (inference: the cached static attribute tensor - the encoder may keep what it computes from it)
         for ds in names:
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
-            norm_in, norm_out = (_fused_norm or {}).get(ds, (None, None))
-            x_data_latent, x_skip, raw = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds, norm=norm_in)
+            norm_in, norm_out, *rest = (_fused_norm or {}).get(ds, (None, None))
+            imputer = rest[0] if rest else None
+            x_data_latent, x_skip, raw, nan_mask = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds, norm=norm_in,
+                                                                        imputer=imputer)
+            if nan_mask is not None:  # the nan_locations the imputer's own transform would have left; no loss mask at inference
+                imputer.record_nan_locations(nan_mask.unsqueeze(0), nan_mask.shape[-1], loss_mask=False)
             if self._truncated[ds]:  # once per dataset and forward: down (columns, normaliser), up; the skip is then normalised
                 x_skip, raw = self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data), False
-            skips[ds], data_shards[ds] = (x_skip, raw, norm_in, norm_out), shard_sizes_data
+            skips[ds], data_shards[ds] = _EdgeState(x_skip, raw, norm_in, norm_out, imputer, nan_mask), shard_sizes_data
             if (_SIDE_JOB and carrier is not None and model_comm_group is None and not torch.is_grad_enabled()
                     and isinstance(self.decoder[ds], GraphTransformerBackwardMapper)):
                 side_job = carrier.side_job = self.decoder[ds].destination_side_job(x_data_latent, _SIDE_PANELS_PER_RIDER)
@@ -397,23 +442,30 @@ class AnemoiModelEncProcDec(nn.Module):
                                      edge_index=ei, model_comm_group=model_comm_group, keep_x_dst_sharded=in_out_sharded[ds], **chain_kw)
             if side_job is not None:
                 LAST_SIDE_JOB_PANELS = (side_job.hosted, side_job.n_panels - side_job.hosted)
-            x_skip, raw, norm_in, norm_out = skips[ds]
-            out[ds] = self._assemble_output(x_out, x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=norm_in, skip_is_raw=raw,
-                                            denorm=norm_out, compact=self._truncated[ds])
+            e = skips[ds]
+            out[ds] = self._assemble_output(x_out, e.x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=e.norm_in, skip_is_raw=e.skip_is_raw,
+                                            denorm=e.norm_out, compact=self._truncated[ds], imputer=e.imputer, nan_mask=e.nan_mask)
+            if e.imputer is not None and e.nan_mask is None:  # imputed by the stand-alone kernel on the way in: restored by its counterpart
+                out[ds] = e.imputer.inverse_transform(out[ds].contiguous(), in_place=True)  # (several output steps: a permuted clone)
         return out
 
     # -- predict_step (models/base.py:303-391) ----------------------------------------------------------------------------
     @staticmethod
-    def _sole_normalizer(procs, inverse: bool):
-        """The InputNormalizer of a ``Processors`` chain that consists of nothing else (what the model edge can fuse), else None."""
-        from ..preprocessing import InputNormalizer, Processors
+    def _edge_chain(procs, inverse: bool):
+        """(imputer or None, InputNormalizer) of a ``Processors`` chain the model edge can fuse - the normaliser alone, or one imputer followed
+        by the normaliser (the members of an inverse chain are stored in the same order and applied last to first) - else None: two
+        imputers, an imputer after the normaliser or a member of any other type stay opaque processors."""
+        from ..preprocessing import BaseImputer, InputNormalizer, Processors
 
         if isinstance(procs, InputNormalizer):
-            return procs
-        if isinstance(procs, Processors) and procs.inverse == inverse and len(procs.processors) == 1:
-            only = next(iter(procs.processors.values()))
-            if isinstance(only, InputNormalizer):
-                return only
+            return None, procs
+        if not isinstance(procs, Processors) or procs.inverse != inverse:
+            return None
+        members = list(procs.processors.values())
+        if len(members) == 1 and isinstance(members[0], InputNormalizer):
+            return None, members[0]
+        if len(members) == 2 and isinstance(members[0], BaseImputer) and isinstance(members[1], InputNormalizer):
+            return members[0], members[1]
         return None
 
     def predict_step(self, batch: dict, pre_processors, post_processors, n_step_input: int, model_comm_group=None,
@@ -421,7 +473,10 @@ class AnemoiModelEncProcDec(nn.Module):
         """Pre-process, forward, post-process (reference models/base.py:303-391): ``batch[ds]`` is [batch, time, grid, vars] of
         RAW data.  When a dataset's pre- / post-processor chains are just the input normaliser, it is fused into the model
         edges: the transform runs inside the input assembly kernel (and on the skip connection inside the residual kernel),
-        the inverse inside the output column program - no pass of its own over the data."""
+        the inverse inside the output column program - no pass of its own over the data.  The chain [one imputer, input normaliser]
+        (and the inverse chain over the same two modules) is fused likewise: the imputation program runs in the same kernels, the NaN mask
+        of the first step is written by the input assembly and read by the output column program, and the imputer's ``nan_locations`` is
+        what its own transform would have left.  Any other chain goes through the modules."""
         from ..distributed.primitives import gather_tensor
 
         with torch.no_grad():
@@ -436,12 +491,15 @@ class AnemoiModelEncProcDec(nn.Module):
                 x = {ds: shard_tensor(x[ds], -2, grid_shard_sizes[ds], model_comm_group) for ds in names}
             fused = {}
             for ds in names:
-                pre, post = self._sole_normalizer(pre_processors[ds], False), self._sole_normalizer(post_processors[ds], True)
-                if pre is not None and post is not None and x[ds].is_cuda:
-                    fused[ds] = (pre, post)
+                pre, post = self._edge_chain(pre_processors[ds], False), self._edge_chain(post_processors[ds], True)
+                if pre is not None and post is not None and pre[0] is post[0] and x[ds].is_cuda:
+                    imputer, pre, post = pre[0], pre[1], post[1]
+                    fused[ds] = (pre, post) if imputer is None else (pre, post, imputer)
                     check = getattr(pre_processors[ds], "check_first_batch", None)
                     if check is not None and getattr(pre_processors[ds], "_awaiting_first_batch", False):
-                        check(pre.transform(x[ds], in_place=False))  # the chain's one-off NaN check survives the fusion
+                        # the chain's one-off NaN check survives the fusion: the member modules run once, on a copy
+                        first = x[ds] if imputer is None else imputer.transform(x[ds], in_place=False)
+                        check(pre.transform(first, in_place=False))
                 else:
                     x[ds] = pre_processors[ds](x[ds], in_place=False)
             y_hat = self.forward(x, model_comm_group=model_comm_group, grid_shard_sizes=grid_shard_sizes, _fused_norm=fused, **kwargs)

@@ -1448,11 +1448,87 @@ def glu_backward(gate_value: Tensor, d_out: Tensor, kind: str) -> Tensor:
     return out
 
 
+class ImputeProgram(NamedTuple):
+    """The imputation program on the device (include/anemoi_hip.h): ``kind_src`` int32 [V, 2] = (kind, source column) with kind 0 none,
+    1 constant, 2 copy; ``value`` fp32 [V], each entry already rounded to the data dtype."""
+    kind_src: Tensor
+    value: Tensor
+
+
+def impute_program(kinds, values, sources, device) -> ImputeProgram:
+    """Build the device tables from per-column host lists; a copy source that is itself imputed is refused (the kernels read sources
+    raw, the reference's sequential fill would read the filled value)."""
+    V = len(kinds)
+    for c in range(V):
+        if kinds[c] not in (0, 1, 2):
+            raise ValueError(f"impute_program: column {c}: kind {kinds[c]} is not 0 (none), 1 (constant) or 2 (copy)")
+        if kinds[c] == 2 and not (0 <= sources[c] < V and kinds[sources[c]] == 0):
+            raise NotImplementedError(f"impute_program: column {c} copies column {sources[c]}, which is out of range or itself imputed")
+    ks = torch.tensor([[int(k), int(s) if k == 2 else 0] for k, s in zip(kinds, sources)], dtype=torch.int32).reshape(V, 2)
+    return ImputeProgram(ks.to(device), torch.tensor([float(v) for v in values], dtype=torch.float32).to(device))
+
+
+def _impute_ptrs(impute: ImputeProgram, V: int, what: str) -> tuple[int, int]:
+    ks, val = impute
+    if ks.shape != (V, 2) or ks.dtype != torch.int32 or not ks.is_contiguous():
+        raise ValueError(f"{what}: impute.kind_src must be contiguous int32 [{V}, 2], got {tuple(ks.shape)} {ks.dtype}")
+    return ks.data_ptr(), _vec(val, "impute.value", V, torch.float32)
+
+
+def _bool_mask(mask: Tensor, shape: tuple, what: str) -> Tensor:
+    if mask.dtype != torch.bool or tuple(mask.shape) != tuple(shape) or not mask.is_contiguous():
+        raise ValueError(f"{what}: the mask must be a contiguous torch.bool tensor of shape {tuple(shape)}, got {tuple(mask.shape)} {mask.dtype}")
+    return mask
+
+
+def impute_columns(x: Tensor, impute: ImputeProgram, out: Optional[Tensor] = None, mask: Optional[Tensor] = None) -> Tensor:
+    """BaseImputer.transform as one kernel: x [batch, time, grid, V] or [batch, time, ensemble, grid, V] (any strides, columns contiguous);
+    a NaN of ensemble member 0 is replaced, in EVERY member, by what the program says for its column; each time step has its own NaN
+    locations.  ``out``: x itself (in place) or a tensor of x's shape (default: a new one).  ``mask``: bool [batch, grid, V], receives the NaN
+    locations of time step 0, member 0, all columns."""
+    _dev(x, impute.kind_src, impute.value, out, mask)
+    if x.dim() not in (4, 5) or x.stride(-1) != 1:
+        raise ValueError(f"impute_columns: x must be [batch, time, (ensemble,) grid, vars] with contiguous variables, got {tuple(x.shape)}")
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype or y.stride(-1) != 1:
+        raise ValueError("impute_columns: out must match x")
+    x5, y5 = (x.unsqueeze(2), y.unsqueeze(2)) if x.dim() == 4 else (x, y)
+    B, T, E, N, V = x5.shape
+    kp, vp = _impute_ptrs(impute, V, "impute_columns")
+    mp = 0 if mask is None else _bool_mask(mask, (B, N, V), "impute_columns").data_ptr()
+    if x5.numel():
+        _lib.check(_lib.load().anemoi_impute_columns(x5.data_ptr(), *x5.stride()[:4], y5.data_ptr(), *y5.stride()[:4], kp, vp, mp, B, T, E, N, V, _dt(x),
+                                                     _stream()), "impute_columns")
+    return y
+
+
+def restore_nan_columns(x: Tensor, mask: Tensor, src_of: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """BaseImputer.inverse_transform as one kernel: x [batch, ..., grid, V_out] contiguous; y[b, ..., n, c] = NaN where src_of[c] >= 0 and
+    mask[b, n, src_of[c]] (mask bool [batch, grid, V_mask], src_of int32 [V_out]), else x.  ``out``: x itself (in place) or like x."""
+    _dev(x, mask, src_of, out)
+    if x.dim() < 3 or not x.is_contiguous():
+        raise ValueError("restore_nan_columns: x must be a contiguous [batch, ..., grid, vars] tensor")
+    y = torch.empty_like(x) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype or not y.is_contiguous():
+        raise ValueError("restore_nan_columns: out must match x")
+    B, N, V = x.shape[0], x.shape[-2], x.shape[-1]
+    if mask.dim() != 3:
+        raise ValueError(f"restore_nan_columns: the mask must be [batch, grid, vars], got {tuple(mask.shape)}")
+    _bool_mask(mask, (B, N, mask.shape[2]), "restore_nan_columns")
+    M = x.numel() // max(1, B * N * V)
+    if x.numel():
+        _lib.check(_lib.load().anemoi_restore_nan_columns(x.data_ptr(), V, y.data_ptr(), V, mask.data_ptr(), mask.shape[2], mask.shape[2],
+                                                          _vec(src_of, "src_of", V, torch.int32), B, M, N, V, _dt(x), _stream()), "restore_nan_columns")
+    return y
+
+
 def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Optional[Tensor] = None, col_add: Optional[Tensor] = None,
-                   out_dtype: Optional[torch.dtype] = None) -> Tensor:
+                   out_dtype: Optional[torch.dtype] = None, *, impute: Optional[ImputeProgram] = None, nan_mask: Optional[Tensor] = None) -> Tensor:
     """x [T, N, V] (time slices of one batch / ensemble member), attrs [N, A] -> [N, width] = [x[0] | ... | x[T-1] | attrs | 0...].
     With ``col_mul`` / ``col_add`` (fp32 [V]) the time / variable columns become x * mul[v] + add[v] (the input normaliser as a
-    column program); ``out_dtype``: the model dtype when x is fp32 data fed to a 16-bit model (default: x's dtype)."""
+    column program); ``out_dtype``: the model dtype when x is fp32 data fed to a 16-bit model (default: x's dtype).
+    ``impute`` (with ``nan_mask`` bool [N, V]): every raw element is imputed within its own time step before the normaliser, and
+    nan_mask receives the NaN locations of step 0."""
     _dev(x, attrs, col_mul, col_add)
     T, N, V = x.shape
     A = 0 if attrs is None else attrs.shape[1]
@@ -1461,6 +1537,20 @@ def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Opti
         raise ValueError("assemble_input: x must be [T, N, V] with contiguous variables, attrs [N, A] of the output dtype")
     out = torch.empty((N, width), dtype=odt, device=x.device)
     ap, lda = _rows(attrs, "attrs", odt)
+    if impute is not None or nan_mask is not None:
+        if impute is None or nan_mask is None:
+            raise ValueError("assemble_input: impute and nan_mask go together")
+        _dev(x, impute.kind_src, impute.value, nan_mask)
+        if (col_mul is None) != (col_add is None):
+            raise ValueError("assemble_input: col_mul and col_add go together")
+        if x.dtype != odt and x.dtype != torch.float32:
+            raise ValueError("assemble_input: x must be in the output dtype or fp32")
+        kp, vp = _impute_ptrs(impute, V, "assemble_input")
+        _lib.check(_lib.load().anemoi_assemble_input_impute(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, kp, vp,
+                                                            _bool_mask(nan_mask, (N, V), "assemble_input").data_ptr(), V,
+                                                            _vec(col_mul, "col_mul", V, torch.float32), _vec(col_add, "col_add", V, torch.float32), ap, lda,
+                                                            A, out.data_ptr(), width, width, N, _DT[odt], _stream()), "assemble_input_impute")
+        return out
     plain_pad = T == 1 and A == 0 and odt != torch.float32 and width % 8 == 0  # cast + zero-pad of [N, V] rows: the division-free 16-byte path
     if col_mul is None and col_add is None and odt == x.dtype and not plain_pad:
         _lib.check(_lib.load().anemoi_assemble_input(x.data_ptr(), x.stride(0), x.stride(1), T, V, ap, lda, A, out.data_ptr(), width, width, N,
@@ -1476,18 +1566,27 @@ def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Opti
     return out
 
 
-def assemble_output(x_out: Tensor, x_skip: Tensor, col_map: Tensor, col_mul: Optional[Tensor] = None, col_add: Optional[Tensor] = None) -> Tensor:
+def assemble_output(x_out: Tensor, x_skip: Tensor, col_map: Tensor, col_mul: Optional[Tensor] = None, col_add: Optional[Tensor] = None, *,
+                    impute: Optional[ImputeProgram] = None) -> Tensor:
     """out[n, v] = x_out[n, v] + x_skip[n, col_map[v]] (where col_map[v] >= 0); x_out [N, V_out], x_skip [N, V_in] (row
     stride allowed), col_map int32 [V_out].  With ``col_mul`` / ``col_add`` (fp32 [V_in]) the skip is the RAW input, normalised
-    on the fly (x_skip * mul[m] + add[m]); the result has x_skip's dtype (the model dtype or fp32)."""
+    on the fly (x_skip * mul[m] + add[m]); the result has x_skip's dtype (the model dtype or fp32).  ``impute`` (over the V_in columns):
+    the raw skip is imputed before it is normalised."""
     _dev(x_out, x_skip, col_map, col_mul, col_add)
     N, V = x_out.shape
     out = torch.empty((N, V), dtype=x_skip.dtype, device=x_out.device)
     (xp, ldx), (sp, lds) = _rows(x_out, "x_out"), _rows(x_skip, "x_skip")
+    Vin = x_skip.shape[1]
+    if impute is not None:
+        _dev(x_out, impute.kind_src, impute.value)
+        kp, vp = _impute_ptrs(impute, Vin, "assemble_output")
+        _lib.check(_lib.load().anemoi_assemble_output_impute(xp, ldx, _dt(x_out), sp, lds, col_map.data_ptr(), kp, vp,
+                                                             _vec(col_mul, "col_mul", Vin, torch.float32), _vec(col_add, "col_add", Vin, torch.float32),
+                                                             out.data_ptr(), V, N, V, _dt(x_skip), _stream()), "assemble_output_impute")
+        return out
     if col_mul is None and col_add is None and x_skip.dtype == x_out.dtype:
         _lib.check(_lib.load().anemoi_assemble_output(xp, ldx, sp, lds, col_map.data_ptr(), out.data_ptr(), V, N, V, _dt(x_out), _stream()), "assemble_output")
         return out
-    Vin = x_skip.shape[1]
     _lib.check(_lib.load().anemoi_assemble_output_norm(xp, ldx, _dt(x_out), sp, lds, col_map.data_ptr(), _vec(col_mul, "col_mul", Vin, torch.float32),
                                                        _vec(col_add, "col_add", Vin, torch.float32), out.data_ptr(), V, N, V, _dt(x_skip), _stream()),
                "assemble_output_norm")
@@ -1511,14 +1610,26 @@ def affine_columns(x: Tensor, col_mul: Tensor, col_add: Tensor, inverse: bool = 
     return y
 
 
-def bound_columns_(x: Tensor, op_table: Tensor, param_table: Tensor) -> Tensor:
-    """In place: apply the column program (int32 [n_ops, 4], fp32 [n_ops, 2]; see anemoi_bound_columns) to x [..., V]."""
-    _dev(x, op_table, param_table)
+def bound_columns_(x: Tensor, op_table: Tensor, param_table: Tensor, *, nan_mask: Optional[Tensor] = None, n_nan_ops: int = 0) -> Tensor:
+    """In place: apply the column program (int32 [n_ops, 4], fp32 [n_ops, 2]; see anemoi_bound_columns) to x [..., V].  ``nan_mask``
+    (bool [rows of x, V_mask]) serves the ops of kind 10, (10, dst column, mask column, 0): NaN where the mask is set; ``n_nan_ops``: how
+    many of them the program holds - a program with such ops and no mask is an error."""
+    _dev(x, op_table, param_table, nan_mask)
     if not x.is_contiguous():
         raise ValueError("bound_columns_: x must be contiguous")
     V = x.shape[-1]
-    _lib.check(_lib.load().anemoi_bound_columns(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(),
-                                                op_table.shape[0], _dt(x), _stream()), "bound_columns")
+    if nan_mask is None and not n_nan_ops:
+        _lib.check(_lib.load().anemoi_bound_columns(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(),
+                                                    op_table.shape[0], _dt(x), _stream()), "bound_columns")
+        return x
+    mp = vm = 0
+    if nan_mask is not None:
+        vm = nan_mask.shape[-1]
+        mp = _bool_mask(nan_mask, nan_mask.shape, "bound_columns_").data_ptr()
+        if nan_mask.numel() != (x.numel() // V) * vm:
+            raise ValueError(f"bound_columns_: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
+    _lib.check(_lib.load().anemoi_bound_columns_mask(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
+                                                     mp, vm, vm, int(n_nan_ops), _dt(x), _stream()), "bound_columns_mask")
     return x
 
 

@@ -1,4 +1,5 @@
-"""Pre- / post-processors at the model edge (scope row f4) for the one processor on the hot path, the input normaliser.
+"""Pre- / post-processors at the model edge (scope row f4): the input normaliser and the imputers (InputImputer, ConstantImputer,
+CopyImputer - imputer.py) that precede it in the chains of datasets with masked fields.
 
 Written from the documented behaviour of the reference's ``anemoi.models.preprocessing`` package, not from its text:
 
@@ -12,7 +13,9 @@ Written from the documented behaviour of the reference's ``anemoi.models.preproc
 
 State_dict keys (``processors.<name>.<buffer>``) are those of the reference, so its checkpoints load strictly.  On the HIP
 path ``AnemoiModelEncProcDec.predict_step`` does not call these modules at all when the chain is a lone ``InputNormalizer``:
-the affine map becomes a column program of the assembly kernels; ``Processors.check_first_batch`` keeps the NaN check there."""
+the affine map becomes a column program of the assembly kernels; ``Processors.check_first_batch`` keeps the NaN check there.  The
+chain [one imputer, ``InputNormalizer``] is fused the same way: the imputation program rides in the same kernels, the NaN mask of the first
+time step is written by the input assembly and read by the output column program."""
 from __future__ import annotations
 
 import logging
@@ -132,3 +135,4 @@ class Processors(nn.Module):
 
 
 from .normalizer import InputNormalizer  # noqa: E402,F401
+from .imputer import BaseImputer, ConstantImputer, CopyImputer, InputImputer  # noqa: E402,F401

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 19
+#define ANEMOI_HIP_ABI_VERSION 20
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -351,6 +351,47 @@ int anemoi_assemble_output_norm(const void* x_out, int64_t ldx, anemoi_dtype_t m
  * y = (x - add[c]) / mul[c]) over the last dimension of a [n_rows, V] view; y may alias x (in_place). */
 int anemoi_affine_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const float* col_mul, const float* col_add,
                           int32_t inverse, int32_t n_rows, int32_t V, anemoi_dtype_t dtype, void* stream);
+
+/* ---- imputers at the model edges -------------------------------------------------------------------------------------------
+ * The reference's imputers (preprocessing/imputer.py) replace NaN in configured input variables before the normaliser and put NaN back
+ * into the model's output where the input's first time step had it.  The IMPUTATION PROGRAM is a per-column table over the V input columns:
+ * kind_src int32 [V][2] = (kind, source column), value fp32 [V].  kind 0: not imputed; 1: NaN -> value[c] (rounded to the data dtype on
+ * the host, so the fp32 entry is exact); 2: NaN -> the element of column `source` at the same position (CopyImputer; a source column is
+ * never itself imputed).  Masks are bool tensors, one byte per element, written with ordinary vector stores. */
+
+/* Stand-alone BaseImputer.transform over x [batch, time, ensemble, grid, V] (element strides ld_b .. ld_n, columns contiguous; y likewise
+ * and may alias x): the NaN test of an element is that of ensemble member 0 at the same (batch, time, grid, column) and applies to every
+ * member; each time step has its own.  mask (NULL: none): bool [batch, grid, V], the NaN locations of time step 0, member 0, ALL columns. */
+int anemoi_impute_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, void* y, int64_t yd_b, int64_t yd_t,
+                          int64_t yd_e, int64_t yd_n, const int32_t* kind_src, const float* value, void* mask, int32_t B, int32_t T_steps,
+                          int32_t E, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream);
+
+/* Stand-alone BaseImputer.inverse_transform: y[b, m, n, c] = NaN where src_of[c] >= 0 and mask[b, n, src_of[c]], else x[b, m, n, c];
+ * x / y [batch, M, grid, V] with rows ldx / ldy apart (y may alias x: only the restored elements are stored), mask bool [batch, grid, ldm]
+ * with n_mask_cols columns, src_of int32 [V] (-1: the column is left alone). */
+int anemoi_restore_nan_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const void* mask, int64_t ldm, int32_t n_mask_cols,
+                               const int32_t* src_of, int32_t B, int32_t M, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream);
+
+/* anemoi_assemble_input_norm with the imputation program in front of the normaliser: every raw element is tested and imputed within its
+ * own time step (the copy source is read from the same step and row), then x * col_mul[v] + col_add[v] with the same two fp32 roundings
+ * (NULL/NULL: none).  mask: bool [n_rows][ldm], the NaN locations of step 0, written in the same pass.  Same scalar / 8-column routes. */
+int anemoi_assemble_input_impute(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
+                                 const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const float* col_mul,
+                                 const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo, int32_t W,
+                                 int32_t n_rows, anemoi_dtype_t dtype, void* stream);
+
+/* anemoi_assemble_output_norm whose RAW skip is imputed by the same program (over the skip's columns) before it is normalised. */
+int anemoi_assemble_output_impute(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
+                                  const int32_t* col_map, const int32_t* kind_src, const float* value, const float* col_mul,
+                                  const float* col_add, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols, anemoi_dtype_t dtype,
+                                  void* stream);
+
+/* anemoi_bound_columns with a mask bool [n_rows][ldm] (n_mask_cols columns) and one more op kind, 10 "NaN where mask[n, src]", encoded
+ * (10, dst column, src mask column, 0) and appended after the op-9 de-normalisations: boundings, de-normalisation and NaN restoration
+ * stay one in-place launch.  n_nan_ops: how many ops of kind 10 the program holds; n_nan_ops > 0 with mask == NULL is an error, and
+ * mask == NULL otherwise forwards to anemoi_bound_columns. */
+int anemoi_bound_columns_mask(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
+                              const void* mask, int64_t ldm, int32_t n_mask_cols, int32_t n_nan_ops, anemoi_dtype_t dtype, void* stream);
 
 /* ---- device-initiated row exchange between the ranks of a model-parallel group (scope row e) ----------------------------
  * The reference exchanges node rows with host-issued NCCL collectives: the per-layer halo all-to-all
