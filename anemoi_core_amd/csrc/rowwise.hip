@@ -12,6 +12,7 @@
 
 #include <algorithm>
 
+#include "remap_core.h"
 #include "rowwise_common.h"
 
 namespace anemoi {
@@ -793,7 +794,11 @@ __global__ void assemble_output_impute_kernel(const TM* __restrict__ x_out, int6
 // bound_columns_kernel with one more kind, 10: NaN where mask[r, tot] (BaseImputer.inverse_transform as an op of the output column program,
 // appended after the op-9 de-normalisations; `tot` is the mask column).  The kinds 1..9 are those of bound_columns_kernel, statement for
 // statement; that kernel is kept as it is for the programs without a mask.
-template <typename T>
+// EXT (anemoi_column_program; the instantiation without it is the kernel as it was): the kinds of the post-processors and the remapper's
+// inverse.  11: p0 where row[tot] == 0 (ConditionalZeroPostprocessor); 12: NaN where row[tot] is NaN (ConditionalNaNPostprocessor) - both
+// read the masking column as the ops before them left it, so the host orders a fill OF the masking column after the fills it masks;
+// 16 + op: the RemapOp `op` (remap_core.h) with flags = ops[4 i + 3] and a third parameter as the float bits of ops[4 i + 2].
+template <typename T, bool EXT>
 __global__ void bound_columns_mask_kernel(T* __restrict__ x, int64_t ldx, int n_rows, const int32_t* __restrict__ ops, const float* __restrict__ params,
                                           int n_ops, const uint8_t* __restrict__ mask, int64_t ldm, int n_mask_cols) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -821,10 +826,149 @@ __global__ void bound_columns_mask_kernel(T* __restrict__ x, int64_t ldx, int n_
         if ((unsigned)tot >= (unsigned)n_mask_cols || mask[(int64_t)r * ldm + tot] == 0) continue;  // every other bit of the row stays
         v = __builtin_nanf("");
         break;
-      default: break;
+      default:
+        if constexpr (EXT) {
+          if (kind == 11) {
+            if (!(to_float(row[tot]) == 0.f)) continue;
+            v = p0;
+          } else if (kind == 12) {
+            if (!isnan(to_float(row[tot]))) continue;
+            v = __builtin_nanf("");
+          } else if (kind >= 16) {
+            bool bad = false;
+            v = remap_apply<T>(v, kind - 16, ops[4 * i + 3], p0, p1, __int_as_float(tot), 0.f, bad);
+          }
+        }
+        break;
     }
     row[col] = from_float<T>(v);
   }
+}
+
+// Stand-alone Remapper.transform / inverse_transform over x [batch, time, ensemble, grid, V] (element strides ld_b .. ld_n, columns
+// contiguous; y likewise and may alias x).  The program is a per-column table: op_flags int32 [V][2] = (RemapOp, flags), par fp32 [V][4].
+// A thread owns one element of one ACTIVE column: `active` int32 [n_active] lists the columns whose op is not REMAP_NONE, so an in-place
+// launch neither loads nor stores the others (2-4 of ~80 columns in a typical configuration); active == nullptr walks all V columns (out
+// of place, where every element is copied).  viol (may be null): int32 [V], entry c counts the elements of column c that fail the reference's
+// domain assertion, with an ordinary atomic add - rare by construction, the host reads it once after the launch.
+template <typename T>
+__global__ void remap_columns_kernel(const T* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, T* y, int64_t yd_b, int64_t yd_t,  // (y may be x)
+                                     int64_t yd_e, int64_t yd_n, const int32_t* __restrict__ op_flags, const float* __restrict__ par,
+                                     const int32_t* __restrict__ active, int n_active, int32_t* viol, int B, int T_steps, int E, int N, int V) {
+  const int per_row = active != nullptr ? n_active : V;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * T_steps * E * N * per_row) return;
+  const int a = (int)(i % per_row);
+  int64_t row = i / per_row;
+  const int n = (int)(row % N);
+  row /= N;
+  const int e = (int)(row % E);
+  row /= E;
+  const int t = (int)(row % T_steps), b = (int)(row / T_steps);
+  const int c = active != nullptr ? active[a] : a;
+  const int2 of = reinterpret_cast<const int2*>(op_flags)[c];
+  const float4 p = reinterpret_cast<const float4*>(par)[c];
+  const T in = x[b * ld_b + t * ld_t + e * ld_e + (int64_t)n * ld_n + c];
+  bool bad = false;
+  const T out = of.x == REMAP_NONE ? in : from_float<T>(remap_apply<T>(to_float(in), of.x, of.y, p.x, p.y, p.z, p.w, bad));
+  y[b * yd_b + t * yd_t + e * yd_e + (int64_t)n * yd_n + c] = out;
+  if (bad && viol != nullptr) atomicAdd(viol + c, 1);
+}
+
+// One raw element of the chain [imputer]? Remapper InputNormalizer: impute (kind_src == nullptr: no imputer), remap forward with the
+// roundings of the RAW dtype TI (the module runs on the raw tensor), then x * mul + add as the other assembly kernels.  Nothing is counted
+// here: the chain's one-off first-batch check runs the member modules, with their assertion, on a copy.
+template <typename TI>
+__device__ __forceinline__ float edge_chain_one(float v, const TI* __restrict__ row, int cv, const int32_t* __restrict__ kind_src,
+                                                const float* __restrict__ value, const int32_t* __restrict__ op_flags, const float* __restrict__ par,
+                                                const float* __restrict__ mul, const float* __restrict__ add) {
+  if (kind_src != nullptr && isnan(v)) {
+    const int2 ks = reinterpret_cast<const int2*>(kind_src)[cv];
+    if (ks.x != 0) v = ks.x == 1 ? value[cv] : to_float(row[ks.y]);
+  }
+  const int2 of = reinterpret_cast<const int2*>(op_flags)[cv];
+  if (of.x != REMAP_NONE) {
+    const float4 p = reinterpret_cast<const float4*>(par)[cv];
+    bool bad = false;
+    v = remap_apply<TI>(v, of.x, of.y, p.x, p.y, p.z, p.w, bad);
+  }
+  if (mul != nullptr) v = mul_then_add(v, mul[cv], add[cv]);
+  return v;
+}
+
+// assemble_input_impute_kernel with the remap program between the imputation program (optional: kind_src / value / mask all null) and
+// the normaliser.  The NaN mask of step 0 is that of the RAW input, as the imputer's own transform records it.
+template <typename TI, typename TO>
+__global__ void assemble_input_remap_kernel(const TI* __restrict__ x, int64_t ld_t, int64_t ldx, int T_steps, int V, const int32_t* __restrict__ kind_src,
+                                            const float* __restrict__ value, uint8_t* __restrict__ mask, int64_t ldm,
+                                            const int32_t* __restrict__ op_flags, const float* __restrict__ par, const float* __restrict__ mul,
+                                            const float* __restrict__ add, const TO* __restrict__ attrs, int64_t lda, int A, TO* __restrict__ out,
+                                            int64_t ldo, int W, int n_rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * W) return;
+  const int n = (int)(i / W), c = (int)(i % W);
+  float v = 0.f;
+  if (c < T_steps * V) {
+    const int t = c / V, cv = c % V;
+    const TI* xr = x + t * ld_t + (int64_t)n * ldx;
+    v = to_float(xr[cv]);
+    if (mask != nullptr && t == 0) mask[(int64_t)n * ldm + cv] = isnan(v) ? 1 : 0;
+    v = edge_chain_one<TI>(v, xr, cv, kind_src, value, op_flags, par, mul, add);
+  } else if (c < T_steps * V + A) {
+    v = to_float(attrs[(int64_t)n * lda + (c - T_steps * V)]);
+  }
+  out[(int64_t)n * ldo + c] = from_float<TO>(v);
+}
+
+// The same for 16-bit outputs whose width is a multiple of 8 (one 16-byte store per thread), as assemble_input_impute_vec8_kernel; the
+// mask bytes of step 0 are stored one by one.
+template <typename TI, typename TO>
+__global__ void assemble_input_remap_vec8_kernel(const TI* __restrict__ x, int64_t ld_t, int64_t ldx, int T_steps, int V,
+                                                 const int32_t* __restrict__ kind_src, const float* __restrict__ value, uint8_t* __restrict__ mask,
+                                                 int64_t ldm, const int32_t* __restrict__ op_flags, const float* __restrict__ par,
+                                                 const float* __restrict__ mul, const float* __restrict__ add, const TO* __restrict__ attrs, int64_t lda,
+                                                 int A, TO* __restrict__ out, int64_t ldo, int W, int n_rows) {
+  const int per_row = W >> 3;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * per_row) return;
+  const int n = (int)(i / per_row), c0 = (int)(i % per_row) << 3;
+  Vec<TO, 8> o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = c0 + j;
+    float v = 0.f;
+    if (c < T_steps * V) {
+      const int t = c / V, cv = c % V;
+      const TI* xr = x + t * ld_t + (int64_t)n * ldx;
+      v = to_float(xr[cv]);
+      if (mask != nullptr && t == 0) mask[(int64_t)n * ldm + cv] = isnan(v) ? 1 : 0;
+      v = edge_chain_one<TI>(v, xr, cv, kind_src, value, op_flags, par, mul, add);
+    } else if (c < T_steps * V + A) {
+      v = to_float(attrs[(int64_t)n * lda + (c - T_steps * V)]);
+    }
+    o.v[j] = from_float<TO>(v);
+  }
+  *reinterpret_cast<Vec<TO, 8>*>(out + (int64_t)n * ldo + c0) = o;
+}
+
+// assemble_output_impute_kernel whose RAW skip goes through the same chain: impute (optional), remap forward, normalise.
+template <typename TM, typename TS>
+__global__ void assemble_output_remap_kernel(const TM* __restrict__ x_out, int64_t ldx, const TS* __restrict__ skip, int64_t lds,
+                                             const int32_t* __restrict__ col_map, const int32_t* __restrict__ kind_src, const float* __restrict__ value,
+                                             const int32_t* __restrict__ op_flags, const float* __restrict__ par, const float* __restrict__ mul,
+                                             const float* __restrict__ add, TS* __restrict__ out, int64_t ldo, int n_rows, int n_cols) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n_rows * n_cols) return;
+  const int n = (int)(i / n_cols), v = (int)(i % n_cols);
+  float val = to_float(from_float<TS>(to_float(x_out[(int64_t)n * ldx + v])));
+  const int m = col_map[v];
+  if (m >= 0) {
+    const TS* sr = skip + (int64_t)n * lds;
+    float sk = edge_chain_one<TS>(to_float(sr[m]), sr, m, kind_src, value, op_flags, par, nullptr, nullptr);
+    if (mul != nullptr) sk = to_float(from_float<TS>(mul_then_add(sk, mul[m], add[m])));
+    val += sk;
+  }
+  out[(int64_t)n * ldo + v] = from_float<TS>(val);
 }
 
 template <typename T>
@@ -1290,7 +1434,120 @@ extern "C" int anemoi_bound_columns_mask(void* x, int64_t ldx, int32_t n_rows, i
   hipStream_t st = as_stream(stream);
   return dispatch_dtype(dtype, [&](auto t) {
     using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((bound_columns_mask_kernel<T>), grid, block, 0, st, (T*)x, ldx, n_rows, ops, params, n_ops, (const uint8_t*)mask, ldm, n_mask_cols);
+    hipLaunchKernelGGL((bound_columns_mask_kernel<T, false>), grid, block, 0, st, (T*)x, ldx, n_rows, ops, params, n_ops, (const uint8_t*)mask, ldm, n_mask_cols);
     return check_launch("bound_columns_mask_kernel");
+  });
+}
+
+// ---- remapper and post-processors (see remap_core.h and the kernels above) -------------------------------------------------------------
+extern "C" int anemoi_remap_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, void* y, int64_t yd_b, int64_t yd_t,
+                                    int64_t yd_e, int64_t yd_n, const int32_t* op_flags, const float* par, const int32_t* active, int32_t n_active,
+                                    int32_t* violations, int32_t B, int32_t T_steps, int32_t E, int32_t N, int32_t V, anemoi_dtype_t dtype,
+                                    void* stream) {
+  ANEMOI_REQUIRE(B >= 0 && T_steps >= 0 && E >= 0 && N >= 0 && V > 0 && ld_n >= V && yd_n >= V, "remap_columns: bad sizes");
+  ANEMOI_REQUIRE(n_active >= 0 && n_active <= V, "remap_columns: n_active must lie in [0, V]");
+  ANEMOI_REQUIRE(active != nullptr || x != y || n_active == V, "remap_columns: an in-place launch takes the list of active columns");
+  const int64_t n = (int64_t)B * T_steps * E * N * (active != nullptr ? n_active : V);
+  if (n == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && y && op_flags && par, "remap_columns: null pointer");
+  ANEMOI_REQUIRE((reinterpret_cast<uintptr_t>(op_flags) & 7) == 0 && (reinterpret_cast<uintptr_t>(par) & 15) == 0,
+                 "remap_columns: the program tables must be 8- / 16-byte aligned");
+  ANEMOI_REQUIRE((n + 255) / 256 <= 0x7fffffffLL, "remap_columns: too many elements for one launch");
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((remap_columns_kernel<T>), grid, block, 0, st, (const T*)x, ld_b, ld_t, ld_e, ld_n, (T*)y, yd_b, yd_t, yd_e, yd_n, op_flags, par,
+                       active, n_active, violations, B, T_steps, E, N, V);
+    return check_launch("remap_columns_kernel");
+  });
+}
+
+extern "C" int anemoi_column_program(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
+                                     const void* mask, int64_t ldm, int32_t n_mask_cols, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && n_cols > 0 && ldx >= n_cols && n_ops >= 0, "column_program: bad sizes");
+  ANEMOI_REQUIRE(mask == nullptr ? n_mask_cols == 0 : (n_mask_cols > 0 && ldm >= n_mask_cols), "column_program: bad mask sizes");
+  if (n_rows == 0 || n_ops == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && ops && params, "column_program: null pointer");
+  const dim3 grid((n_rows + 255) / 256), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((bound_columns_mask_kernel<T, true>), grid, block, 0, st, (T*)x, ldx, n_rows, ops, params, n_ops, (const uint8_t*)mask, ldm, n_mask_cols);
+    return check_launch("column_program_kernel");
+  });
+}
+
+static bool remap_tables_aligned(const int32_t* op_flags, const float* par, const int32_t* kind_src) {
+  return (reinterpret_cast<uintptr_t>(op_flags) & 7) == 0 && (reinterpret_cast<uintptr_t>(par) & 15) == 0 && (reinterpret_cast<uintptr_t>(kind_src) & 7) == 0;
+}
+
+extern "C" int anemoi_assemble_input_remap(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
+                                           const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const int32_t* op_flags,
+                                           const float* par, const float* col_mul, const float* col_add, const void* attrs, int64_t lda, int32_t A,
+                                           void* out, int64_t ldo, int32_t W, int32_t n_rows, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && T_steps > 0 && V > 0 && A >= 0 && W >= T_steps * V + A && ldo >= W && ldx >= V && (A == 0 || lda >= A),
+                 "assemble_input_remap: bad sizes");
+  ANEMOI_REQUIRE((col_mul == nullptr) == (col_add == nullptr), "assemble_input_remap: col_mul and col_add go together");
+  ANEMOI_REQUIRE((kind_src == nullptr) == (value == nullptr) && (kind_src == nullptr) == (mask == nullptr),
+                 "assemble_input_remap: the imputation program, its values and the mask go together");
+  ANEMOI_REQUIRE(mask == nullptr || ldm >= V, "assemble_input_remap: bad mask sizes");
+  if (n_rows == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x && out && op_flags && par && (A == 0 || attrs), "assemble_input_remap: null pointer");
+  ANEMOI_REQUIRE(remap_tables_aligned(op_flags, par, kind_src), "assemble_input_remap: the program tables must be 8- / 16-byte aligned");
+  ANEMOI_REQUIRE(x_dtype == dtype || x_dtype == ANEMOI_F32, "assemble_input_remap: the input is in the model dtype or fp32");
+  hipStream_t st = as_stream(stream);
+  uint8_t* mk = (uint8_t*)mask;
+  return dispatch_dtype(dtype, [&](auto t) {
+    using TO = typename decltype(t)::type;
+    const bool wide_in = x_dtype == ANEMOI_F32;  // TI = float, else TI = TO
+    if constexpr (sizeof(TO) == 2) {
+      if (W % 8 == 0 && ldo % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+        const int64_t n8 = (int64_t)n_rows * (W / 8);
+        const dim3 grid8((unsigned)((n8 + 255) / 256)), block8(256);
+        if (wide_in)
+          hipLaunchKernelGGL((assemble_input_remap_vec8_kernel<float, TO>), grid8, block8, 0, st, (const float*)x, ld_t, ldx, T_steps, V, kind_src,
+                             value, mk, ldm, op_flags, par, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        else
+          hipLaunchKernelGGL((assemble_input_remap_vec8_kernel<TO, TO>), grid8, block8, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, kind_src, value,
+                             mk, ldm, op_flags, par, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+        return check_launch("assemble_input_remap_vec8_kernel");
+      }
+    }
+    const int64_t n = (int64_t)n_rows * W;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (wide_in)
+      hipLaunchKernelGGL((assemble_input_remap_kernel<float, TO>), grid, block, 0, st, (const float*)x, ld_t, ldx, T_steps, V, kind_src, value, mk, ldm,
+                         op_flags, par, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    else
+      hipLaunchKernelGGL((assemble_input_remap_kernel<TO, TO>), grid, block, 0, st, (const TO*)x, ld_t, ldx, T_steps, V, kind_src, value, mk, ldm,
+                         op_flags, par, col_mul, col_add, (const TO*)attrs, lda, A, (TO*)out, ldo, W, n_rows);
+    return check_launch("assemble_input_remap_kernel");
+  });
+}
+
+extern "C" int anemoi_assemble_output_remap(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
+                                            const int32_t* col_map, const int32_t* kind_src, const float* value, const int32_t* op_flags,
+                                            const float* par, const float* col_mul, const float* col_add, void* out, int64_t ldo, int32_t n_rows,
+                                            int32_t n_cols, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(n_rows >= 0 && n_cols > 0 && ldx >= n_cols && ldo >= n_cols, "assemble_output_remap: bad sizes");
+  ANEMOI_REQUIRE((col_mul == nullptr) == (col_add == nullptr), "assemble_output_remap: col_mul and col_add go together");
+  ANEMOI_REQUIRE((kind_src == nullptr) == (value == nullptr), "assemble_output_remap: the imputation program and its values go together");
+  if (n_rows == 0) return ANEMOI_OK;
+  ANEMOI_REQUIRE(x_out && x_skip && col_map && out && op_flags && par, "assemble_output_remap: null pointer");
+  ANEMOI_REQUIRE(remap_tables_aligned(op_flags, par, kind_src), "assemble_output_remap: the program tables must be 8- / 16-byte aligned");
+  ANEMOI_REQUIRE(model_dtype == dtype || dtype == ANEMOI_F32, "assemble_output_remap: the output is in the model dtype or fp32");
+  const int64_t n = (int64_t)n_rows * n_cols;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  hipStream_t st = as_stream(stream);
+  return dispatch_dtype(model_dtype, [&](auto t) {
+    using TM = typename decltype(t)::type;
+    if (dtype == ANEMOI_F32)  // TS = float, else TS = TM
+      hipLaunchKernelGGL((assemble_output_remap_kernel<TM, float>), grid, block, 0, st, (const TM*)x_out, ldx, (const float*)x_skip, lds, col_map,
+                         kind_src, value, op_flags, par, col_mul, col_add, (float*)out, ldo, n_rows, n_cols);
+    else
+      hipLaunchKernelGGL((assemble_output_remap_kernel<TM, TM>), grid, block, 0, st, (const TM*)x_out, ldx, (const TM*)x_skip, lds, col_map, kind_src,
+                         value, op_flags, par, col_mul, col_add, (TM*)out, ldo, n_rows, n_cols);
+    return check_launch("assemble_output_remap_kernel");
   });
 }

@@ -21,12 +21,31 @@ def _leaky_hardtanh(x: Tensor, lo: float, hi: float, slope: float = 0.01) -> Ten
     return torch.where(x > hi, hi + slope * (x - hi), y)
 
 
-def apply_program_torch(x: Tensor, program: list) -> Tensor:
-    """Differentiable, out-of-place evaluation of a column program (training path and CPU-side checks)."""
+DENORMALISE, NAN_WHERE_MASK = 9, 10  # (x - p0) / p1: the normaliser's inverse; NaN where mask[n, total column]: the imputer's inverse
+FILL_WHERE_ZERO, NAN_WHERE_NAN, REMAP_BASE = 11, 12, 16  # the kinds of anemoi_column_program beyond 1..10; REMAP_BASE + remap op
+
+
+def apply_program_torch(x: Tensor, program: list, mask: Optional[Tensor] = None) -> Tensor:
+    """Differentiable, out-of-place evaluation of a column program (training path and CPU-side checks).  An op is
+    (kind, column, total column, p0, p1); the ops of the remapper's inverse carry two more: (..., flags, p2).  ``mask`` (bool, one row of
+    mask columns per row of x) serves the ops of kind 10."""
     cols = list(x.unbind(-1))
-    for kind, col, tot, p0, p1 in program:
+    for kind, col, tot, p0, p1, *more in program:
         v = cols[col]
-        if kind == RELU:
+        if kind == DENORMALISE:  # (a division by a TENSOR, as the normaliser's: torch's device kernels multiply by a scalar's reciprocal)
+            v = (v - p0) / torch.full((), p1, dtype=v.dtype, device=v.device)
+        elif kind == NAN_WHERE_MASK:
+            v = torch.where(mask[..., tot].reshape(v.shape), torch.full((), float("nan"), dtype=v.dtype, device=v.device), v)
+        elif kind == FILL_WHERE_ZERO:
+            v = torch.where(cols[tot] == 0, torch.full((), p0, dtype=v.dtype, device=v.device), v)
+        elif kind == NAN_WHERE_NAN:
+            v = torch.where(torch.isnan(cols[tot]), torch.full((), float("nan"), dtype=v.dtype, device=v.device), v)
+        elif kind >= REMAP_BASE:
+            from ..preprocessing.remapper import apply_entry_torch
+
+            flags, p2 = more if more else (0, 0.0)
+            v = apply_entry_torch(v, (kind - REMAP_BASE, flags, p0, p1, p2, 0.0))
+        elif kind == RELU:
             v = torch.relu(v)
         elif kind == LEAKY_RELU:
             v = torch.nn.functional.leaky_relu(v)
@@ -46,7 +65,7 @@ def apply_program_torch(x: Tensor, program: list) -> Tensor:
     return torch.stack(cols, dim=-1)
 
 
-NAN_WHERE_MASK = 10  # (10, dst column, mask column, 0, 0): NaN where mask[n, src] - the imputer's inverse transform; needs a mask
+# NAN_WHERE_MASK (above): (10, dst column, mask column, 0, 0): NaN where mask[n, src] - the imputer's inverse transform; needs a mask
 
 
 def program_tables(program: list, device) -> tuple[Tensor, Tensor]:
@@ -64,6 +83,27 @@ class MaskedProgramTables(NamedTuple):
 
 def masked_program_tables(program: list, device) -> MaskedProgramTables:
     return MaskedProgramTables(*_tables(program, device), sum(op[0] == NAN_WHERE_MASK for op in program))
+
+
+def extended_program_tables(program: list, width: int, device) -> tuple[Tensor, Tensor]:
+    """Device tables for ``ops.column_program_``: the layout of ``program_tables``; an op of the remapper's inverse
+    (kind, column, 0, p0, p1, flags, p2) puts its flags into the fourth integer and the float bits of p2 into the third.  Every column
+    the kernel will index is checked against ``width`` here."""
+    rows, pars = [], []
+    for kind, col, tot, p0, p1, *more in program:
+        flags, p2 = more if more else (0, 0.0)
+        if kind >= REMAP_BASE:
+            from ..preprocessing.remapper import device_entry
+
+            _, flags, p0, p1, p2, _ = device_entry((kind - REMAP_BASE, flags, p0, p1, p2, 0.0))  # (scalar divisors as fp32 reciprocals)
+            tot = int(torch.tensor(float(p2), dtype=torch.float32).view(torch.int32))
+        elif kind in (FRACTION, LEAKY_FRACTION, FILL_WHERE_ZERO, NAN_WHERE_NAN) and not 0 <= tot < width:
+            raise ValueError(f"extended_program_tables: total / masking column {tot} outside [0, {width})")
+        if not 0 <= col < width:
+            raise ValueError(f"extended_program_tables: column {col} outside [0, {width})")
+        rows.append([int(kind), int(col), int(tot), int(flags)])
+        pars.append([float(p0), float(p1)])
+    return (torch.tensor(rows, dtype=torch.int32, device=device).reshape(-1, 4), torch.tensor(pars, dtype=torch.float32, device=device).reshape(-1, 2))
 
 
 def _tables(program: list, device) -> tuple[Tensor, Tensor]:

@@ -50,6 +50,9 @@ class _EdgeState(NamedTuple):
     norm_out: Optional[nn.Module]
     imputer: Optional[nn.Module]
     nan_mask: Optional[Tensor]  # bool [N, V] when the imputation program ran inside the assembly kernel, else None
+    remapper: Optional[nn.Module] = None  # the chain's Remapper: its inverse is part of the output column program
+    remap_fused: bool = False  # the remap program ran inside the assembly kernel: the raw skip is not remapped either
+    post_members: Optional[list] = None  # the members of the post chain when it holds more than [imputer, normaliser]
 
 
 def _retarget(cfg) -> dict:
@@ -231,16 +234,37 @@ class AnemoiModelEncProcDec(nn.Module):
         return out
 
     # -- glue (encoder_processor_decoder.py:98-163) ---------------------------------------------------------
-    def _assemble_input(self, x: Tensor, batch_size: int, shard_sizes, group, ds: str, norm=None, imputer=None):
-        """``norm``: the dataset's InputNormalizer when ``predict_step`` fuses it (x is then the RAW batch); ``imputer``: the imputer that
-        precedes it in the chain.  Returns (x_data_latent, x_skip, skip_is_raw, nan_mask): nan_mask bool [N, V], the NaN locations of the
-        first step, when the imputation program ran inside the assembly kernel (the skip is then raw AND not imputed), else None."""
+    def _assemble_input(self, x: Tensor, batch_size: int, shard_sizes, group, ds: str, norm=None, imputer=None, remapper=None):
+        """``norm``: the dataset's InputNormalizer when ``predict_step`` fuses it (x is then the RAW batch); ``imputer`` / ``remapper``: the
+        imputer and the Remapper that precede it in the chain.  Returns (x_data_latent, x_skip, skip_is_raw, nan_mask, remap_fused):
+        nan_mask bool [N, V], the NaN locations of the first step, when the imputation program ran inside the assembly kernel (the skip is
+        then raw AND not imputed), else None; remap_fused: the remap program ran there as well (the raw skip is not remapped)."""
         node_attr = self.node_attributes(ds, batch_size=batch_size)
         if shard_sizes is not None:
             node_attr = shard_tensor(node_attr, 0, shard_sizes, group)
         B, T, E, N, V = x.shape
         fusable = (_FUSED_INPUT and B == 1 and E == 1 and x.is_cuda and x.stride(4) == 1
                    and not (torch.is_grad_enabled() and (x.requires_grad or node_attr.requires_grad)))
+        if remapper is not None:
+            # as with the imputer below: the programs ride in the assembly kernels for one sample, one output step, the step skip and a whole
+            # grid; everything else runs the stand-alone kernels first (no host synchronisation: the domain assertion belongs to the chain's
+            # first-batch check) and goes on as if the chain were the normaliser alone
+            if not (fusable and self.n_step_output == 1 and not self._truncated[ds] and shard_sizes is None and not torch.is_grad_enabled()
+                    and (node_attr.dtype == x.dtype or x.dtype == torch.float32)):
+                fresh = imputer is not None
+                if fresh:
+                    x, imputer = imputer.transform(x, in_place=False), None
+                x, remapper = remapper.transform(x if x.stride(-1) == 1 else x.contiguous(), in_place=fresh, check_domain=False), None
+            else:
+                width = T * V + node_attr.shape[1]
+                if node_attr.dtype != torch.float32 and self._prepad(ds):
+                    width += (-width) % 64 if (-width) % 64 <= 16 and _PAD64 else (-width) % 8
+                nan_mask = None if imputer is None else torch.empty((N, V), dtype=torch.bool, device=x.device)
+                mul, add = norm.column_program(V)
+                out = ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype,
+                                         impute=None if imputer is None else imputer.device_program(V, x.dtype, x.device), nan_mask=nan_mask,
+                                         remap=remapper.device_program(V, False, x.device)[0])
+                return out, x[:, self._skip_step, ...], True, nan_mask, True
         if imputer is not None:
             # the program rides in the assembly kernels for one sample, one output step, the step skip and a whole grid; everything else
             # (a batch, several output steps, a truncated residual - whose down projection would need the program on every gathered value -,
@@ -256,16 +280,16 @@ class AnemoiModelEncProcDec(nn.Module):
                 mul, add = norm.column_program(V)
                 out = ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype,
                                          impute=imputer.device_program(V, x.dtype, x.device), nan_mask=nan_mask)
-                return out, x[:, self._skip_step, ...], True, nan_mask
+                return out, x[:, self._skip_step, ...], True, nan_mask, False
         if fusable and (node_attr.dtype == x.dtype or (norm is not None and x.dtype == torch.float32)):
             # inference, one member: permute + cat + alignment zeros (+ the input normaliser as a column program) in ONE kernel
             width = T * V + node_attr.shape[1]
             if node_attr.dtype != torch.float32 and self._prepad(ds):
                 width += (-width) % 64 if (-width) % 64 <= 16 and _PAD64 else (-width) % 8
             if norm is None:
-                return ops.assemble_input(x[0, :, 0], node_attr, width), x[:, self._skip_step, ...], False, None
+                return ops.assemble_input(x[0, :, 0], node_attr, width), x[:, self._skip_step, ...], False, None, False
             mul, add = norm.column_program(V)
-            return ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype), x[:, self._skip_step, ...], True, None
+            return ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype), x[:, self._skip_step, ...], True, None, False
         if norm is not None:  # not fusable: the normaliser's own kernel, then the generic path
             x = norm.transform(x, in_place=False).to(node_attr.dtype)
         x_skip = x[:, self._skip_step, ...]  # SkipConnection (layers/residual.py:60-81): last input step
@@ -280,7 +304,7 @@ class AnemoiModelEncProcDec(nn.Module):
             if self._pad_zeros is None or self._pad_zeros[0] != key:
                 self._pad_zeros = (key, torch.zeros((flat.shape[0], pad), dtype=flat.dtype, device=flat.device))
             cols.append(self._pad_zeros[1])
-        return torch.cat(cols, dim=-1), x_skip, False, None
+        return torch.cat(cols, dim=-1), x_skip, False, None, False
 
     def _prepad(self, ds: str) -> bool:
         """The GraphTransformer mappers embed their inputs through PaddedLinear, which accepts rows that already carry the
@@ -302,11 +326,15 @@ class AnemoiModelEncProcDec(nn.Module):
         return self._hidden_padded[1]
 
     def _assemble_output(self, x_out: Tensor, x_skip: Tensor, batch_size: int, ensemble_size: int, dtype, ds: str, norm=None,
-                         skip_is_raw: bool = False, denorm=None, compact: bool = False, imputer=None, nan_mask: Optional[Tensor] = None) -> Tensor:
+                         skip_is_raw: bool = False, denorm=None, compact: bool = False, imputer=None, nan_mask: Optional[Tensor] = None,
+                         remapper=None, remap_fused: bool = False, post_members: Optional[list] = None) -> Tensor:
         """``norm`` / ``skip_is_raw``: x_skip is the RAW input and is normalised inside the residual kernel; ``denorm``: the
         output InputNormalizer whose inverse transform is appended to the column program of the boundings; ``compact``: x_skip holds the
         prognostic columns only, in their order (the truncated residual); ``imputer`` / ``nan_mask`` (from ``_assemble_input``): the raw skip
-        is imputed by the imputer's program as well, and its NaN restoration (op 10, reading nan_mask) closes the column program."""
+        is imputed by the imputer's program as well, and its NaN restoration (op 10, reading nan_mask) closes the column program.
+        ``remapper`` / ``remap_fused``: the raw skip goes through the remap program as well; ``post_members``: the members of a post chain
+        with a Remapper or post-processors - the output program is then the boundings followed by every member's inverse ops, last member
+        first (``ops.column_program_``)."""
         N = x_out.shape[0] // (batch_size * ensemble_size)
         in_idx, out_idx = getattr(self, f"_in_idx_{ds}"), getattr(self, f"_out_idx_{ds}")
         col_map = getattr(self, f"_col_map_c_{ds}" if compact else f"_col_map_{ds}")
@@ -314,11 +342,18 @@ class AnemoiModelEncProcDec(nn.Module):
                    and not (torch.is_grad_enabled() and (x_out.requires_grad or x_skip.requires_grad)))
         fused_norm = fusable and skip_is_raw and x_skip.dtype == dtype and dtype in (x_out.dtype, torch.float32)
         program = None if nan_mask is None else imputer.device_program(x_skip.shape[-1], x_skip.dtype, x_skip.device)
-        if skip_is_raw and not fused_norm:  # every path but the fused-normalisation kernel takes a NORMALISED (and imputed) skip
+        remap = remapper.device_program(x_skip.shape[-1], False, x_skip.device)[0] if remap_fused else None
+        if skip_is_raw and not fused_norm:  # every path but the fused-normalisation kernel takes a NORMALISED (imputed, remapped) skip
             if program is not None:
                 x_skip = ops.impute_columns(x_skip.unsqueeze(1), program).squeeze(1)
-            x_skip, skip_is_raw = norm.transform(x_skip, in_place=program is not None), False
-        if fused_norm:
+            if remap is not None:
+                x_skip = ops.remap_columns((x_skip if x_skip.stride(-1) == 1 else x_skip.contiguous()).unsqueeze(1), remap,
+                                           out=x_skip.unsqueeze(1) if program is not None else None).squeeze(1)
+            x_skip, skip_is_raw = norm.transform(x_skip, in_place=program is not None or remap is not None), False
+        if fused_norm and remap is not None:
+            mul, add = norm.column_program(x_skip.shape[-1])
+            x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add, impute=program, remap=remap).view(1, 1, 1, N, -1)
+        elif fused_norm:
             mul, add = norm.column_program(x_skip.shape[-1])
             x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add, impute=program).view(1, 1, 1, N, -1)
         elif fusable and x_out.dtype == dtype and x_skip.dtype == dtype:
@@ -329,6 +364,8 @@ class AnemoiModelEncProcDec(nn.Module):
             # SkipConnection._expand_time (layers/residual.py:53-57): the skip is repeated over the output steps
             skip = x_skip.unsqueeze(1).expand(-1, self.n_step_output, -1, -1, -1)
             x_out.index_add_(-1, out_idx, (skip if compact else skip.index_select(-1, in_idx)).to(dtype))
+        if post_members is not None:
+            return self._extended_output_program(x_out, ds, post_members, imputer, nan_mask)
         nan_ops = [] if nan_mask is None else imputer.inverse_program(x_out.shape[-1])
         if len(self.boundings[ds]) or denorm is not None or nan_ops:
             # all configured boundings (configuration order) and, fused, the output de-normalisation as ONE in-place column program
@@ -357,6 +394,37 @@ class AnemoiModelEncProcDec(nn.Module):
                     ops.bound_columns_(x_out, tables.ops, tables.params, nan_mask=nan_mask, n_nan_ops=tables.n_nan_ops)
                 else:
                     ops.bound_columns_(x_out, *tables)
+        return x_out
+
+    def _extended_output_program(self, x_out: Tensor, ds: str, members: list, imputer, nan_mask: Optional[Tensor]) -> Tensor:
+        """The boundings, then the inverse ops of every member of the post chain, last member first, as ONE in-place launch of the extended
+        column program.  The imputer's NaN restoration is part of it when its mask was written by the input assembly (``nan_mask``); when the
+        imputer ran stand-alone, ``forward`` restores after this (no post-processor stands before an imputer in a fusable chain)."""
+        from ..layers.bounding import apply_program_torch, extended_program_tables
+        from ..preprocessing import BaseImputer
+
+        if torch.is_grad_enabled() and x_out.requires_grad:
+            x_out = apply_program_torch(x_out, [op for b in self.boundings[ds] for op in b.program()])
+            for member in reversed(members):
+                if not (isinstance(member, BaseImputer) and nan_mask is None):
+                    x_out = member.inverse_transform(x_out, in_place=False)
+            return x_out
+        if not x_out.is_contiguous():
+            x_out = x_out.contiguous()
+        # (built once per chain and normaliser state, as the tables of the plain program)
+        state = tuple((id(m), m._norm_mul._version, m._norm_add._version) if hasattr(m, "_norm_mul") else (id(m),) for m in members)
+        key = (ds, str(x_out.device), "ext", nan_mask is not None) + state
+        if key not in self._bound_tables:
+            width = x_out.shape[-1]
+            prog = [op for b in self.boundings[ds] for op in b.program()]
+            for member in reversed(members):
+                if isinstance(member, BaseImputer) and nan_mask is None:
+                    continue
+                prog += member.inverse_program(width)
+            self._bound_tables[key] = extended_program_tables(prog, width, x_out.device)
+        tables = self._bound_tables[key]
+        if tables[0].shape[0]:
+            ops.column_program_(x_out, *tables, nan_mask=nan_mask)
         return x_out
 
     @scoped_forward
@@ -397,14 +465,14 @@ class AnemoiModelEncProcDec(nn.Module):
         for ds in names:
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
             norm_in, norm_out, *rest = (_fused_norm or {}).get(ds, (None, None))
-            imputer = rest[0] if rest else None
-            x_data_latent, x_skip, raw, nan_mask = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds, norm=norm_in,
-                                                                        imputer=imputer)
+            imputer, remapper, post_members = (tuple(rest) + (None, None, None))[:3]
+            x_data_latent, x_skip, raw, nan_mask, remap_fused = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds,
+                                                                                     norm=norm_in, imputer=imputer, remapper=remapper)
             if nan_mask is not None:  # the nan_locations the imputer's own transform would have left; no loss mask at inference
                 imputer.record_nan_locations(nan_mask.unsqueeze(0), nan_mask.shape[-1], loss_mask=False)
             if self._truncated[ds]:  # once per dataset and forward: down (columns, normaliser), up; the skip is then normalised
                 x_skip, raw = self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data), False
-            skips[ds], data_shards[ds] = _EdgeState(x_skip, raw, norm_in, norm_out, imputer, nan_mask), shard_sizes_data
+            skips[ds], data_shards[ds] = _EdgeState(x_skip, raw, norm_in, norm_out, imputer, nan_mask, remapper, remap_fused, post_members), shard_sizes_data
             if (_SIDE_JOB and carrier is not None and model_comm_group is None and not torch.is_grad_enabled()
                     and isinstance(self.decoder[ds], GraphTransformerBackwardMapper)):
                 side_job = carrier.side_job = self.decoder[ds].destination_side_job(x_data_latent, _SIDE_PANELS_PER_RIDER)
@@ -444,7 +512,8 @@ class AnemoiModelEncProcDec(nn.Module):
                 LAST_SIDE_JOB_PANELS = (side_job.hosted, side_job.n_panels - side_job.hosted)
             e = skips[ds]
             out[ds] = self._assemble_output(x_out, e.x_skip, batch_size, ensemble_size, x[ds].dtype, ds, norm=e.norm_in, skip_is_raw=e.skip_is_raw,
-                                            denorm=e.norm_out, compact=self._truncated[ds], imputer=e.imputer, nan_mask=e.nan_mask)
+                                            denorm=e.norm_out, compact=self._truncated[ds], imputer=e.imputer, nan_mask=e.nan_mask,
+                                            remapper=e.remapper, remap_fused=e.remap_fused, post_members=e.post_members)
             if e.imputer is not None and e.nan_mask is None:  # imputed by the stand-alone kernel on the way in: restored by its counterpart
                 out[ds] = e.imputer.inverse_transform(out[ds].contiguous(), in_place=True)  # (several output steps: a permuted clone)
         return out
@@ -454,19 +523,31 @@ class AnemoiModelEncProcDec(nn.Module):
     def _edge_chain(procs, inverse: bool):
         """(imputer or None, InputNormalizer) of a ``Processors`` chain the model edge can fuse - the normaliser alone, or one imputer followed
         by the normaliser (the members of an inverse chain are stored in the same order and applied last to first) - else None: two
-        imputers, an imputer after the normaliser or a member of any other type stay opaque processors."""
-        from ..preprocessing import BaseImputer, InputNormalizer, Processors
+        imputers, an imputer after the normaliser or a member of any other type stay opaque processors.
+
+        A chain [imputer]? [Remapper]? InputNormalizer with post-processors (``Postprocessor`` family: the identity going forward) anywhere
+        after the imputer fuses as well and comes back as (imputer or None, InputNormalizer, Remapper or None, members): ``members`` is the
+        whole list in its stored order, from which the output column program takes every member's inverse ops, last member first.  A
+        post-processor BEFORE the imputer would have to run after the NaN restoration, which a stand-alone imputer performs after the
+        program: such a chain stays opaque, as does a Remapper after the normaliser."""
+        from ..preprocessing import BaseImputer, InputNormalizer, Postprocessor, Processors, Remapper
 
         if isinstance(procs, InputNormalizer):
             return None, procs
         if not isinstance(procs, Processors) or procs.inverse != inverse:
             return None
         members = list(procs.processors.values())
-        if len(members) == 1 and isinstance(members[0], InputNormalizer):
-            return None, members[0]
-        if len(members) == 2 and isinstance(members[0], BaseImputer) and isinstance(members[1], InputNormalizer):
-            return members[0], members[1]
-        return None
+        core = [m for m in members if not isinstance(m, Postprocessor)]
+        if not core or not isinstance(core[-1], InputNormalizer):
+            return None
+        imputer = core[0] if isinstance(core[0], BaseImputer) else None
+        rest = core[1:-1] if imputer is not None else core[:-1]
+        if len(rest) > 1 or (rest and type(rest[0]) is not Remapper) or (imputer is not None and members[0] is not imputer):
+            return None
+        remapper = rest[0] if rest else None
+        if remapper is None and len(core) == len(members):
+            return imputer, core[-1]
+        return imputer, core[-1], remapper, members
 
     def predict_step(self, batch: dict, pre_processors, post_processors, n_step_input: int, model_comm_group=None,
                      gather_out: bool = True, **kwargs) -> dict:
@@ -476,7 +557,10 @@ class AnemoiModelEncProcDec(nn.Module):
         the inverse inside the output column program - no pass of its own over the data.  The chain [one imputer, input normaliser]
         (and the inverse chain over the same two modules) is fused likewise: the imputation program runs in the same kernels, the NaN mask
         of the first step is written by the input assembly and read by the output column program, and the imputer's ``nan_locations`` is
-        what its own transform would have left.  Any other chain goes through the modules."""
+        what its own transform would have left.  A ``Remapper`` between the imputer and the normaliser and post-processors
+        (``Postprocessor`` family) anywhere after the imputer fuse too (``_edge_chain``): the remap program follows the imputation program
+        in the assembly kernels, and the output column program holds every member's inverse ops in inverse-chain order.  Any other chain
+        goes through the modules."""
         from ..distributed.primitives import gather_tensor
 
         with torch.no_grad():
@@ -492,13 +576,20 @@ class AnemoiModelEncProcDec(nn.Module):
             fused = {}
             for ds in names:
                 pre, post = self._edge_chain(pre_processors[ds], False), self._edge_chain(post_processors[ds], True)
-                if pre is not None and post is not None and pre[0] is post[0] and x[ds].is_cuda:
-                    imputer, pre, post = pre[0], pre[1], post[1]
-                    fused[ds] = (pre, post) if imputer is None else (pre, post, imputer)
+                same = pre is not None and post is not None and len(pre) == len(post) and pre[0] is post[0]
+                if same and len(pre) == 4:  # a Remapper or post-processors: the same modules in the same order (the normalisers may be two)
+                    same = len(pre[3]) == len(post[3]) and all(a is b or (a is pre[1] and b is post[1]) for a, b in zip(pre[3], post[3]))
+                if same and x[ds].is_cuda:
+                    imputer, remapper, members = pre[0], (pre[2] if len(pre) == 4 else None), (post[3] if len(post) == 4 else None)
+                    pre, post = pre[1], post[1]
+                    fused[ds] = (pre, post) if imputer is None and members is None else (pre, post, imputer, remapper, members)
                     check = getattr(pre_processors[ds], "check_first_batch", None)
                     if check is not None and getattr(pre_processors[ds], "_awaiting_first_batch", False):
-                        # the chain's one-off NaN check survives the fusion: the member modules run once, on a copy
+                        # the chain's one-off NaN check survives the fusion: the member modules run once, on a copy (with the remapper's
+                        # domain assertion, which the fused kernels do not evaluate)
                         first = x[ds] if imputer is None else imputer.transform(x[ds], in_place=False)
+                        if remapper is not None:
+                            first = remapper.transform(first if first.stride(-1) == 1 else first.contiguous(), in_place=imputer is not None)
                         check(pre.transform(first, in_place=False))
                 else:
                     x[ds] = pre_processors[ds](x[ds], in_place=False)

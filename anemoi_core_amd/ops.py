@@ -1523,12 +1523,14 @@ def restore_nan_columns(x: Tensor, mask: Tensor, src_of: Tensor, out: Optional[T
 
 
 def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Optional[Tensor] = None, col_add: Optional[Tensor] = None,
-                   out_dtype: Optional[torch.dtype] = None, *, impute: Optional[ImputeProgram] = None, nan_mask: Optional[Tensor] = None) -> Tensor:
+                   out_dtype: Optional[torch.dtype] = None, *, impute: Optional[ImputeProgram] = None, nan_mask: Optional[Tensor] = None,
+                   remap: Optional["RemapProgram"] = None) -> Tensor:
     """x [T, N, V] (time slices of one batch / ensemble member), attrs [N, A] -> [N, width] = [x[0] | ... | x[T-1] | attrs | 0...].
     With ``col_mul`` / ``col_add`` (fp32 [V]) the time / variable columns become x * mul[v] + add[v] (the input normaliser as a
     column program); ``out_dtype``: the model dtype when x is fp32 data fed to a 16-bit model (default: x's dtype).
     ``impute`` (with ``nan_mask`` bool [N, V]): every raw element is imputed within its own time step before the normaliser, and
-    nan_mask receives the NaN locations of step 0."""
+    nan_mask receives the NaN locations of step 0.  ``remap`` (the FORWARD program of a remapper over the V columns): every raw element
+    is remapped after the imputation and before the normaliser."""
     _dev(x, attrs, col_mul, col_add)
     T, N, V = x.shape
     A = 0 if attrs is None else attrs.shape[1]
@@ -1537,6 +1539,22 @@ def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Opti
         raise ValueError("assemble_input: x must be [T, N, V] with contiguous variables, attrs [N, A] of the output dtype")
     out = torch.empty((N, width), dtype=odt, device=x.device)
     ap, lda = _rows(attrs, "attrs", odt)
+    if remap is not None:
+        if (impute is None) != (nan_mask is None):
+            raise ValueError("assemble_input: impute and nan_mask go together")
+        if (col_mul is None) != (col_add is None):
+            raise ValueError("assemble_input: col_mul and col_add go together")
+        if x.dtype != odt and x.dtype != torch.float32:
+            raise ValueError("assemble_input: x must be in the output dtype or fp32")
+        kp, vp = (0, 0) if impute is None else _impute_ptrs(impute, V, "assemble_input")
+        mp = 0 if nan_mask is None else _bool_mask(nan_mask, (N, V), "assemble_input").data_ptr()
+        if impute is not None:
+            _dev(x, impute.kind_src, impute.value, nan_mask)
+        op, pp = _remap_ptrs(remap, V, "assemble_input")
+        _lib.check(_lib.load().anemoi_assemble_input_remap(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, kp, vp, mp, V, op, pp,
+                                                           _vec(col_mul, "col_mul", V, torch.float32), _vec(col_add, "col_add", V, torch.float32), ap, lda,
+                                                           A, out.data_ptr(), width, width, N, _DT[odt], _stream()), "assemble_input_remap")
+        return out
     if impute is not None or nan_mask is not None:
         if impute is None or nan_mask is None:
             raise ValueError("assemble_input: impute and nan_mask go together")
@@ -1567,16 +1585,28 @@ def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Opti
 
 
 def assemble_output(x_out: Tensor, x_skip: Tensor, col_map: Tensor, col_mul: Optional[Tensor] = None, col_add: Optional[Tensor] = None, *,
-                    impute: Optional[ImputeProgram] = None) -> Tensor:
+                    impute: Optional[ImputeProgram] = None, remap: Optional["RemapProgram"] = None) -> Tensor:
     """out[n, v] = x_out[n, v] + x_skip[n, col_map[v]] (where col_map[v] >= 0); x_out [N, V_out], x_skip [N, V_in] (row
     stride allowed), col_map int32 [V_out].  With ``col_mul`` / ``col_add`` (fp32 [V_in]) the skip is the RAW input, normalised
     on the fly (x_skip * mul[m] + add[m]); the result has x_skip's dtype (the model dtype or fp32).  ``impute`` (over the V_in columns):
-    the raw skip is imputed before it is normalised."""
+    the raw skip is imputed before it is normalised.  ``remap`` (the FORWARD program of a remapper over the V_in columns): the raw skip is
+    remapped after the imputation and before the normaliser."""
     _dev(x_out, x_skip, col_map, col_mul, col_add)
     N, V = x_out.shape
     out = torch.empty((N, V), dtype=x_skip.dtype, device=x_out.device)
     (xp, ldx), (sp, lds) = _rows(x_out, "x_out"), _rows(x_skip, "x_skip")
     Vin = x_skip.shape[1]
+    if remap is not None:
+        if x_skip.dtype != x_out.dtype and x_skip.dtype != torch.float32:
+            raise ValueError("assemble_output: x_skip must be in x_out's dtype or fp32")
+        kp, vp = (0, 0) if impute is None else _impute_ptrs(impute, Vin, "assemble_output")
+        if impute is not None:
+            _dev(x_out, impute.kind_src, impute.value)
+        op, pp = _remap_ptrs(remap, Vin, "assemble_output")
+        _lib.check(_lib.load().anemoi_assemble_output_remap(xp, ldx, _dt(x_out), sp, lds, _vec(col_map, "col_map", V, torch.int32), kp, vp, op, pp,
+                                                            _vec(col_mul, "col_mul", Vin, torch.float32), _vec(col_add, "col_add", Vin, torch.float32),
+                                                            out.data_ptr(), V, N, V, _dt(x_skip), _stream()), "assemble_output_remap")
+        return out
     if impute is not None:
         _dev(x_out, impute.kind_src, impute.value)
         kp, vp = _impute_ptrs(impute, Vin, "assemble_output")
@@ -1630,6 +1660,91 @@ def bound_columns_(x: Tensor, op_table: Tensor, param_table: Tensor, *, nan_mask
             raise ValueError(f"bound_columns_: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
     _lib.check(_lib.load().anemoi_bound_columns_mask(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
                                                      mp, vm, vm, int(n_nan_ops), _dt(x), _stream()), "bound_columns_mask")
+    return x
+
+
+class RemapProgram(NamedTuple):
+    """One direction of a remapper on the device (include/anemoi_hip.h): ``op_flags`` int32 [V, 2] = (remap op, flags), ``par`` fp32 [V, 4],
+    ``active`` int32: the columns whose op is not 0 (none)."""
+    op_flags: Tensor
+    par: Tensor
+    active: Tensor
+
+
+REMAP_OPS = 16  # the remap ops are 0 (none) .. 16 (affine inverse), include/anemoi_hip.h
+
+
+def remap_program(entries, device) -> RemapProgram:
+    """Build the device tables from one host entry per column: ``(op, flags, p0, p1, p2, p3)``, op 0 = the column is left alone."""
+    V = len(entries)
+    for c, e in enumerate(entries):
+        if len(e) != 6 or not 0 <= int(e[0]) <= REMAP_OPS:
+            raise ValueError(f"remap_program: column {c}: expected (op in 0..{REMAP_OPS}, flags, p0, p1, p2, p3), got {e}")
+    of = torch.tensor([[int(e[0]), int(e[1])] for e in entries], dtype=torch.int32).reshape(V, 2)
+    par = torch.tensor([[float(p) for p in e[2:]] for e in entries], dtype=torch.float32).reshape(V, 4)
+    active = torch.tensor([c for c, e in enumerate(entries) if int(e[0]) != 0], dtype=torch.int32)
+    return RemapProgram(of.to(device), par.to(device), active.to(device))
+
+
+def _remap_ptrs(program: RemapProgram, V: int, what: str) -> tuple[int, int]:
+    of, par, _ = program
+    _dev(of, par)
+    if of.shape != (V, 2) or of.dtype != torch.int32 or not of.is_contiguous() or par.shape != (V, 4) or par.dtype != torch.float32 or not par.is_contiguous():
+        raise ValueError(f"{what}: the remap program must be contiguous int32 [{V}, 2] and fp32 [{V}, 4], got {tuple(of.shape)} {of.dtype}, "
+                         f"{tuple(par.shape)} {par.dtype}")
+    return of.data_ptr(), par.data_ptr()
+
+
+def remap_columns(x: Tensor, program: RemapProgram, inverse: bool = False, out: Optional[Tensor] = None, violations: Optional[Tensor] = None) -> Tensor:
+    """Remapper.transform / inverse_transform as one kernel: x [batch, time, grid, V] or [batch, time, ensemble, grid, V] (any strides,
+    columns contiguous).  ``program``: the tables of ONE direction, or a (forward, inverse) pair from which ``inverse`` picks.  ``out``: x
+    itself (in place: only the remapped columns are loaded and stored) or a tensor of x's shape (default: a new one).  ``violations``:
+    int32 [V], entry c incremented per element of column c that fails the reference's forward domain assertion (x >= 0 under a power
+    without clipping)."""
+    if not isinstance(program, RemapProgram):
+        program = program[1 if inverse else 0]
+    of, par, active = program
+    _dev(x, of, par, active, out, violations)
+    if x.dim() not in (4, 5) or x.stride(-1) != 1:
+        raise ValueError(f"remap_columns: x must be [batch, time, (ensemble,) grid, vars] with contiguous variables, got {tuple(x.shape)}")
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    if y.shape != x.shape or y.dtype != x.dtype or y.stride(-1) != 1:
+        raise ValueError("remap_columns: out must match x")
+    x5, y5 = (x.unsqueeze(2), y.unsqueeze(2)) if x.dim() == 4 else (x, y)
+    B, T, E, N, V = x5.shape
+    _remap_ptrs(program, V, "remap_columns")
+    if active.dtype != torch.int32 or active.dim() != 1 or active.shape[0] > V or not active.is_contiguous():
+        raise ValueError("remap_columns: program.active must be contiguous int32 [<= V]")
+    vp = 0 if violations is None else _vec(violations, "violations", V, torch.int32)
+    in_place = y5.data_ptr() == x5.data_ptr() and y5.stride() == x5.stride()
+    if not in_place and y5.data_ptr() == x5.data_ptr():
+        raise ValueError("remap_columns: out aliases x with other strides")
+    if x5.numel() and (active.shape[0] or not in_place):
+        ap, na = (active.data_ptr(), active.shape[0]) if in_place else (0, V)
+        _lib.check(_lib.load().anemoi_remap_columns(x5.data_ptr(), *x5.stride()[:4], y5.data_ptr(), *y5.stride()[:4], of.data_ptr(), par.data_ptr(), ap, na,
+                                                    vp, B, T, E, N, V, _dt(x), _stream()), "remap_columns")
+    return y
+
+
+def column_program_(x: Tensor, op_table: Tensor, param_table: Tensor, *, nan_mask: Optional[Tensor] = None) -> Tensor:
+    """In place: the ordered column program of ``bound_columns_`` with the kinds of the post-processors and the remapper's inverse
+    (anemoi_column_program: 11 fill where the masking column is 0, 12 NaN where it is NaN, 16 + remap op) over x [..., V].  Columns are
+    checked against V when the tables are built (``layers.bounding.extended_program_tables``)."""
+    _dev(x, op_table, param_table, nan_mask)
+    if not x.is_contiguous():
+        raise ValueError("column_program_: x must be contiguous")
+    V = x.shape[-1]
+    if op_table.dim() != 2 or op_table.shape[1] != 4 or op_table.dtype != torch.int32 or not op_table.is_contiguous() or \
+            tuple(param_table.shape) != (op_table.shape[0], 2) or param_table.dtype != torch.float32 or not param_table.is_contiguous():
+        raise ValueError("column_program_: the tables must be contiguous int32 [n_ops, 4] and fp32 [n_ops, 2]")
+    mp = vm = 0
+    if nan_mask is not None:
+        vm = nan_mask.shape[-1]
+        mp = _bool_mask(nan_mask, nan_mask.shape, "column_program_").data_ptr()
+        if nan_mask.numel() != (x.numel() // V) * vm:
+            raise ValueError(f"column_program_: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
+    _lib.check(_lib.load().anemoi_column_program(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
+                                                 mp, vm, vm, _dt(x), _stream()), "column_program")
     return x
 
 

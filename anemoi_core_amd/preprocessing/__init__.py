@@ -1,5 +1,6 @@
-"""Pre- / post-processors at the model edge (scope row f4): the input normaliser and the imputers (InputImputer, ConstantImputer,
-CopyImputer - imputer.py) that precede it in the chains of datasets with masked fields.
+"""Pre- / post-processors at the model edge (scope row f4): the input normaliser, the imputers (InputImputer, ConstantImputer,
+CopyImputer - imputer.py) that precede it in the chains of datasets with masked fields, the Remapper (remapper.py) and the post-processors
+(Postprocessor, NormalizedReluPostprocessor, ConditionalZeroPostprocessor, ConditionalNaNPostprocessor - postprocessor.py).
 
 Written from the documented behaviour of the reference's ``anemoi.models.preprocessing`` package, not from its text:
 
@@ -15,7 +16,9 @@ State_dict keys (``processors.<name>.<buffer>``) are those of the reference, so 
 path ``AnemoiModelEncProcDec.predict_step`` does not call these modules at all when the chain is a lone ``InputNormalizer``:
 the affine map becomes a column program of the assembly kernels; ``Processors.check_first_batch`` keeps the NaN check there.  The
 chain [one imputer, ``InputNormalizer``] is fused the same way: the imputation program rides in the same kernels, the NaN mask of the first
-time step is written by the input assembly and read by the output column program."""
+time step is written by the input assembly and read by the output column program.  A Remapper between the imputer and the normaliser and
+post-processors anywhere after the imputer fuse as well (the remap program in the assembly kernels, every inverse op in the output column
+program)."""
 from __future__ import annotations
 
 import logging
@@ -136,3 +139,6 @@ class Processors(nn.Module):
 
 from .normalizer import InputNormalizer  # noqa: E402,F401
 from .imputer import BaseImputer, ConstantImputer, CopyImputer, InputImputer  # noqa: E402,F401
+from .remapper import Remapper  # noqa: E402,F401
+from .postprocessor import (ConditionalNaNPostprocessor, ConditionalPostprocessor, ConditionalZeroPostprocessor,  # noqa: E402,F401
+                            NormalizedReluPostprocessor, Postprocessor)

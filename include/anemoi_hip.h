@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 20
+#define ANEMOI_HIP_ABI_VERSION 21
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -392,6 +392,45 @@ int anemoi_assemble_output_impute(const void* x_out, int64_t ldx, anemoi_dtype_t
  * mask == NULL otherwise forwards to anemoi_bound_columns. */
 int anemoi_bound_columns_mask(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
                               const void* mask, int64_t ldm, int32_t n_mask_cols, int32_t n_nan_ops, anemoi_dtype_t dtype, void* stream);
+
+/* ---- remapper and post-processors at the model edges ----------------------------------------------------------------------------
+ * The reference's Remapper (preprocessing/remapper.py, mappings.py) maps single variables through log1p / sqrt / power / boxcox / atanh /
+ * asinh / displaced boundary atoms / an affine map before the normaliser, and back on the output; its post-processors
+ * (preprocessing/postprocessor.py) clamp output variables or fill them where a masking variable is zero / NaN.  A REMAP OP is one
+ * direction of one map: 0 none, 1 log1p, 2 expm1, 3 power, 4 power inverse, 5 boxcox, 6 boxcox inverse, 7 log, 8 exp, 9 atanh,
+ * 10 atanh inverse, 11 asinh, 12 asinh inverse, 13 displace atoms, 14 clamp, 15 affine, 16 affine inverse; flags: 1 clip negatives,
+ * 2 tangent-linear above one, 4 / 8 a lower / upper bound exists, bits 4..7 how the power is taken (0 powf, 1 sqrt, 2 x*x, 3 x*x*x,
+ * 4 copy - torch's scalar pow).  Every step of a map rounds to the data dtype, as the reference's in-place torch ops do; where a map
+ * divides by a scalar parameter the table holds its fp32 reciprocal and the kernel multiplies, as torch's device kernels do. */
+
+/* Stand-alone Remapper.transform / inverse_transform over x [batch, time, ensemble, grid, V] (element strides ld_b .. ld_n, columns
+ * contiguous; y likewise and may alias x).  op_flags int32 [V][2] = (remap op, flags), par fp32 [V][4] (8- / 16-byte aligned).
+ * active int32 [n_active]: the columns whose op is not 0 - only those are loaded and stored (required in place); NULL: all V columns (out
+ * of place).  violations (NULL: none): int32 [V], entry c counts the elements of column c that fail the reference's forward domain assertion. */
+int anemoi_remap_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_e, int64_t ld_n, void* y, int64_t yd_b, int64_t yd_t,
+                         int64_t yd_e, int64_t yd_n, const int32_t* op_flags, const float* par, const int32_t* active, int32_t n_active,
+                         int32_t* violations, int32_t B, int32_t T_steps, int32_t E, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream);
+
+/* anemoi_assemble_input_impute for the chain [imputer]? Remapper InputNormalizer: every raw element is imputed (kind_src / value / mask
+ * all NULL: the chain has no imputer), then mapped by the remap program (op_flags int32 [V][2], par fp32 [V][4], each step rounded to the
+ * RAW dtype), then normalised.  mask: the NaN locations of step 0 of the raw input.  Same scalar / 8-column routes. */
+int anemoi_assemble_input_remap(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
+                                const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const int32_t* op_flags, const float* par,
+                                const float* col_mul, const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo,
+                                int32_t W, int32_t n_rows, anemoi_dtype_t dtype, void* stream);
+
+/* anemoi_assemble_output_impute whose RAW skip goes through the same chain (the tables span the skip's columns; kind_src / value NULL:
+ * no imputer). */
+int anemoi_assemble_output_remap(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
+                                 const int32_t* col_map, const int32_t* kind_src, const float* value, const int32_t* op_flags, const float* par,
+                                 const float* col_mul, const float* col_add, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols,
+                                 anemoi_dtype_t dtype, void* stream);
+
+/* anemoi_bound_columns_mask (mask may be NULL with n_mask_cols = 0) with further op kinds: 11 "p0 where x[n, total column] == 0",
+ * 12 "NaN where x[n, total column] is NaN" - both read the row as the ops before them left it - and 16 + r: remap op r, with
+ * flags = ops[i][3] and its third parameter as the float bits of ops[i][2].  Kinds 1..10 are those of anemoi_bound_columns_mask. */
+int anemoi_column_program(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
+                          const void* mask, int64_t ldm, int32_t n_mask_cols, anemoi_dtype_t dtype, void* stream);
 
 /* ---- device-initiated row exchange between the ranks of a model-parallel group (scope row e) ----------------------------
  * The reference exchanges node rows with host-issued NCCL collectives: the per-layer halo all-to-all
