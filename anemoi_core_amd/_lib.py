@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -108,6 +108,8 @@ SIGNATURES = {
     "anemoi_gnn_node_chain_fwd": ([_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _i64, _p, _p, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_peer_exchange_rows": ([_p, _i64, _p, _p, _i32, _i32, _i32, _p, _p, _i64, _p], C.c_int),
     "anemoi_window_attention_fwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, C.c_int, _p], C.c_int),
+    "anemoi_window_attention_bwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _i32,
+                                     _i32, _f, _f, _p, _i32, C.c_int, _p], C.c_int),
     "anemoi_sparse_project_fwd": ([_p, _i64, _i64, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, C.c_int, C.c_int, _p], C.c_int),
 }
 

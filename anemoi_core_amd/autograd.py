@@ -1,5 +1,5 @@
 """Autograd glue for the training path (scope row f1): torch.autograd.Functions whose forward AND backward are the HIP
-kernels of this package.  ``ops.linear`` / ``ops.layer_norm`` route here whenever autograd is recording; the attention op
+kernels of this package.  ``ops.linear`` / ``ops.layer_norm`` / ``ops.window_attention`` route here whenever autograd is recording; the edge attention op
 carries its own registration (``ops.graph_transformer_attention``).
 
 Linear backward (reference: autograd of torch.nn.Linear as instantiated by layer_kernels, layers/utils.py:107-121):
@@ -373,3 +373,61 @@ def pack_edge_features(edge_attr: Tensor) -> Tensor:
 
 def fused_edge_attention(spec: dict, bufs, feat: Tensor, lin_edge, csc: "ops.CSC", num_heads: int, reverse) -> Tensor:
     return FusedEdgeAttentionFunction.apply(spec, csc, num_heads, reverse, feat, lin_edge.weight, lin_edge.bias, *bufs)
+
+
+class WindowAttentionFunction(torch.autograd.Function):
+    """``ops.window_attention`` with its HIP backward (csrc/window_attention_bwd.hip).  Returns (out, lse); the lse carries no gradient,
+    nor do the ALiBi slopes (they are no parameters in the reference)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads, window, scale, softcap, alibi_slopes, batch_size):
+        kw = dict(scale=scale, softcap=softcap, alibi_slopes=alibi_slopes, batch_size=batch_size)
+        out, lse = ops._window_attention_fwd(q, k, v, num_heads, window, return_lse=True, **kw)
+        ctx.H, ctx.window, ctx.kw = num_heads, window, kw
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, d_out, _d_lse):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = ops.window_attention_bwd(d_out.contiguous(), q, k, v, out, lse, ctx.H, ctx.window, **ctx.kw)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+class WindowAttentionQKVFunction(torch.autograd.Function):
+    """The same attention with q | k | v given as the ONE [rows, 3A] projection buffer they were computed into (the Transformer block's
+    case): the backward kernels write dq / dk / dv into the three column slices of one [rows, 3A] gradient, so autograd sees a single
+    gradient for the GEMM output instead of three zero-padded slice gradients and their sums (cf. FusedAttentionFunction)."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads, window, scale, softcap, alibi_slopes, batch_size):
+        A = qkv.shape[1] // 3
+        kw = dict(scale=scale, softcap=softcap, alibi_slopes=alibi_slopes, batch_size=batch_size)
+        out, lse = ops._window_attention_fwd(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], num_heads, window, return_lse=True, **kw)
+        ctx.H, ctx.window, ctx.kw = num_heads, window, kw
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, d_out, _d_lse):
+        qkv, out, lse = ctx.saved_tensors
+        A = qkv.shape[1] // 3
+        grad = torch.empty_like(qkv, memory_format=torch.contiguous_format)
+        ops.window_attention_bwd(d_out.contiguous(), qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], out, lse, ctx.H, ctx.window,
+                                 grads_out=(grad[:, :A], grad[:, A:2 * A], grad[:, 2 * A:]), **ctx.kw)
+        return grad, None, None, None, None, None, None
+
+
+def window_attention_qkv(qkv: Tensor, num_heads: int, window: Optional[int], *, scale: Optional[float] = None, softcap: Optional[float] = None,
+                         alibi_slopes: Optional[Tensor] = None, batch_size: int = 1) -> Tensor:
+    """``ops.window_attention`` of the column thirds of ``qkv`` [rows, 3A], differentiable in ``qkv`` as a whole."""
+    if qkv.dim() != 2 or qkv.shape[1] % 3 or (qkv.shape[1] // 3) % num_heads:
+        raise ValueError(f"qkv must be [rows, 3 * heads * d], got {tuple(qkv.shape)} for {num_heads} heads")
+    d = qkv.shape[1] // 3 // num_heads
+    if d not in ops.WINDOW_HEAD_DIMS:
+        raise ValueError(f"window_attention: head dimension {d} not supported; supported: {set(ops.WINDOW_HEAD_DIMS)}")
+    if batch_size <= 0 or qkv.shape[0] % batch_size:
+        raise ValueError(f"rows {qkv.shape[0]} not divisible by batch_size {batch_size}")
+    return WindowAttentionQKVFunction.apply(qkv, num_heads, window, scale, softcap, alibi_slopes, batch_size)[0]

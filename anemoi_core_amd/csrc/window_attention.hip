@@ -15,7 +15,7 @@
 // an exact 0; the masks are evaluated only on the tiles that cross a band or sequence edge.
 //
 // fp32 path: one wave per (query, head), plain and exact (expf, sequential dots) - a correctness path, not a fast one.
-#include "common.h"
+#include "window_attention_core.h"
 
 namespace anemoi {
 
@@ -24,13 +24,6 @@ namespace {
 constexpr int kWinWaves = 4;
 constexpr int kWinQ = 16 * kWinWaves;  // query rows per workgroup
 constexpr int kWinK = 64;              // keys per tile
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-
-using frag8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 struct WinArgs {
   const void* q;
@@ -47,20 +40,6 @@ struct WinArgs {
   float scale, softcap;
   hipStream_t stream;
 };
-
-__device__ __forceinline__ f32x4 mfma16(const frag8& a, const frag8& b, const f32x4& c, bf16_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a),
-                                                 __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const frag8& a, const frag8& b, const f32x4& c, f16_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) _Float16, a),
-                                                __builtin_bit_cast(__attribute__((ext_vector_type(8))) _Float16, b), c, 0, 0, 0);
-}
-
-template <typename T>
-__device__ __forceinline__ short to_bits(float x) {
-  return (short)__builtin_bit_cast(uint16_t, from_float<T>(x));
-}
 
 // the score of query i, key j from the raw dot product, in the log2 domain (FANCY: softcap and / or ALiBi)
 template <bool FANCY>
@@ -203,13 +182,7 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
 #pragma unroll
     for (int db = 0; db < D / 16; ++db) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const uint16_t* vr = vt_lds + (16 * db + c) * VS + 32 * s + 4 * g;
-        const u32x2 lo4 = *reinterpret_cast<const u32x2*>(vr);
-        const u32x2 hi4 = *reinterpret_cast<const u32x2*>(vr + 16);
-        const frag8 vf = __builtin_bit_cast(frag8, u32x4{lo4.x, lo4.y, hi4.x, hi4.y});
-        acc[db] = mfma16(vf, pf[s], acc[db], T{});
-      }
+      for (int s = 0; s < 2; ++s) acc[db] = mfma16(transposed_frag(vt_lds, VS, 16 * db + c, s, g), pf[s], acc[db], T{});
     }
   }
 

@@ -3,7 +3,8 @@ same constructor keywords, forward signature and state_dict keys (``lin_q``, ``l
 
 Both of the reference's ``attention_implementation`` values select the one HIP kernel (csrc/window_attention.hip), which has the
 flash-attention semantics: the sliding window, softcap and ALiBi.  ``use_rotary_embeddings`` is accepted and ignored, exactly as in the
-reference, whose TransformerProcessor never passes it to its blocks.  Inference only: the backward kernel is not built yet."""
+reference, whose TransformerProcessor never passes it to its blocks.  Training runs through csrc/window_attention_bwd.hip
+(``autograd.WindowAttentionFunction``); ``forbid_autograd`` names the three cases the backward kernel does not cover."""
 from __future__ import annotations
 
 import math
@@ -31,18 +32,32 @@ def get_alibi_slopes(num_heads: int) -> Tensor:
     return alibi_slopes
 
 
-def forbid_autograd(module: nn.Module, *tensors: Optional[Tensor], dropout_p: float = 0.0) -> None:
-    """The window attention has no backward kernel yet: fail before autograd would record through it."""
-    needs = torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors)
-                                         or any(p.requires_grad for p in module.parameters()))
-    if needs or (module.training and dropout_p > 0):
+def forbid_autograd(module: nn.Module, *tensors: Optional[Tensor], dropout_p: float = 0.0, model_comm_group=None) -> None:
+    """Fail before autograd would record through what the window attention's backward kernel does not cover: tensors off the GPU,
+    attention dropout, and heads sharded over a model-parallel group."""
+    name = type(module).__name__
+    if module.training and dropout_p > 0:
         raise NotImplementedError(
-            f"{type(module).__name__}: training through the window attention is not supported - its backward kernel is not built yet. "
-            "Run inference under torch.no_grad() / torch.inference_mode() (predict_step does), with dropout_p = 0 or in eval mode.")
+            f"{name}: attention dropout (dropout_p = {dropout_p}) is not in the window attention's backward kernel, nor in its forward. "
+            "Use dropout_p = 0, or eval mode for inference.")
+    if not torch.is_grad_enabled():
+        return
+    params = list(module.parameters())
+    if not (any(t is not None and t.requires_grad for t in tensors) or any(p.requires_grad for p in params)):
+        return
+    if any(t is not None and not t.is_cuda for t in (*tensors, *params)):
+        raise NotImplementedError(
+            f"{name}: training through the window attention needs its HIP backward kernel, which runs on the GPU only - there is no CPU "
+            "fallback. Move the module and its input to the device, or run inference under torch.no_grad() / torch.inference_mode().")
+    if model_is_distributed(model_comm_group):
+        raise NotImplementedError(
+            f"{name}: training with the heads sharded over a model-parallel group is not supported - the backward kernel is built for "
+            "unsharded heads only. Train on one GPU per model instance, or run inference under torch.no_grad().")
 
 
 class MultiHeadSelfAttention(nn.Module):
-    """Multi-head self-attention over (batch grid) rows with a sliding window of half-width ``window_size``."""
+    """Multi-head self-attention over (batch grid) rows with a sliding window of half-width ``window_size``.  Differentiable on the GPU:
+    the q|k|v GEMM, the qk-norm LayerNorms and the window attention each run their HIP backward kernel."""
 
     def __init__(self, num_heads: int, embed_dim: int, layer_kernels, attn_channels: Optional[int] = None, qkv_bias: bool = False,
                  qk_norm: bool = False, is_causal: bool = False, window_size: Optional[int] = None, dropout_p: float = 0.0,
@@ -95,9 +110,16 @@ class MultiHeadSelfAttention(nn.Module):
     def _window(self) -> int:
         return -1 if self.window_size is None else int(self.window_size)
 
-    def attend(self, q: Tensor, k: Tensor, v: Tensor, batch_size: int, shard_sizes=None, model_comm_group=None) -> Tensor:
-        """The attention of q, k, v [rows, A] (column slices of one projection are read in place) -> [rows, A], before ``projection``."""
+    def attend(self, q: Tensor, k: Tensor, v: Tensor, batch_size: int, shard_sizes=None, model_comm_group=None,
+               qkv: Optional[Tensor] = None) -> Tensor:
+        """The attention of q, k, v [rows, A] (column slices of one projection are read in place) -> [rows, A], before ``projection``.
+        ``qkv``: the [rows, 3A] buffer q, k, v are the thirds of; under autograd it receives ONE gradient written by the backward kernels."""
         H, d = self.num_heads, self.head_dim
+        if qkv is not None and not self.qk_norm and ops._needs_grad(qkv) and not model_is_distributed(model_comm_group):
+            from ..autograd import window_attention_qkv
+
+            return window_attention_qkv(qkv, H, self._window(), softcap=self.softcap if self.softcap else None,
+                                        alibi_slopes=self.slopes(qkv.device), batch_size=batch_size)
         if self.qk_norm:  # per-head LayerNorm over d, no bias (attention.py:206-208)
             q = self.q_norm(q.reshape(-1, H, d)).view(-1, H * d)
             k = self.k_norm(k.reshape(-1, H, d)).view(-1, H * d)
@@ -124,10 +146,10 @@ class MultiHeadSelfAttention(nn.Module):
         return back.reshape(P, n_loc, Hl * d).permute(1, 0, 2).reshape(n_loc, A)
 
     def forward(self, x: Tensor, grid_shard_sizes, batch_size: int, model_comm_group=None) -> Tensor:
-        forbid_autograd(self, x, dropout_p=self.dropout_p)
+        forbid_autograd(self, x, dropout_p=self.dropout_p, model_comm_group=model_comm_group)
         w = torch.cat([self.lin_q.weight, self.lin_k.weight, self.lin_v.weight], 0)
         b = None if self.lin_q.bias is None else torch.cat([self.lin_q.bias, self.lin_k.bias, self.lin_v.bias])
         qkv = ops.linear(x, w, b)
         A = self.attn_channels
-        o = self.attend(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], batch_size, grid_shard_sizes.nodes, model_comm_group)
+        o = self.attend(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], batch_size, grid_shard_sizes.nodes, model_comm_group, qkv=qkv)
         return ops.linear(o, self.projection.weight, self.projection.bias)

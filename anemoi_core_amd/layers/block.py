@@ -721,7 +721,9 @@ class GraphTransformerProcessorBlock(GraphTransformerBaseBlock):
 class TransformerProcessorBlock(BlockTail, BaseBlock):
     """Transformer block (reference block.py:123-196): ``x = x + projection(MHSA(LN_att(x)))``, ``x = x + MLP(LN_mlp(x))``.  Inference path:
     LayerNorm + q|k|v as one GEMM (or handed over by the previous tail), the window-attention kernel reading the column slices in place, and
-    the tail on the route ``BlockTail._tail_route`` picks - the GraphTransformer tail without the ``lin_self`` term."""
+    the tail on the route ``BlockTail._tail_route`` picks - the GraphTransformer tail without the ``lin_self`` term.  Training path: the same
+    GEMM under autograd, ``autograd.window_attention_qkv`` (one [rows, 3A] gradient written by csrc/window_attention_bwd.hip) and the "plain"
+    tail route."""
 
     folds_row_stats = True
 
@@ -772,7 +774,7 @@ class TransformerProcessorBlock(BlockTail, BaseBlock):
         from .attention import forbid_autograd
 
         att = self.attention
-        forbid_autograd(self, x, cond, dropout_p=att.dropout_p)
+        forbid_autograd(self, x, cond, dropout_p=att.dropout_p, model_comm_group=model_comm_group)
         carrier, extra = layer_kwargs.get("carrier"), layer_kwargs.get("extra_residual")
         ln, A = self.layer_norm_attention, att.attn_channels
         lins = [att.lin_q, att.lin_k, att.lin_v]
@@ -781,7 +783,7 @@ class TransformerProcessorBlock(BlockTail, BaseBlock):
         if qkv is None:
             w, b = self._fused.get("qkv", lins)
             qkv = ops.linear(apply_layer_norm(ln, x, cond), w, None if att.lin_q.bias is None else b)
-        o = att.attend(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], batch_size, shard_info.nodes, model_comm_group)
+        o = att.attend(qkv[:, :A], qkv[:, A:2 * A], qkv[:, 2 * A:], batch_size, shard_info.nodes, model_comm_group, qkv=qkv)
         return (self._post_attention(o, x, cond, carrier, extra),)
 
 

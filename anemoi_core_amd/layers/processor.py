@@ -107,8 +107,8 @@ class GraphTransformerProcessor(BaseProcessor):
 
 
 class TransformerProcessor(BaseProcessor):
-    """Stack of sliding-window self-attention blocks over the hidden rows (reference processor.py:204-316).  Inference only (the window
-    attention has no backward kernel yet).  The graph arguments it is given (``edge_attr``, ``edge_index``, ``edge_dim``) are ignored, as
+    """Stack of sliding-window self-attention blocks over the hidden rows (reference processor.py:204-316).  Trains through the window
+    attention's backward kernel (not with attention dropout, off the GPU or with sharded heads: ``layers.attention.forbid_autograd``).  The graph arguments it is given (``edge_attr``, ``edge_index``, ``edge_dim``) are ignored, as
     in the reference; so is ``use_rotary_embeddings``, which the reference accepts but never passes to its blocks."""
 
     def __init__(self, *, num_layers: int, num_channels: int, num_chunks: int, num_heads: int, mlp_hidden_ratio: float,

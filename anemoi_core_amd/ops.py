@@ -395,7 +395,8 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
     """Sliding-window multi-head self-attention (layers/attention.py MultiHeadSelfAttention with flash-attention semantics).  q, k, v:
     [batch * N, A] (column slices of one projection buffer are read in place), head h = columns [h d, (h+1) d), d = A / num_heads in
     WINDOW_HEAD_DIMS; query i attends keys j of its own sequence with |i - j| <= window (None or -1: all).  scale defaults to d^-1/2;
-    softcap > 0 caps the scores; alibi_slopes fp32 [num_heads].  Returns out [batch * N, A] (and the fp32 LSE [batch * N, num_heads])."""
+    softcap > 0 caps the scores; alibi_slopes fp32 [num_heads].  Returns out [batch * N, A] (and the fp32 LSE [batch * N, num_heads]).
+    Differentiable in q, k, v: with autograd recording it runs as ``autograd.WindowAttentionFunction`` (HIP backward kernel)."""
     if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape:
         raise ValueError(f"q, k and v must be 2-D of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
     rows, A = q.shape
@@ -406,9 +407,27 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
         raise ValueError(f"window_attention: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
     if batch_size <= 0 or rows % batch_size:
         raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    if _needs_grad(q, k, v):
+        from .autograd import WindowAttentionFunction
+
+        out, lse = WindowAttentionFunction.apply(q, k, v, num_heads, window, scale, softcap, alibi_slopes, batch_size)
+        return (out, lse) if return_lse else out
+    return _window_attention_fwd(q, k, v, num_heads, window, scale=scale, softcap=softcap, alibi_slopes=alibi_slopes, batch_size=batch_size,
+                                 return_lse=return_lse)
+
+
+def _window_scalars(d: int, window: Optional[int], scale: Optional[float], softcap: Optional[float]) -> tuple[int, float, float]:
+    """(window, scale, softcap) as the C ABI takes them: -1 = unbounded, the default scale d^-1/2, 0 = no cap."""
     w = -1 if window is None or window < 0 else int(min(window, 2**31 - 1))
-    scale = float(d ** -0.5 if scale is None else scale)
-    cap = float(softcap) if softcap is not None and softcap > 0 else 0.0
+    return w, float(d ** -0.5 if scale is None else scale), float(softcap) if softcap is not None and softcap > 0 else 0.0
+
+
+def _window_attention_fwd(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Optional[int], *, scale: Optional[float] = None,
+                          softcap: Optional[float] = None, alibi_slopes: Optional[Tensor] = None, batch_size: int = 1,
+                          return_lse: bool = False):
+    rows, A = q.shape
+    d = A // num_heads
+    w, scale, cap = _window_scalars(d, window, scale, softcap)
     ext = _ext.ops()
     if ext is not None:
         out, lse = ext.window_attention(q, k, v, num_heads, w, scale, cap, alibi_slopes, batch_size, return_lse)
@@ -422,6 +441,53 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
                                                  _vec(alibi_slopes, "alibi_slopes", num_heads, torch.float32), _dt(q), _stream())
     _lib.check(rc, "window_attention_fwd")
     return (out, lse) if return_lse else out
+
+
+WINDOW_BWD_QUERY_PASS, WINDOW_BWD_KEY_PASS = 1, 2  # include/anemoi_hip.h: ANEMOI_WINDOW_BWD_*
+
+
+def window_attention_bwd(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor, num_heads: int, window: Optional[int], *,
+                         scale: Optional[float] = None, softcap: Optional[float] = None, alibi_slopes: Optional[Tensor] = None,
+                         batch_size: int = 1, grads_out=None, delta: Optional[Tensor] = None,
+                         passes: int = WINDOW_BWD_QUERY_PASS | WINDOW_BWD_KEY_PASS):
+    """Gradients (dq, dk, dv) of ``window_attention`` (csrc/window_attention_bwd.hip: a query pass and a key pass, deterministic).
+    ``out`` / ``lse`` are the forward's results, the scalars the forward's.  ``grads_out`` = (dq, dk, dv): write the gradients into these
+    row-strided views, e.g. the three column slices of one [rows, 3A] gradient buffer.  ``delta``: the fp32 [rows, H] workspace the query
+    pass fills and the key pass reads (allocated here by default); ``passes`` runs one pass alone, for timing."""
+    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape or d_out.shape != q.shape:
+        raise ValueError("q, k, v, out and d_out must be 2-D of one shape")
+    rows, A = q.shape
+    if num_heads <= 0 or A % num_heads:
+        raise ValueError(f"channels {A} not divisible by heads {num_heads}")
+    d = A // num_heads
+    if d not in WINDOW_HEAD_DIMS:
+        raise ValueError(f"window_attention_bwd: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
+    if batch_size <= 0 or rows % batch_size:
+        raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    if tuple(lse.shape) != (rows, num_heads) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError(f"lse must be contiguous fp32 [{rows}, {num_heads}]")
+    w, scale, cap = _window_scalars(d, window, scale, softcap)
+    _dev(d_out, q, k, v, out, lse, alibi_slopes, delta)
+    if grads_out is None:
+        dq, dk, dv = (torch.empty((rows, A), dtype=q.dtype, device=q.device) for _ in range(3))
+    else:
+        dq, dk, dv = grads_out
+        if dq.shape != q.shape or dk.shape != q.shape or dv.shape != q.shape:
+            raise ValueError("grads_out shapes must equal q's")
+    if delta is None:
+        delta = torch.empty((rows, num_heads), dtype=torch.float32, device=q.device)
+    elif tuple(delta.shape) != (rows, num_heads) or delta.dtype != torch.float32 or not delta.is_contiguous():
+        raise ValueError(f"delta must be contiguous fp32 [{rows}, {num_heads}]")
+    if rows == 0:  # nothing to launch (and an empty d_out has no strides to speak of)
+        return dq, dk, dv
+    (qp, ldq), (kp, ldk), (vp, ldv) = _rows(q, "q"), _rows(k, "k", q.dtype), _rows(v, "v", q.dtype)
+    (op, ldo), (gp, ldg) = _rows(out, "out", q.dtype), _rows(d_out, "d_out", q.dtype)
+    (dqp, lddq), (dkp, lddk), (dvp, lddv) = _rows(dq, "dq", q.dtype), _rows(dk, "dk", q.dtype), _rows(dv, "dv", q.dtype)
+    rc = _lib.load().anemoi_window_attention_bwd(qp, ldq, kp, ldk, vp, ldv, op, ldo, gp, ldg, lse.data_ptr(), dqp, lddq, dkp, lddk, dvp, lddv,
+                                                 delta.data_ptr(), batch_size, rows // batch_size, num_heads, d, w, scale, cap,
+                                                 _vec(alibi_slopes, "alibi_slopes", num_heads, torch.float32), int(passes), _dt(q), _stream())
+    _lib.check(rc, "window_attention_bwd")
+    return dq, dk, dv
 
 
 # ------------------------------------------------------------------------------------------ sparse projection

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 21
+#define ANEMOI_HIP_ABI_VERSION 22
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -674,6 +674,26 @@ int anemoi_gnn_node_chain_segsum_fwd(const void* x, int64_t ld_x, const void* ed
 int anemoi_window_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
                                 float* lse, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window, float scale, float softcap,
                                 const float* alibi_slopes, anemoi_dtype_t dtype, void* stream);
+
+/* Backward of the op above.
+ * Replaces: autograd through MultiHeadSelfAttention.attention_computation (layers/attention.py:41-262; the reference differentiates its
+ * flash-attention / SDPA call).  With t = <q_i, k_j> * scale, s the capped and biased score of the forward and p = exp(s - lse[i, h]):
+ *     Delta_i = <d_out_i, out_i>;  dP = <d_out_i, v_j>;  dS = p (dP - Delta_i);  dT = dS (1 - tanh^2(t / softcap))  (softcap > 0) or dS
+ *     dq_i = scale sum_j dT k_j;  dk_j = scale sum_i dT q_i;  dv_j = sum_i p d_out_i          (alibi_slopes get no gradient)
+ * Two launches that both recompute the scores: the query pass writes dq and delta, the key pass reads delta and writes dk and dv;
+ * `passes` selects them (ANEMOI_WINDOW_BWD_BOTH_PASSES in product code; one pass alone is for timing, and the key pass alone needs the
+ * delta of an earlier query pass).  out, lse: the forward's results (lse fp32 [batch seq_len, H]); delta: fp32 [batch seq_len, H]
+ * workspace of the caller; every operand has its own leading dimension, so dq / dk / dv can be the three column slices of one
+ * [rows, 3A] gradient buffer.  No atomics: every element is summed in a fixed order, bitwise reproducible.  Shapes, window
+ * normalisation and d as in the forward; 16-bit operands need 16-byte aligned rows of the inputs and 8-byte aligned rows of dq / dk / dv.
+ * The work is proportional to seq_len (2 window + 1); no allocation, no synchronisation. */
+#define ANEMOI_WINDOW_BWD_QUERY_PASS 1
+#define ANEMOI_WINDOW_BWD_KEY_PASS 2
+#define ANEMOI_WINDOW_BWD_BOTH_PASSES 3
+int anemoi_window_attention_bwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* out, int64_t ldo,
+                                const void* d_out, int64_t ldg, const float* lse, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
+                                int64_t lddv, float* delta, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window, float scale,
+                                float softcap, const float* alibi_slopes, int32_t passes, anemoi_dtype_t dtype, void* stream);
 
 /* Sparse projection of node rows by a constant CSR matrix, forward (and, on the transposed matrix, backward).
  * Replaces: SparseProjector._project_flattened (layers/sparse_projector.py:78-104: permute copy, torch.sparse.mm, permute copy) as

@@ -10,6 +10,7 @@ Floors (a cost model, not a measurement): the softmax's vector issue, SOFTMAX_CY
 1 024 SIMDs at CLOCK_HZ, and the MFMAs, 4 * pairs * A flops at the dense bf16 peak.
 
     python tools/transformer_time.py [--channels 1024] [--hidden-res 6] [--window 512] [--layers 16] [--steps 20]
+    python tools/transformer_time.py --backward --channels 1024 [--no-model]     (see backward_report)
 """
 from __future__ import annotations
 
@@ -70,6 +71,61 @@ def eager_ms(fn, steps: int) -> float:
     return a.elapsed_time(b) / steps
 
 
+def backward_report(args) -> dict:
+    """``--backward``: the window attention's forward, its backward and each backward pass alone (csrc/window_attention_bwd.hip), as
+    hipGraph replays, at the hidden meshes of res 5 and 6 (10 242 and 40 962 rows), window ``--window`` and unbounded, bf16; then one
+    training step (forward + backward of the whole model, bf16 parameters, fp32 batch) of the O96 -> res ``--hidden-res`` model."""
+    dev, dt = "cuda", torch.bfloat16
+    H, A = args.heads, args.channels
+    res: dict = dict(tool="transformer_time --backward", channels=A, heads=H, head_dim=A // H, dtype="bf16", device=torch.cuda.get_device_name(),
+                     shapes=[])
+    for N in (10 * 4 ** 5 + 2, 10 * 4 ** 6 + 2):
+        torch.manual_seed(0)
+        buf = torch.randn(N, 3 * A, device=dev, dtype=dt)
+        q, k, v = buf[:, :A], buf[:, A:2 * A], buf[:, 2 * A:]
+        d_out = torch.randn(N, A, device=dev, dtype=dt)
+        grad = torch.empty_like(buf)
+        grads = (grad[:, :A], grad[:, A:2 * A], grad[:, 2 * A:])
+        delta = torch.empty(N, H, device=dev, dtype=torch.float32)
+        for w in (args.window, None):
+            out, lse = ops.window_attention(q, k, v, H, w, return_lse=True)
+            bwd = lambda passes, w=w, out=out, lse=lse: ops.window_attention_bwd(d_out, q, k, v, out, lse, H, w, grads_out=grads,  # noqa: E731
+                                                                                 delta=delta, passes=passes)
+            bwd(ops.WINDOW_BWD_QUERY_PASS)  # the key pass alone reads this delta
+            # a timed window of about half a second each: the replay count follows a three-replay estimate
+            long_enough = lambda fn: timed(fn, max(args.steps, min(5000, int(500.0 / timed(fn, 3)))))  # noqa: E731
+            us = {name: round(long_enough(fn) * 1e3, 1) for name, fn in (
+                ("forward", lambda w=w: ops.window_attention(q, k, v, H, w, return_lse=True)),
+                ("backward", lambda: bwd(ops.WINDOW_BWD_QUERY_PASS | ops.WINDOW_BWD_KEY_PASS)),
+                ("query_pass", lambda: bwd(ops.WINDOW_BWD_QUERY_PASS)),
+                ("key_pass", lambda: bwd(ops.WINDOW_BWD_KEY_PASS)))}
+            pairs = band_pairs(N, w)
+            res["shapes"].append(dict(rows=N, window="none" if w is None else w, band_pairs=pairs, us=us,
+                                      backward_over_forward=round(us["backward"] / us["forward"], 2),
+                                      forward_tflops=round(4.0 * pairs * A / (us["forward"] * 1e-6) / 1e12, 1),
+                                      backward_tflops=round(14.0 * pairs * A / (us["backward"] * 1e-6) / 1e12, 1)))
+        del buf, grad
+    if not args.no_model:
+        from anemoi_core_amd.graphs.synthetic import build_synthetic_graph
+        from anemoi_core_amd.models import AnemoiModelEncProcDec
+        from anemoi_core_amd.models.configs import make_data_indices, model_config
+
+        g = build_synthetic_graph("o96", args.hidden_res, processor_edges=False)
+        n_vars, n_step = 84, 2
+        model = AnemoiModelEncProcDec(model_config=model_config("transformer", A, args.layers, H, 8, window_size=args.window),
+                                      data_indices=make_data_indices(n_vars, n_vars), statistics={"data": None}, n_step_input=n_step,
+                                      n_step_output=1, graph_data=g).train().to(dev, dt)
+        x = {"data": torch.randn(1, n_step, 1, g.num_data, n_vars, device=dev)}
+
+        def step():
+            model.zero_grad(set_to_none=True)
+            model(x)["data"].float().square().mean().backward()
+
+        res.update(train_step_ms=round(timed(step, args.steps), 3), train_step_rows=g.num_hidden, train_step_layers=args.layers,
+                   train_step_window=args.window)
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--channels", type=int, default=512)
@@ -79,7 +135,11 @@ def main() -> None:
     ap.add_argument("--heads", type=int, default=16)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--no-model", action="store_true", help="the attention kernel alone")
+    ap.add_argument("--backward", action="store_true", help="time the attention's backward passes and one training step instead")
     args = ap.parse_args()
+    if args.backward:
+        print(json.dumps(backward_report(args)))
+        return
     dev, dt = "cuda", torch.bfloat16
     H, A = args.heads, args.channels
     d = A // H
