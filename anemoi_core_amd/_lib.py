@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -51,22 +51,15 @@ SIGNATURES = {
     "anemoi_cond_layernorm_proj_fwd": ([_p, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _f, C.c_int, _p], C.c_int),
     "anemoi_assemble_input": ([_p, _i64, _i64, _i32, _i32, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_assemble_output": ([_p, _i64, _p, _i64, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_assemble_input_norm": ([_p, C.c_int, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_assemble_output_norm": ([_p, _i64, C.c_int, _p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_affine_columns": ([_p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_bound_columns": ([_p, _i64, _i32, _i32, _p, _p, _i32, C.c_int, _p], C.c_int),
     "anemoi_impute_columns": ([_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_restore_nan_columns": ([_p, _i64, _p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_assemble_input_impute": ([_p, C.c_int, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, C.c_int, _p],
-                                     C.c_int),
-    "anemoi_assemble_output_impute": ([_p, _i64, C.c_int, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_bound_columns_mask": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_remap_columns": ([_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, C.c_int, _p],
                              C.c_int),
-    "anemoi_assemble_input_remap": ([_p, C.c_int, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32,
+    "anemoi_assemble_input_chain": ([_p, C.c_int, _i64, _i64, _i32, _i32, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32,
                                      C.c_int, _p], C.c_int),
-    "anemoi_assemble_output_remap": ([_p, _i64, C.c_int, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
-    "anemoi_column_program": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i64, _i32, C.c_int, _p], C.c_int),
+    "anemoi_assemble_output_chain": ([_p, _i64, C.c_int, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, C.c_int, _p], C.c_int),
+    "anemoi_column_program": ([_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i64, _i32, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_layernorm_fwd": ([_p, _i64, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _f, C.c_int, _p], C.c_int),
     "anemoi_gt_attention_fused_edge_bwd_partial_floats": ([_i32, _i32, _i32], _i64),
     "anemoi_gt_attention_fused_edge_bwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i32, _p, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p,

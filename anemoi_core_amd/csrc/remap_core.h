@@ -35,7 +35,7 @@ enum RemapOp : int {
 constexpr int kRemapClip = 1, kRemapTangent = 2, kRemapLower = 4, kRemapUpper = 8;  // flags; bits 4..7: how pow is taken (remap_pow)
 
 // One torch op's rounding: the value is pinned in a VGPR (no FMA contraction across it, no fused fp16 conversion - see mul_f32 in
-// rowwise.hip), then rounded to T and widened again.
+// model_edge.hip), then rounded to T and widened again.
 template <typename T>
 __device__ __forceinline__ float rnd(float t) {
   asm("" : "+v"(t));

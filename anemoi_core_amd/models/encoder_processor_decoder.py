@@ -245,16 +245,18 @@ class AnemoiModelEncProcDec(nn.Module):
         B, T, E, N, V = x.shape
         fusable = (_FUSED_INPUT and B == 1 and E == 1 and x.is_cuda and x.stride(4) == 1
                    and not (torch.is_grad_enabled() and (x.requires_grad or node_attr.requires_grad)))
-        if remapper is not None:
-            # as with the imputer below: the programs ride in the assembly kernels for one sample, one output step, the step skip and a whole
-            # grid; everything else runs the stand-alone kernels first (no host synchronisation: the domain assertion belongs to the chain's
-            # first-batch check) and goes on as if the chain were the normaliser alone
+        if imputer is not None or remapper is not None:
+            # the programs ride in the assembly kernels for one sample, one output step, the step skip and a whole grid; everything else
+            # (a batch, several output steps, a truncated residual - whose down projection would need the programs on every gathered value -,
+            # a sharded grid, training) runs the stand-alone kernels first, ONE pass per member (no host synchronisation: the domain
+            # assertion belongs to the chain's first-batch check), and goes on as if the chain were the normaliser alone
             if not (fusable and self.n_step_output == 1 and not self._truncated[ds] and shard_sizes is None and not torch.is_grad_enabled()
                     and (node_attr.dtype == x.dtype or x.dtype == torch.float32)):
                 fresh = imputer is not None
                 if fresh:
                     x, imputer = imputer.transform(x, in_place=False), None
-                x, remapper = remapper.transform(x if x.stride(-1) == 1 else x.contiguous(), in_place=fresh, check_domain=False), None
+                if remapper is not None:
+                    x, remapper = remapper.transform(x if x.stride(-1) == 1 else x.contiguous(), in_place=fresh, check_domain=False), None
             else:
                 width = T * V + node_attr.shape[1]
                 if node_attr.dtype != torch.float32 and self._prepad(ds):
@@ -263,24 +265,8 @@ class AnemoiModelEncProcDec(nn.Module):
                 mul, add = norm.column_program(V)
                 out = ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype,
                                          impute=None if imputer is None else imputer.device_program(V, x.dtype, x.device), nan_mask=nan_mask,
-                                         remap=remapper.device_program(V, False, x.device)[0])
-                return out, x[:, self._skip_step, ...], True, nan_mask, True
-        if imputer is not None:
-            # the program rides in the assembly kernels for one sample, one output step, the step skip and a whole grid; everything else
-            # (a batch, several output steps, a truncated residual - whose down projection would need the program on every gathered value -,
-            # a sharded grid, training) imputes in ONE stand-alone pass first and goes on as if the chain were the normaliser alone
-            if not (fusable and self.n_step_output == 1 and not self._truncated[ds] and shard_sizes is None and not torch.is_grad_enabled()
-                    and (node_attr.dtype == x.dtype or x.dtype == torch.float32)):
-                x, imputer = imputer.transform(x, in_place=False), None
-            else:
-                width = T * V + node_attr.shape[1]
-                if node_attr.dtype != torch.float32 and self._prepad(ds):
-                    width += (-width) % 64 if (-width) % 64 <= 16 and _PAD64 else (-width) % 8
-                nan_mask = torch.empty((N, V), dtype=torch.bool, device=x.device)
-                mul, add = norm.column_program(V)
-                out = ops.assemble_input(x[0, :, 0], node_attr, width, mul, add, out_dtype=node_attr.dtype,
-                                         impute=imputer.device_program(V, x.dtype, x.device), nan_mask=nan_mask)
-                return out, x[:, self._skip_step, ...], True, nan_mask, False
+                                         remap=None if remapper is None else remapper.device_program(V, False, x.device)[0])
+                return out, x[:, self._skip_step, ...], True, nan_mask, remapper is not None
         if fusable and (node_attr.dtype == x.dtype or (norm is not None and x.dtype == torch.float32)):
             # inference, one member: permute + cat + alignment zeros (+ the input normaliser as a column program) in ONE kernel
             width = T * V + node_attr.shape[1]
@@ -350,12 +336,9 @@ class AnemoiModelEncProcDec(nn.Module):
                 x_skip = ops.remap_columns((x_skip if x_skip.stride(-1) == 1 else x_skip.contiguous()).unsqueeze(1), remap,
                                            out=x_skip.unsqueeze(1) if program is not None else None).squeeze(1)
             x_skip, skip_is_raw = norm.transform(x_skip, in_place=program is not None or remap is not None), False
-        if fused_norm and remap is not None:
+        if fused_norm:
             mul, add = norm.column_program(x_skip.shape[-1])
             x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add, impute=program, remap=remap).view(1, 1, 1, N, -1)
-        elif fused_norm:
-            mul, add = norm.column_program(x_skip.shape[-1])
-            x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map, mul, add, impute=program).view(1, 1, 1, N, -1)
         elif fusable and x_out.dtype == dtype and x_skip.dtype == dtype:
             # one kernel for cast / residual on the prognostic columns (instead of clone + index_select + index_add_)
             x_out = ops.assemble_output(x_out, x_skip.reshape(N, -1), col_map).view(1, 1, 1, N, -1)

@@ -1534,8 +1534,11 @@ def impute_program(kinds, values, sources, device) -> ImputeProgram:
     return ImputeProgram(ks.to(device), torch.tensor([float(v) for v in values], dtype=torch.float32).to(device))
 
 
-def _impute_ptrs(impute: ImputeProgram, V: int, what: str) -> tuple[int, int]:
+def _impute_ptrs(impute: Optional[ImputeProgram], V: int, what: str) -> tuple[int, int]:
+    if impute is None:  # a chain without this stage: the null pointer group
+        return 0, 0
     ks, val = impute
+    _dev(ks, val)
     if ks.shape != (V, 2) or ks.dtype != torch.int32 or not ks.is_contiguous():
         raise ValueError(f"{what}: impute.kind_src must be contiguous int32 [{V}, 2], got {tuple(ks.shape)} {ks.dtype}")
     return ks.data_ptr(), _vec(val, "impute.value", V, torch.float32)
@@ -1605,48 +1608,24 @@ def assemble_input(x: Tensor, attrs: Optional[Tensor], width: int, col_mul: Opti
         raise ValueError("assemble_input: x must be [T, N, V] with contiguous variables, attrs [N, A] of the output dtype")
     out = torch.empty((N, width), dtype=odt, device=x.device)
     ap, lda = _rows(attrs, "attrs", odt)
-    if remap is not None:
-        if (impute is None) != (nan_mask is None):
-            raise ValueError("assemble_input: impute and nan_mask go together")
-        if (col_mul is None) != (col_add is None):
-            raise ValueError("assemble_input: col_mul and col_add go together")
-        if x.dtype != odt and x.dtype != torch.float32:
-            raise ValueError("assemble_input: x must be in the output dtype or fp32")
-        kp, vp = (0, 0) if impute is None else _impute_ptrs(impute, V, "assemble_input")
-        mp = 0 if nan_mask is None else _bool_mask(nan_mask, (N, V), "assemble_input").data_ptr()
-        if impute is not None:
-            _dev(x, impute.kind_src, impute.value, nan_mask)
-        op, pp = _remap_ptrs(remap, V, "assemble_input")
-        _lib.check(_lib.load().anemoi_assemble_input_remap(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, kp, vp, mp, V, op, pp,
-                                                           _vec(col_mul, "col_mul", V, torch.float32), _vec(col_add, "col_add", V, torch.float32), ap, lda,
-                                                           A, out.data_ptr(), width, width, N, _DT[odt], _stream()), "assemble_input_remap")
-        return out
-    if impute is not None or nan_mask is not None:
-        if impute is None or nan_mask is None:
-            raise ValueError("assemble_input: impute and nan_mask go together")
-        _dev(x, impute.kind_src, impute.value, nan_mask)
-        if (col_mul is None) != (col_add is None):
-            raise ValueError("assemble_input: col_mul and col_add go together")
-        if x.dtype != odt and x.dtype != torch.float32:
-            raise ValueError("assemble_input: x must be in the output dtype or fp32")
-        kp, vp = _impute_ptrs(impute, V, "assemble_input")
-        _lib.check(_lib.load().anemoi_assemble_input_impute(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, kp, vp,
-                                                            _bool_mask(nan_mask, (N, V), "assemble_input").data_ptr(), V,
-                                                            _vec(col_mul, "col_mul", V, torch.float32), _vec(col_add, "col_add", V, torch.float32), ap, lda,
-                                                            A, out.data_ptr(), width, width, N, _DT[odt], _stream()), "assemble_input_impute")
-        return out
+    staged = impute is not None or nan_mask is not None or remap is not None
     plain_pad = T == 1 and A == 0 and odt != torch.float32 and width % 8 == 0  # cast + zero-pad of [N, V] rows: the division-free 16-byte path
-    if col_mul is None and col_add is None and odt == x.dtype and not plain_pad:
+    if not staged and col_mul is None and col_add is None and odt == x.dtype and not plain_pad:
         _lib.check(_lib.load().anemoi_assemble_input(x.data_ptr(), x.stride(0), x.stride(1), T, V, ap, lda, A, out.data_ptr(), width, width, N,
                                                      _dt(x), _stream()), "assemble_input")
         return out
+    if (impute is None) != (nan_mask is None):
+        raise ValueError("assemble_input: impute and nan_mask go together")
     if (col_mul is None) != (col_add is None):
         raise ValueError("assemble_input: col_mul and col_add go together")
     if x.dtype != odt and x.dtype != torch.float32:
         raise ValueError("assemble_input: x must be in the output dtype or fp32")
-    _lib.check(_lib.load().anemoi_assemble_input_norm(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, _vec(col_mul, "col_mul", V, torch.float32),
-                                                      _vec(col_add, "col_add", V, torch.float32), ap, lda, A, out.data_ptr(), width, width, N,
-                                                      _DT[odt], _stream()), "assemble_input_norm")
+    _dev(x, nan_mask)
+    mp = 0 if nan_mask is None else _bool_mask(nan_mask, (N, V), "assemble_input").data_ptr()
+    _lib.check(_lib.load().anemoi_assemble_input_chain(x.data_ptr(), _dt(x), x.stride(0), x.stride(1), T, V, *_impute_ptrs(impute, V, "assemble_input"),
+                                                       mp, V, *_remap_ptrs(remap, V, "assemble_input"), _vec(col_mul, "col_mul", V, torch.float32),
+                                                       _vec(col_add, "col_add", V, torch.float32), ap, lda, A, out.data_ptr(), width, width, N,
+                                                       _DT[odt], _stream()), "assemble_input_chain")
     return out
 
 
@@ -1662,30 +1641,15 @@ def assemble_output(x_out: Tensor, x_skip: Tensor, col_map: Tensor, col_mul: Opt
     out = torch.empty((N, V), dtype=x_skip.dtype, device=x_out.device)
     (xp, ldx), (sp, lds) = _rows(x_out, "x_out"), _rows(x_skip, "x_skip")
     Vin = x_skip.shape[1]
-    if remap is not None:
-        if x_skip.dtype != x_out.dtype and x_skip.dtype != torch.float32:
-            raise ValueError("assemble_output: x_skip must be in x_out's dtype or fp32")
-        kp, vp = (0, 0) if impute is None else _impute_ptrs(impute, Vin, "assemble_output")
-        if impute is not None:
-            _dev(x_out, impute.kind_src, impute.value)
-        op, pp = _remap_ptrs(remap, Vin, "assemble_output")
-        _lib.check(_lib.load().anemoi_assemble_output_remap(xp, ldx, _dt(x_out), sp, lds, _vec(col_map, "col_map", V, torch.int32), kp, vp, op, pp,
-                                                            _vec(col_mul, "col_mul", Vin, torch.float32), _vec(col_add, "col_add", Vin, torch.float32),
-                                                            out.data_ptr(), V, N, V, _dt(x_skip), _stream()), "assemble_output_remap")
-        return out
-    if impute is not None:
-        _dev(x_out, impute.kind_src, impute.value)
-        kp, vp = _impute_ptrs(impute, Vin, "assemble_output")
-        _lib.check(_lib.load().anemoi_assemble_output_impute(xp, ldx, _dt(x_out), sp, lds, col_map.data_ptr(), kp, vp,
-                                                             _vec(col_mul, "col_mul", Vin, torch.float32), _vec(col_add, "col_add", Vin, torch.float32),
-                                                             out.data_ptr(), V, N, V, _dt(x_skip), _stream()), "assemble_output_impute")
-        return out
-    if col_mul is None and col_add is None and x_skip.dtype == x_out.dtype:
+    if impute is None and remap is None and col_mul is None and col_add is None and x_skip.dtype == x_out.dtype:
         _lib.check(_lib.load().anemoi_assemble_output(xp, ldx, sp, lds, col_map.data_ptr(), out.data_ptr(), V, N, V, _dt(x_out), _stream()), "assemble_output")
         return out
-    _lib.check(_lib.load().anemoi_assemble_output_norm(xp, ldx, _dt(x_out), sp, lds, col_map.data_ptr(), _vec(col_mul, "col_mul", Vin, torch.float32),
-                                                       _vec(col_add, "col_add", Vin, torch.float32), out.data_ptr(), V, N, V, _dt(x_skip), _stream()),
-               "assemble_output_norm")
+    if x_skip.dtype != x_out.dtype and x_skip.dtype != torch.float32:
+        raise ValueError("assemble_output: x_skip must be in x_out's dtype or fp32")
+    _lib.check(_lib.load().anemoi_assemble_output_chain(xp, ldx, _dt(x_out), sp, lds, _vec(col_map, "col_map", V, torch.int32),
+                                                        *_impute_ptrs(impute, Vin, "assemble_output"), *_remap_ptrs(remap, Vin, "assemble_output"),
+                                                        _vec(col_mul, "col_mul", Vin, torch.float32), _vec(col_add, "col_add", Vin, torch.float32),
+                                                        out.data_ptr(), V, N, V, _dt(x_skip), _stream()), "assemble_output_chain")
     return out
 
 
@@ -1707,25 +1671,26 @@ def affine_columns(x: Tensor, col_mul: Tensor, col_add: Tensor, inverse: bool = 
 
 
 def bound_columns_(x: Tensor, op_table: Tensor, param_table: Tensor, *, nan_mask: Optional[Tensor] = None, n_nan_ops: int = 0) -> Tensor:
-    """In place: apply the column program (int32 [n_ops, 4], fp32 [n_ops, 2]; see anemoi_bound_columns) to x [..., V].  ``nan_mask``
+    """In place: apply the column program (int32 [n_ops, 4], fp32 [n_ops, 2]; see anemoi_column_program) to x [..., V].  ``nan_mask``
     (bool [rows of x, V_mask]) serves the ops of kind 10, (10, dst column, mask column, 0): NaN where the mask is set; ``n_nan_ops``: how
     many of them the program holds - a program with such ops and no mask is an error."""
     _dev(x, op_table, param_table, nan_mask)
     if not x.is_contiguous():
         raise ValueError("bound_columns_: x must be contiguous")
+    return _column_program(x, op_table, param_table, nan_mask, int(n_nan_ops), False, "bound_columns_")
+
+
+def _column_program(x: Tensor, op_table: Tensor, param_table: Tensor, nan_mask: Optional[Tensor], n_nan_ops: int, extended: bool, what: str) -> Tensor:
+    """The one launch behind ``bound_columns_`` and ``column_program_``; ``extended``: the tables may hold the kinds above 10."""
     V = x.shape[-1]
-    if nan_mask is None and not n_nan_ops:
-        _lib.check(_lib.load().anemoi_bound_columns(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(),
-                                                    op_table.shape[0], _dt(x), _stream()), "bound_columns")
-        return x
     mp = vm = 0
     if nan_mask is not None:
         vm = nan_mask.shape[-1]
-        mp = _bool_mask(nan_mask, nan_mask.shape, "bound_columns_").data_ptr()
+        mp = _bool_mask(nan_mask, nan_mask.shape, what).data_ptr()
         if nan_mask.numel() != (x.numel() // V) * vm:
-            raise ValueError(f"bound_columns_: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
-    _lib.check(_lib.load().anemoi_bound_columns_mask(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
-                                                     mp, vm, vm, int(n_nan_ops), _dt(x), _stream()), "bound_columns_mask")
+            raise ValueError(f"{what}: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
+    _lib.check(_lib.load().anemoi_column_program(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
+                                                 mp, vm, vm, n_nan_ops, 1 if extended else 0, _dt(x), _stream()), "column_program")
     return x
 
 
@@ -1752,7 +1717,9 @@ def remap_program(entries, device) -> RemapProgram:
     return RemapProgram(of.to(device), par.to(device), active.to(device))
 
 
-def _remap_ptrs(program: RemapProgram, V: int, what: str) -> tuple[int, int]:
+def _remap_ptrs(program: Optional[RemapProgram], V: int, what: str) -> tuple[int, int]:
+    if program is None:  # a chain without this stage: the null pointer group
+        return 0, 0
     of, par, _ = program
     _dev(of, par)
     if of.shape != (V, 2) or of.dtype != torch.int32 or not of.is_contiguous() or par.shape != (V, 4) or par.dtype != torch.float32 or not par.is_contiguous():
@@ -1799,19 +1766,10 @@ def column_program_(x: Tensor, op_table: Tensor, param_table: Tensor, *, nan_mas
     _dev(x, op_table, param_table, nan_mask)
     if not x.is_contiguous():
         raise ValueError("column_program_: x must be contiguous")
-    V = x.shape[-1]
     if op_table.dim() != 2 or op_table.shape[1] != 4 or op_table.dtype != torch.int32 or not op_table.is_contiguous() or \
             tuple(param_table.shape) != (op_table.shape[0], 2) or param_table.dtype != torch.float32 or not param_table.is_contiguous():
         raise ValueError("column_program_: the tables must be contiguous int32 [n_ops, 4] and fp32 [n_ops, 2]")
-    mp = vm = 0
-    if nan_mask is not None:
-        vm = nan_mask.shape[-1]
-        mp = _bool_mask(nan_mask, nan_mask.shape, "column_program_").data_ptr()
-        if nan_mask.numel() != (x.numel() // V) * vm:
-            raise ValueError(f"column_program_: the mask {tuple(nan_mask.shape)} does not have one row per row of x {tuple(x.shape)}")
-    _lib.check(_lib.load().anemoi_column_program(x.data_ptr(), V, x.numel() // V, V, op_table.data_ptr(), param_table.data_ptr(), op_table.shape[0],
-                                                 mp, vm, vm, _dt(x), _stream()), "column_program")
-    return x
+    return _column_program(x, op_table, param_table, nan_mask, 0, True, "column_program_")
 
 
 def transpose_pad(x: Tensor, mult: int = 64) -> Tensor:

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 22
+#define ANEMOI_HIP_ABI_VERSION 23
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -167,15 +167,6 @@ int anemoi_cond_layernorm_proj_fwd(const void* x, int64_t ldx, const void* cond,
 int anemoi_cond_layernorm_bwd(const void* x, int64_t ldx, const void* scale, int64_t lds, const void* d_y, int64_t lddy,
                               void* d_x, int64_t lddx, void* d_scale, int64_t ldds, int32_t n_rows, int32_t D, float eps,
                               anemoi_dtype_t dtype, void* stream);
-
-/* Output boundings at the model edge, in place and in configuration order (layers/bounding.py:81-307;
- * models/encoder_processor_decoder.py:160-162).  ops: int32 [n_ops][4] = (kind, column, total column, 0); params: fp32
- * [n_ops][2].  kind 1 ReluBounding, 2 LeakyReluBounding, 3 / 4 Normalized(Leaky)ReluBounding (params[0] = the normalised
- * minimum), 5 / 6 (Leaky)HardtanhBounding (min, max), 7 / 8 (Leaky)FractionBounding (min, max; times column ``total``),
- * 9 de-normalisation (x - params[0]) / params[1] = InputNormalizer.inverse_transform of that column
- * (preprocessing/normalizer.py:217-252), appended after the boundings when the output normaliser is fused. */
-int anemoi_bound_columns(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params,
-                         int32_t n_ops, anemoi_dtype_t dtype, void* stream);
 
 /* Input assembly at the model edge for batch = ensemble = 1 (models/encoder_processor_decoder.py:98-143): out[n] = [x[0, n, :] | ... |
  * x[T-1, n, :] | attrs[n, :] | zeros up to W], x time slices ld_t elements apart, rows ldx apart.  Replaces the permute-copy, the cat
@@ -332,21 +323,6 @@ int anemoi_glu_bwd(const void* gate_value, int64_t ldgv, const void* d_out, int6
  * x * _norm_mul + _norm_add per variable, `inverse_transform`: (x - _norm_add) / _norm_mul, preprocessing/normalizer.py:154-252).
  * Here the transform rides in the kernels that touch every input / output element anyway. */
 
-/* anemoi_assemble_input with the normaliser as a column program: the T * V time/variable columns become
- * x * col_mul[v] + col_add[v] (fp32, two roundings like torch's mul_ / add_; NULL/NULL = plain copy).  `x` may be fp32
- * (x_dtype) while `attrs` / `out` are in the model `dtype`. */
-int anemoi_assemble_input_norm(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
-                               const float* col_mul, const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out,
-                               int64_t ldo, int32_t W, int32_t n_rows, anemoi_dtype_t dtype, void* stream);
-
-/* anemoi_assemble_output with the skip connection read from the RAW input and normalised on the fly:
- * out[n, v] = x_out[n, v] + (col_map[v] >= 0 ? x_skip[n, m] * col_mul[m] + col_add[m] : 0), m = col_map[v].
- * x_out in `model_dtype`; x_skip / out in `dtype` (= model_dtype or fp32: the reference adds the residual in the input's
- * dtype, models/encoder_processor_decoder.py:145-158).  The de-normalisation of the result is op 9 of anemoi_bound_columns. */
-int anemoi_assemble_output_norm(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
-                                const int32_t* col_map, const float* col_mul, const float* col_add, void* out, int64_t ldo,
-                                int32_t n_rows, int32_t n_cols, anemoi_dtype_t dtype, void* stream);
-
 /* Stand-alone InputNormalizer.transform (inverse = 0: y = x * mul[c] + add[c]) / inverse_transform (inverse = 1:
  * y = (x - add[c]) / mul[c]) over the last dimension of a [n_rows, V] view; y may alias x (in_place). */
 int anemoi_affine_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const float* col_mul, const float* col_add,
@@ -372,27 +348,6 @@ int anemoi_impute_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_
 int anemoi_restore_nan_columns(const void* x, int64_t ldx, void* y, int64_t ldy, const void* mask, int64_t ldm, int32_t n_mask_cols,
                                const int32_t* src_of, int32_t B, int32_t M, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream);
 
-/* anemoi_assemble_input_norm with the imputation program in front of the normaliser: every raw element is tested and imputed within its
- * own time step (the copy source is read from the same step and row), then x * col_mul[v] + col_add[v] with the same two fp32 roundings
- * (NULL/NULL: none).  mask: bool [n_rows][ldm], the NaN locations of step 0, written in the same pass.  Same scalar / 8-column routes. */
-int anemoi_assemble_input_impute(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
-                                 const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const float* col_mul,
-                                 const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo, int32_t W,
-                                 int32_t n_rows, anemoi_dtype_t dtype, void* stream);
-
-/* anemoi_assemble_output_norm whose RAW skip is imputed by the same program (over the skip's columns) before it is normalised. */
-int anemoi_assemble_output_impute(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
-                                  const int32_t* col_map, const int32_t* kind_src, const float* value, const float* col_mul,
-                                  const float* col_add, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols, anemoi_dtype_t dtype,
-                                  void* stream);
-
-/* anemoi_bound_columns with a mask bool [n_rows][ldm] (n_mask_cols columns) and one more op kind, 10 "NaN where mask[n, src]", encoded
- * (10, dst column, src mask column, 0) and appended after the op-9 de-normalisations: boundings, de-normalisation and NaN restoration
- * stay one in-place launch.  n_nan_ops: how many ops of kind 10 the program holds; n_nan_ops > 0 with mask == NULL is an error, and
- * mask == NULL otherwise forwards to anemoi_bound_columns. */
-int anemoi_bound_columns_mask(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
-                              const void* mask, int64_t ldm, int32_t n_mask_cols, int32_t n_nan_ops, anemoi_dtype_t dtype, void* stream);
-
 /* ---- remapper and post-processors at the model edges ----------------------------------------------------------------------------
  * The reference's Remapper (preprocessing/remapper.py, mappings.py) maps single variables through log1p / sqrt / power / boxcox / atanh /
  * asinh / displaced boundary atoms / an affine map before the normaliser, and back on the output; its post-processors
@@ -411,26 +366,46 @@ int anemoi_remap_columns(const void* x, int64_t ld_b, int64_t ld_t, int64_t ld_e
                          int64_t yd_e, int64_t yd_n, const int32_t* op_flags, const float* par, const int32_t* active, int32_t n_active,
                          int32_t* violations, int32_t B, int32_t T_steps, int32_t E, int32_t N, int32_t V, anemoi_dtype_t dtype, void* stream);
 
-/* anemoi_assemble_input_impute for the chain [imputer]? Remapper InputNormalizer: every raw element is imputed (kind_src / value / mask
- * all NULL: the chain has no imputer), then mapped by the remap program (op_flags int32 [V][2], par fp32 [V][4], each step rounded to the
- * RAW dtype), then normalised.  mask: the NaN locations of step 0 of the raw input.  Same scalar / 8-column routes. */
-int anemoi_assemble_input_remap(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
+/* ---- the staged chain at the model edges (ABI 23) ---------------------------------------------------------------------------------
+ * The pre-processor chain [imputer]? [Remapper]? [InputNormalizer]? rides in the kernels that touch every input element anyway.  Each
+ * optional stage is a pointer group that is NULL as a whole where the chain has no such stage:
+ *   kind_src / value (/ mask)   the imputation program above;
+ *   op_flags / par              the FORWARD remap program (int32 [V][2], fp32 [V][4], 8- / 16-byte aligned), each step rounded to the RAW dtype;
+ *   col_mul / col_add           the normaliser, fp32 [V]: x * col_mul[v] + col_add[v], two fp32 roundings like torch's mul_ / add_. */
+
+/* anemoi_assemble_input whose T * V time / variable columns go through the chain: every raw element is tested and imputed within its own
+ * time step (the copy source is read from the same step and row), remapped, normalised.  `x` may be fp32 (x_dtype) while `attrs` / `out`
+ * are in the model `dtype`.  mask (with the imputation program): bool [n_rows][ldm], the NaN locations of step 0 of the RAW input, written
+ * in the same pass.  A 16-bit output with W % 8 == 0, ldo % 8 == 0 and a 16-byte-aligned `out` takes the 8-column kernel. */
+int anemoi_assemble_input_chain(const void* x, anemoi_dtype_t x_dtype, int64_t ld_t, int64_t ldx, int32_t T_steps, int32_t V,
                                 const int32_t* kind_src, const float* value, void* mask, int64_t ldm, const int32_t* op_flags, const float* par,
                                 const float* col_mul, const float* col_add, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo,
                                 int32_t W, int32_t n_rows, anemoi_dtype_t dtype, void* stream);
 
-/* anemoi_assemble_output_impute whose RAW skip goes through the same chain (the tables span the skip's columns; kind_src / value NULL:
- * no imputer). */
-int anemoi_assemble_output_remap(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
+/* anemoi_assemble_output with the skip connection read from the RAW input, which goes through the same chain on the fly (the tables span
+ * the skip's columns): out[n, v] = x_out[n, v] + (col_map[v] >= 0 ? chain(x_skip[n, m]) : 0), m = col_map[v].  x_out in `model_dtype`;
+ * x_skip / out in `dtype` (= model_dtype or fp32: the reference adds the residual in the input's dtype,
+ * models/encoder_processor_decoder.py:145-158).  The de-normalisation of the result is op 9 of anemoi_column_program. */
+int anemoi_assemble_output_chain(const void* x_out, int64_t ldx, anemoi_dtype_t model_dtype, const void* x_skip, int64_t lds,
                                  const int32_t* col_map, const int32_t* kind_src, const float* value, const int32_t* op_flags, const float* par,
                                  const float* col_mul, const float* col_add, void* out, int64_t ldo, int32_t n_rows, int32_t n_cols,
                                  anemoi_dtype_t dtype, void* stream);
 
-/* anemoi_bound_columns_mask (mask may be NULL with n_mask_cols = 0) with further op kinds: 11 "p0 where x[n, total column] == 0",
- * 12 "NaN where x[n, total column] is NaN" - both read the row as the ops before them left it - and 16 + r: remap op r, with
- * flags = ops[i][3] and its third parameter as the float bits of ops[i][2].  Kinds 1..10 are those of anemoi_bound_columns_mask. */
+/* The output column program, in place and in order: the boundings (layers/bounding.py:81-307; models/encoder_processor_decoder.py:160-162)
+ * and what follows them on the output.  ops: int32 [n_ops][4] = (kind, column, total column, 0); params: fp32 [n_ops][2].
+ *   kind 1 ReluBounding, 2 LeakyReluBounding, 3 / 4 Normalized(Leaky)ReluBounding (params[0] = the normalised minimum), 5 / 6
+ *   (Leaky)HardtanhBounding (min, max), 7 / 8 (Leaky)FractionBounding (min, max; times column ``total``), 9 de-normalisation
+ *   (x - params[0]) / params[1] = InputNormalizer.inverse_transform of that column (preprocessing/normalizer.py:217-252);
+ *   with a mask bool [n_rows][ldm] (n_mask_cols columns; NULL with n_mask_cols = 0: none): 10 "NaN where mask[n, src]", encoded
+ *   (10, dst column, src mask column, 0) and appended after the op-9 de-normalisations.  n_nan_ops: how many ops of kind 10 the caller
+ *   knows the program to hold; n_nan_ops > 0 with mask == NULL is an error;
+ *   with extended != 0 (the host says so when it builds the tables; they live in device memory): 11 "p0 where x[n, total column] == 0",
+ *   12 "NaN where x[n, total column] is NaN" - both read the row as the ops before them left it - and 16 + r: remap op r, with
+ *   flags = ops[i][3] and its third parameter as the float bits of ops[i][2].
+ * A kind the call does not enable leaves its column as it is. */
 int anemoi_column_program(void* x, int64_t ldx, int32_t n_rows, int32_t n_cols, const int32_t* ops, const float* params, int32_t n_ops,
-                          const void* mask, int64_t ldm, int32_t n_mask_cols, anemoi_dtype_t dtype, void* stream);
+                          const void* mask, int64_t ldm, int32_t n_mask_cols, int32_t n_nan_ops, int32_t extended, anemoi_dtype_t dtype,
+                          void* stream);
 
 /* ---- device-initiated row exchange between the ranks of a model-parallel group (scope row e) ----------------------------
  * The reference exchanges node rows with host-issued NCCL collectives: the per-layer halo all-to-all

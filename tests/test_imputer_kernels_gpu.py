@@ -1,6 +1,7 @@
-"""The imputer kernels of csrc/rowwise.hip - impute_columns_kernel, restore_nan_columns_kernel, assemble_input_impute_kernel,
-assemble_input_impute_vec8_kernel, assemble_output_impute_kernel and bound_columns_mask_kernel - called directly through their ``ops``
-wrappers with the discipline of tests/test_model_edge_kernels_gpu.py: past one 256-thread block, every dtype pair, every route of the new
+"""The imputer kernels of csrc/model_edge.hip - impute_columns_kernel, restore_nan_columns_kernel, the IMPUTE instantiations
+assemble_input_chain_kernel<TI, TO, true, false>, assemble_input_chain_vec8_kernel<TI, TO, true, false> and
+assemble_output_chain_kernel<TM, TS, true, false>, and column_program_kernel<T, 1> - called directly through their ``ops`` wrappers
+with the discipline of tests/test_model_edge_kernels_gpu.py: past one 256-thread block, every dtype pair, every route of the chain
 entry points, operands as column slabs of sentinel-filled buffers, against the plain-torch restatements of tests/imputer_refs.py (which
 tests/test_imputer_cpu.py holds to the reference's recorded outputs).
 
@@ -20,7 +21,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ROWS = [1, 257, 333]
 PAIRS = [(F32, F32), (F32, BF16), (F32, F16), (BF16, BF16), (F16, F16)]  # (data dtype, model dtype)
-LAYOUTS = [(2, 7, 5, 21), (2, 7, 5, 24), (3, 5, 0, 16), (1, 11, 0, 16), (1, 8, 0, 8), (2, 8, 4, 24)]  # (T, V, A, W)
+LAYOUTS = [(2, 7, 5, 21), (2, 7, 5, 24), (3, 5, 0, 16), (1, 11, 0, 16), (1, 8, 0, 8), (2, 8, 4, 24), (2, 12, 0, 24)]  # (T, V, A, W)
+# (2, 12, 0, 24): the smallest layout whose mask rows are 4-byte aligned (ldm = V = 12) AND whose 8-column groups do both things the mask
+# store branches on: group 0 lies within step 0 (the packed two-word store), group 1 straddles t0|t1 (columns 8-11 of step 0: byte stores)
 FILL = 7.0
 NAN = float("nan")
 
@@ -76,7 +79,7 @@ def _on_device(ops, program):
 
 # ------------------------------------------------------------------------------------------------------------ input assembly
 def _route(W, to):
-    """anemoi_assemble_input_impute: a 16-bit output of W % 8 == 0 takes the 8-column kernel, everything else the scalar one."""
+    """anemoi_assemble_input_chain: a 16-bit output of W % 8 == 0 takes the 8-column kernel, everything else the scalar one."""
     return "vec8" if to != F32 and W % 8 == 0 else "scalar"
 
 
@@ -88,6 +91,7 @@ def test_layouts_reach_both_routes_and_every_straddle():
     straddles = lambda T, V, A, W, edge: 0 < edge < W and edge % 8 != 0 and edge // 8 in groups(T, V, A, W)  # noqa: E731
     assert straddles(2, 7, 5, 24, 7) and straddles(2, 7, 5, 24, 14) and straddles(2, 7, 5, 24, 19)  # t0|t1, x|attrs, attrs|zeros
     assert straddles(3, 5, 0, 16, 5) and straddles(3, 5, 0, 16, 10) and straddles(1, 11, 0, 16, 11)
+    assert straddles(2, 12, 0, 24, 12) and 12 % 4 == 0 and 0 + 8 <= 12  # t0|t1 inside group 1, aligned mask rows, group 0 within step 0
 
 
 @pytest.mark.parametrize("norm", [True, False], ids=["norm", "nonorm"])

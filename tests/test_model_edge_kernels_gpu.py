@@ -1,6 +1,6 @@
-"""The seven model-edge kernels of csrc/rowwise.hip - assemble_input_kernel, assemble_input_norm_kernel,
-assemble_input_norm_vec8_kernel, assemble_output_kernel, assemble_output_norm_kernel, affine_columns_kernel and
-bound_columns_kernel - called directly through their ``ops`` wrappers, past one 256-thread block, at every branch the wrappers
+"""The seven model-edge kernels of csrc/model_edge.hip without an imputer or a remapper - assemble_input_kernel,
+assemble_input_chain_kernel<TI, TO, false, false>, assemble_input_chain_vec8_kernel<TI, TO, false, false>, assemble_output_kernel,
+assemble_output_chain_kernel<TM, TS, false, false>, affine_columns_kernel and column_program_kernel<T, 0> - called directly through their ``ops`` wrappers, past one 256-thread block, at every branch the wrappers
 and the entry points take, NaN and +-inf included, against the plain-torch CPU restatements of tests/model_edge_refs.py (which
 tests/test_model_edge_refs_cpu.py holds to the reference's recorded outputs).
 
@@ -58,10 +58,10 @@ def _dev(t):
 
 # ------------------------------------------------------------------------------------------------------------ assemble_input
 def _input_route(T, V, A, W, ti, to, norm):
-    """The kernel ops.assemble_input reaches for a contiguous input: ops.py:1402-1403 (plain_pad; the plain kernel only without a
-    normaliser, in one dtype and not plain_pad), then anemoi_assemble_input_norm (rowwise.hip:930: 16-bit output with W % 8 == 0
-    takes the vec8 kernel, whose first branch is T == 1 && A == 0, rowwise.hip:568) or anemoi_assemble_input (rowwise.hip:898: Q = 4
-    when V, A, W are multiples of 4)."""
+    """The kernel ops.assemble_input reaches for a contiguous input: ``plain_pad`` in ops.assemble_input (the plain kernel only without
+    a normaliser, in one dtype and not plain_pad), then anemoi_assemble_input_chain (assemble_input_chain_launch: a 16-bit output with
+    W % 8 == 0 takes the vec8 kernel, whose first branch is T == 1 && A == 0) or anemoi_assemble_input (Q = 4 when V, A, W are multiples
+    of 4)."""
     plain_pad = T == 1 and A == 0 and to != F32 and W % 8 == 0
     if not norm and ti == to and not plain_pad:
         return "plain-q4" if V % 4 == 0 and A % 4 == 0 and W % 4 == 0 else "plain-q1"
@@ -81,7 +81,7 @@ EXPECTED_ROUTES = {  # layout -> the kernels it reaches over the dtype pairs, wi
 
 def test_assemble_input_cases_reach_every_kernel_and_branch():
     """The table above selects what it says: every layout reaches exactly the kernels listed for it over the dtype pairs with and
-    without a normaliser, and all five routes (ops.py:1402-1403, rowwise.hip:898, 930, 568) occur."""
+    without a normaliser, and all five routes (``_input_route``) occur."""
     seen = set()
     for lay in LAYOUTS:
         routes = {_input_route(*lay, ti, to, norm) for ti, to in PAIRS for norm in (False, True)}
@@ -97,10 +97,10 @@ def test_assemble_input_cases_reach_every_kernel_and_branch():
 @pytest.mark.parametrize("layout", LAYOUTS, ids=lambda s: "T%d-V%d-A%d-W%d" % s)
 def test_assemble_input_bit_equal(ops, layout, N, pair, norm):
     """ops.assemble_input on contiguous inputs == assemble_input_ref bit for bit.  The (layout, dtype pair, normaliser) triple
-    picks the kernel (``_input_route``): assemble_input_kernel<T, 1 | 4> (ops.py:1403 -> rowwise.hip:898),
-    assemble_input_norm_kernel<TI, TO> (fp32 output, or W % 8 != 0: rowwise.hip:930 not taken), assemble_input_norm_vec8_kernel<TI, TO>
-    general branch (8-column groups straddling t0|t1, x|attrs, attrs|zeros) or its T == 1 && A == 0 branch (rowwise.hip:568), which
-    without col_mul is the plain_pad route of ops.py:1402 with mul == nullptr.  All six <TI, TO> pairs with float input or one
+    picks the kernel (``_input_route``): assemble_input_kernel<T, 1 | 4> (anemoi_assemble_input),
+    assemble_input_chain_kernel<TI, TO, false, false> (fp32 output, or W % 8 != 0: the vec8 route of assemble_input_chain_launch not
+    taken), assemble_input_chain_vec8_kernel<TI, TO, false, false> general branch (8-column groups straddling t0|t1, x|attrs,
+    attrs|zeros) or its T == 1 && A == 0 branch, which without col_mul is the plain_pad route of ops.assemble_input with mul == nullptr.  All six <TI, TO> pairs with float input or one
     16-bit dtype are instantiated by the five dtype pairs here."""
     (T, V, A, W), (ti, to) = layout, pair
     mul, add, mean, stdev = R.column_stats(V, ti, seed=V)
@@ -119,8 +119,8 @@ def test_assemble_input_bit_equal(ops, layout, N, pair, norm):
 def test_assemble_input_model_layout_strided_views(ops, pair, W):
     """The model's real operands (models/encoder_processor_decoder.py, predict_step): x = batch[0, :, 0] of a [1, T, 1, N, V] batch;
     x a [T, N, V] slice of a buffer with a wider row (ldx = V + 4 > V, base pointer off by 2 elements); attrs a column slab of a
-    wider buffer (lda = A + 4, off by 1).  assemble_input_norm_kernel (W = 21, or fp32 output) and the general branch of
-    assemble_input_norm_vec8_kernel (W = 24, 16-bit output: rowwise.hip:930) index x by x.stride(0) / x.stride(1) (ops.py:1411)."""
+    wider buffer (lda = A + 4, off by 1).  assemble_input_chain_kernel (W = 21, or fp32 output) and the general branch of
+    assemble_input_chain_vec8_kernel (W = 24, 16-bit output) index x by x.stride(0) / x.stride(1) (ops.assemble_input)."""
     ti, to = pair
     T, N, V, A = 2, 257, 7, 5
     mul, add, mean, stdev = R.column_stats(V, ti, seed=3)
@@ -139,7 +139,7 @@ def test_assemble_input_model_layout_strided_views(ops, pair, W):
 @pytest.mark.parametrize("N", [257, 333])
 def test_assemble_input_plain_q4_and_its_fallbacks(ops, dtype, N):
     """assemble_input_kernel<T, 4> (V, A, W multiples of 4, every stride a multiple of 4, every pointer 4-element aligned:
-    rowwise.hip:898-899) and each way it falls back to <T, 1>: x with ldx % 4 != 0; attrs a slab starting at column 1, 2, 3 (lda % 4 == 0,
+    ``q4`` in anemoi_assemble_input) and each way it falls back to <T, 1>: x with ldx % 4 != 0; attrs a slab starting at column 1, 2, 3 (lda % 4 == 0,
     pointer misaligned); the time stride ld_t % 4 != 0; and a slab that keeps Q = 4 (offset 4).  Pure data movement: bit-equal."""
     T, V, A, W = 2, 8, 4, 24
     _, _, mean, stdev = R.column_stats(V, dtype, seed=1)
@@ -164,8 +164,8 @@ def test_assemble_input_plain_q4_and_its_fallbacks(ops, dtype, N):
 
 
 def test_assemble_input_error_paths(ops):
-    """ops.assemble_input refuses (ValueError) col_mul without col_add (ops.py:1407), width < T * V + A and attrs of another dtype
-    (ops.py:1398), and 16-bit x with another 16-bit out_dtype (ops.py:1409)."""
+    """ops.assemble_input refuses (ValueError) col_mul without col_add, width < T * V + A and attrs of another dtype, and 16-bit x
+    with another 16-bit out_dtype (the shared argument checks of ops.assemble_input)."""
     x = torch.zeros(2, 9, 7, device=DEV)
     attrs = torch.zeros(9, 5, device=DEV)
     mul = torch.ones(7, device=DEV)
@@ -204,9 +204,9 @@ def _col_maps(V_out):
 def test_assemble_output_bit_equal(ops, V_out, pair, norm):
     """ops.assemble_output == assemble_output_ref bit for bit, for N in {1, 257, 333}, col_map all -1 / all mapped / mixed (one
     skip column mapped twice, the last skip column mapped), x_skip contiguous and a row-strided slab.  (TS, TM) = (data, model)
-    dtype: with a normaliser, or with fp32 data under a 16-bit model, assemble_output_norm_kernel<TM, TS> (ops.py:1425 not taken;
-    rowwise.hip:967 picks TS = float or TM); the same dtype without a normaliser is assemble_output_kernel<T, 1 | 4>
-    (rowwise.hip:875: Q = 4 at V_out = 84)."""
+    dtype: with a normaliser, or with fp32 data under a 16-bit model, assemble_output_chain_kernel<TM, TS, false, false> (the plain route of
+    ops.assemble_output not taken; anemoi_assemble_output_chain picks TS = float or TM); the same dtype without a normaliser is
+    assemble_output_kernel<T, 1 | 4> (``q4`` in anemoi_assemble_output: Q = 4 at V_out = 84)."""
     ts, tm = pair
     mul, add, mean, stdev = R.column_stats(V_IN, ts, seed=V_out)
     m, a = (mul, add) if norm else (None, None)
@@ -225,7 +225,7 @@ def test_assemble_output_bit_equal(ops, V_out, pair, norm):
 @pytest.mark.parametrize("dtype", [F32, BF16, F16], ids=lambda d: NAME[d])
 def test_assemble_output_plain_q4_and_its_fallbacks(ops, dtype):
     """assemble_output_kernel<T, 4> (V_out = 84, contiguous, and a slab at column offset 4) and its fall-backs to <T, 1>
-    (rowwise.hip:875-876): row-strided x_out with ldx % 4 != 0, and x_out a slab at an odd column offset (ldx % 4 == 0, pointer
+    (``q4`` in anemoi_assemble_output): row-strided x_out with ldx % 4 != 0, and x_out a slab at an odd column offset (ldx % 4 == 0, pointer
     misaligned).  V_out % 4 != 0 is covered by test_assemble_output_bit_equal (5, 37)."""
     N, V_out = 257, 84
     _, _, mean, stdev = R.column_stats(V_IN, dtype)
@@ -239,13 +239,13 @@ def test_assemble_output_plain_q4_and_its_fallbacks(ops, dtype):
 
 
 def test_assemble_output_unsupported_pairs_raise(ops):
-    """fp32 x_out with 16-bit x_skip, and two different 16-bit dtypes, are refused by anemoi_assemble_output_norm
-    (rowwise.hip:961) as a ValueError: no tensor comes back that could be mistaken for a result."""
+    """fp32 x_out with 16-bit x_skip, and two different 16-bit dtypes, are refused by ops.assemble_output and
+    anemoi_assemble_output_chain (check_chain) as a ValueError: no tensor comes back that could be mistaken for a result."""
     col_map = torch.tensor([0, -1, 2], dtype=torch.int32, device=DEV)
     for tm, ts in ((F32, BF16), (F32, F16), (BF16, F16), (F16, BF16)):
         with pytest.raises(ValueError):
             ops.assemble_output(torch.zeros(9, 3, dtype=tm, device=DEV), torch.zeros(9, 4, dtype=ts, device=DEV), col_map)
-    with pytest.raises(ValueError):  # col_mul without col_add (rowwise.hip:958)
+    with pytest.raises(ValueError):  # col_mul without col_add (check_chain in model_edge.hip)
         ops.assemble_output(torch.zeros(9, 3, device=DEV), torch.zeros(9, 4, device=DEV), col_map, col_mul=torch.ones(4, device=DEV))
 
 
@@ -257,11 +257,11 @@ def test_assemble_output_unsupported_pairs_raise(ops):
 def test_affine_columns_bit_equal(ops, NV, lead, dtype, inverse):
     """ops.affine_columns == torch's own in-place sequence on a CPU tensor of the same dtype (x.mul_(mul).add_(add) /
     x.subtract_(add).div_(mul)), bit for bit: affine_columns_kernel<T>, forward (fp32: mul_then_add; 16 bit: a rounding to T after
-    each step, rowwise.hip:630-635) and inverse (rowwise.hip:628), the row / column split i / V, i % V up to 6 * 257 * 101 elements
-    (607 blocks); out of place, in place (out = x) and into a given out (ops.py:1442).  N257-V101-4d-fp16-forward is the case that
+    each step) and inverse, the row / column split i / V, i % V up to 6 * 257 * 101 elements
+    (607 blocks); out of place, in place (out = x) and into a given out (ops.affine_columns).  N257-V101-4d-fp16-forward is the case that
     found the fp16 forward rounding its product ONCE (x * mul and the conversion selected as one v_fma_mixlo_f16) where torch rounds to
     fp32 and then to fp16: 4 of 155 742 elements, those whose fp32 product is a tie between two fp16 values (``mul_f32`` in
-    rowwise.hip keeps the fp32 value)."""
+    model_edge.hip keeps the fp32 value)."""
     N, V = NV
     mul, add, mean, stdev = R.column_stats(V, dtype, seed=N)
     x = R.raw_data((*lead, N, V), dtype, mean, stdev, seed=V)
@@ -281,7 +281,7 @@ def test_affine_columns_bit_equal(ops, NV, lead, dtype, inverse):
 
 
 def test_affine_columns_refuses_a_non_contiguous_input(ops):
-    """ops.py:1440: a non-contiguous x (a column slab, a transposed view) raises instead of being read with the wrong stride."""
+    """ops.affine_columns: a non-contiguous x (a column slab, a transposed view) raises instead of being read with the wrong stride."""
     one = torch.ones(7, device=DEV)
     with pytest.raises(ValueError):
         ops.affine_columns(torch.zeros(9, 11, device=DEV)[:, 2:9], one, one)
@@ -325,7 +325,7 @@ def _tables(prog):
 @pytest.mark.parametrize("pair", R.BOUND_PAIRS, ids=lambda p: "p%g_%g" % p)
 @pytest.mark.parametrize("kind", range(1, 10))
 def test_bound_columns_each_kind_at_its_bounds(ops, kind, pair, dtype):
-    """bound_columns_kernel<T>, one op of ``kind`` (the switch at rowwise.hip:460-471) on column 0 of a [n, 3] tensor (column 1: the
+    """column_program_kernel<T, 0> through ops.bound_columns_, one op of ``kind`` (the kernel's one switch) on column 0 of a [n, 3] tensor (column 1: the
     total of kinds 7 / 8; column 2: not named by the program), on inputs dense around the bounds - p0, p1, their neighbours on both
     sides, 0, -0.0, +-tiny, +-large, +-inf, NaN - plus 320 random ones (model_edge_refs.bounding_inputs): some 335 rows, two blocks.
     NaN exactly where the float64 evaluation has it (kinds 1, 3, 5, 7 returned 0 / p0 for NaN while they used fmaxf / fminf),
@@ -360,9 +360,9 @@ ORDER_PROGRAM = [
 @pytest.mark.parametrize("dtype", [F32, BF16, F16], ids=lambda d: NAME[d])
 @pytest.mark.parametrize("N", [1, 255, 256, 257, 1000])
 def test_bound_columns_order_dependent_programs(ops, N, dtype):
-    """bound_columns_kernel<T> on a contiguous [1, 1, 1, N, 10] tensor as the model passes it (encoder_processor_decoder.py:318), one
-    row per thread across the block boundary (N = 255, 256, 257, 1000: rowwise.hip:448-449), with programs whose result depends on
-    the order of the ops (the loop at rowwise.hip:451 reads and writes the row in place): relu on the total column THEN two
+    """column_program_kernel<T, 0> on a contiguous [1, 1, 1, N, 10] tensor as the model passes it (``_assemble_output``), one
+    row per thread across the block boundary (N = 255, 256, 257, 1000), with programs whose result depends on
+    the order of the ops (the kernel's loop over the ops reads and writes the row in place): relu on the total column THEN two
     fractions of it; a fraction whose total is bounded later (it takes the unbounded value, as the reference's sequence of modules
     does); one column bounded twice; and all of it followed by kind 9 on every column - the predict_step program of
     encoder_processor_decoder.py:314-317.  A NaN in a total column makes the fractions of that row NaN; the columns the first program

@@ -1,6 +1,7 @@
-"""The remapper / post-processor kernels of csrc/rowwise.hip (remap_core.h) - remap_columns_kernel, assemble_input_remap_kernel,
-assemble_input_remap_vec8_kernel, assemble_output_remap_kernel and the extended column program (bound_columns_mask_kernel<T, true>) - called
-directly through their ``ops`` wrappers with the discipline of tests/test_imputer_kernels_gpu.py: past one 256-thread block, every dtype
+"""The remapper / post-processor kernels of csrc/model_edge.hip (remap_core.h) - remap_columns_kernel, the REMAP instantiations
+assemble_input_chain_kernel<TI, TO, IMPUTE, true>, assemble_input_chain_vec8_kernel<TI, TO, IMPUTE, true> and
+assemble_output_chain_kernel<TM, TS, IMPUTE, true>, and the extended column program (column_program_kernel<T, 2>) - called directly
+through their ``ops`` wrappers with the discipline of tests/test_imputer_kernels_gpu.py: past one 256-thread block, every dtype
 pair, both assembly routes, operands as column slabs of sentinel-filled buffers, against the plain-torch restatements of
 tests/remapper_refs.py (which tests/test_remapper_cpu.py holds to the reference's recorded outputs).
 
@@ -33,17 +34,18 @@ DEV = "cuda"
 FILL = 7.0
 NAN = float("nan")
 PAIRS = [(F32, F32), (F32, BF16), (F32, F16), (BF16, BF16), (F16, F16)]  # (data dtype, model dtype)
-LAYOUTS = [(2, 7, 5, 21), (2, 7, 5, 24), (3, 5, 0, 16), (1, 11, 0, 16), (1, 8, 0, 8), (2, 8, 4, 24)]  # (T, V, A, W), as the imputer's
+LAYOUTS = [(2, 7, 5, 21), (2, 7, 5, 24), (3, 5, 0, 16), (1, 11, 0, 16), (1, 8, 0, 8), (2, 8, 4, 24), (2, 12, 0, 24)]  # (T, V, A, W), as the imputer's
 SHAPES = [(1, 1, 1), (1, 1, 255), (1, 1, 256), (1, 1, 257), (2, 2, 333), (2, 1, 2, 257)]  # [batch, time, (ensemble,) grid]
 EPS = {F32: 2.0 ** -23, BF16: 2.0 ** -7, F16: 2.0 ** -10}
 ATOMS = {"lower_atom": 0.0, "upper_atom": 1.0, "lower_target": -0.25, "upper_target": 1.25, "eps": 0.0}
-# (method, kwargs, how its column is drawn); a program of V columns takes the first V.  Exactly rounded: 0, 1, 3, 4, 9, 10
+# (method, kwargs, how its column is drawn); a program of V columns takes the first V.  Exactly rounded: 0, 1, 3, 4, 9, 10, 11
 COLUMNS = [("none", {}, "n"), ("affine", {"scale": 2.5, "shift": -0.75}, "n"), ("log1p", {}, "3r"), ("sqrt", {}, "4r"),
            ("displace_boundary_atoms", ATOMS, "atoms"), ("power", {"lambd": 0.33, "clip_negative": True, "tangent_linear_above_one": True}, "3r-"),
            ("boxcox", {"lambd": 0.25}, "r+"), ("atanh", {"rho": 2.0}, "r"), ("asinh", {"c": 3.0}, "3n"),
-           ("power", {"lambd": 0.5, "clip_negative": True, "tangent_linear_above_one": True}, "3r-"), ("none", {}, "n")]
+           ("power", {"lambd": 0.5, "clip_negative": True, "tangent_linear_above_one": True}, "3r-"), ("none", {}, "n"),
+           ("affine", {"scale": 0.5, "shift": 1.25}, "n")]  # (the twelfth: the layout (2, 12, 0, 24) needs it)
 LIBM = {2, 5, 6, 7, 8}
-EXACT_ONLY = [0, 1, 3, 4, 9, 10, 1, 3, 4, 9, 0]  # an 11-column program of exactly rounded methods only (indices into COLUMNS)
+EXACT_ONLY = [0, 1, 3, 4, 9, 10, 1, 3, 4, 9, 0, 11]  # a 12-column program of exactly rounded methods only (indices into COLUMNS)
 
 
 @pytest.fixture(scope="module")
@@ -343,7 +345,7 @@ def test_assemble_output_remap(ops, V_out, pair, impute):
     program = _impute_program(V_in, ts)
     col_map = torch.full((V_out,), -1, dtype=torch.int32)
     col_map[:5] = torch.tensor([1, 3, 9, 4, 0], dtype=torch.int32)
-    for label, columns in (("exact", [COLUMNS[i] for i in EXACT_ONLY]), ("all", COLUMNS)):
+    for label, columns in (("exact", [COLUMNS[i] for i in EXACT_ONLY[:V_in]]), ("all", COLUMNS[:V_in])):
         if label == "all":
             col_map[:5] = torch.tensor([2, 5, 9, 7, 8], dtype=torch.int32)
         remap = _program(ops, columns)
