@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -26,6 +26,12 @@ class LinearPlan(C.Structure):
                                           "tail_rows", "ln_tail_begin")]
 
 
+class AttentionPlan(C.Structure):
+    """anemoi_gt_attention_plan_t: the plan of one edge-attention call (csrc/gt_attention_plan.h), field for field."""
+    _fields_ = [(name, _i32) for name in ("route", "vec", "lph", "fe_pad", "kv_adjacent", "lds_bytes")] + \
+               [(name, C.c_uint32) for name in ("grid_dst", "grid_src", "grid_wgrad")]
+
+
 # name -> argtypes, exactly as in include/anemoi_hip.h
 SIGNATURES = {
     "anemoi_hip_abi_version": ([], C.c_int),
@@ -39,6 +45,7 @@ SIGNATURES = {
                                          _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _f, C.c_uint64, C.c_int, _p], C.c_int),
     "anemoi_attention_dropout_mask": ([_p, _i32, _i32, _f, C.c_uint64, _p], C.c_int),
     "anemoi_gt_attention_fused_edge_fwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i32, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _i32, C.c_int, _p], C.c_int),
+    "anemoi_gt_attention_plan": ([_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_int, C.POINTER(AttentionPlan)], C.c_int),
     "anemoi_pack_edge_weights": ([_p, _p, _p, _i32, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_pack_edge_features": ([_p, _i64, _p, _i32, _i32, _i32, C.c_int, _p], C.c_int),
     "anemoi_reduce_workspace_bytes": ([_i32], _i64),

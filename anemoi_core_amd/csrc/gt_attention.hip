@@ -14,20 +14,15 @@
 // so per destination we build qw[h][f] once (W' = [W_e | b_e] staged in LDS), per edge we only touch the
 // fe_pad fp32 edge features (wave-uniform -> scalar loads) and at the end apply W' to the weighted feature
 // sum.  HBM traffic per layer drops from 2(4ND + MD) to 2*4ND + 4*M*fe_pad bytes.
-#include <type_traits>
-
-#include "common.h"
+//
+// This file: the fused-edge forward kernel.  In front of it gt_attention_core.h (build-time knobs, the packed dot product), behind
+// it gt_attention_fwd_host.h (the materialised-E, generic and pack kernels, the launches, the C entry points); which kernel a call
+// runs is decided by plan_attention (gt_attention_plan.h).  csrc/experiments/gt_attention_r05_variants.hip is built the same way
+// around its own kernel.
+#include "gt_attention_core.h"
 
 namespace anemoi {
 
-#ifndef ANEMOI_ATTN_WPB
-#define ANEMOI_ATTN_WPB 4
-#endif
-constexpr int kWavesPerBlock = ANEMOI_ATTN_WPB;
-#ifndef ANEMOI_ATTN_MIN_WAVES
-#define ANEMOI_ATTN_MIN_WAVES (16 / ANEMOI_ATTN_WPB)
-#endif
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 // Where a destination's loads are requested (profiles/r05_attention_header_ab.txt, same-box A/Bs): the source ids travel WITH the q slice,
 // ahead of the qw set-up (-6 % of the launch), and the scalar part of the next header (id, edge range) one destination ahead.  The
 // round-5 variants that were measured slower or equal - first header beside the W' staging, first ring fill ahead of the qw set-up,
@@ -35,122 +30,8 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 // csrc/experiments/gt_attention_r05_variants.hip (tools/build_alt.sh builds them into an alternative library for same-box A/Bs).
 constexpr int kAttnPF = 3;  // edges of K|V rows in flight per wave (modulo-unrolled ring, counted waits)
 
-template <int VEC>
-struct EdgeRow {
-  float k[VEC];
-  float v[VEC];
-  float e[VEC];
-};
-
-// ---------------------------------------------------------------------------------------------- fast path
-template <typename T, int VEC, int LPH, bool HAS_E>
-__global__ __launch_bounds__(64 * kWavesPerBlock) void gt_attn_fwd_kernel(
-    const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk, const T* __restrict__ v, int64_t ldv,
-    const T* __restrict__ e, int64_t lde, const int32_t* __restrict__ row, const int32_t* __restrict__ colptr,
-    const T* __restrict__ addend, int64_t ldadd, T* __restrict__ out, int64_t ldo, float* __restrict__ lse, int n_dst,
-    int H, float scale, float drop_p, uint64_t drop_seed) {
-  const int lane = threadIdx.x & 63;
-  const int d = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
-  if (d >= n_dst) return;
-  const int beg = __builtin_amdgcn_readfirstlane(colptr[d]);
-  const int end = __builtin_amdgcn_readfirstlane(colptr[d + 1]);
-  const int c0 = lane * VEC;
-  const float inv_keep = 1.0f / (1.0f - drop_p);
-
-  float qv[VEC], acc[VEC];
-  load_vec<T, VEC>(q + (int64_t)d * ldq + c0, qv);
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    qv[j] *= scale;
-    acc[j] = 0.f;
-  }
-  float m = -INFINITY, l = 0.f;
-
-  EdgeRow<VEC> cur, nxt;
-  auto fetch = [&](int ei, EdgeRow<VEC>& r) {
-    const int s = __builtin_amdgcn_readfirstlane(row[ei]);
-    load_vec<T, VEC>(k + (int64_t)s * ldk + c0, r.k);
-    load_vec<T, VEC>(v + (int64_t)s * ldv + c0, r.v);
-    if constexpr (HAS_E) load_vec<T, VEC>(e + (int64_t)ei * lde + c0, r.e);
-  };
-  if (beg < end) fetch(beg, nxt);
-  for (int ei = beg; ei < end; ++ei) {
-    cur = nxt;
-    if (ei + 1 < end) fetch(ei + 1, nxt);
-    float dot = 0.f;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      if constexpr (HAS_E) {
-        cur.k[j] += cur.e[j];
-        cur.v[j] += cur.e[j];
-      }
-      dot = fmaf(qv[j], cur.k[j], dot);
-    }
-    dot = group_sum<LPH>(dot);
-    const float m_new = fmaxf(m, dot);
-    const float corr = __expf(m - m_new);  // first edge: exp(-inf) = 0
-    const float p = __expf(dot - m_new);
-    l = fmaf(l, corr, p);
-    // dropout acts on the NORMALISED weight: the denominator sums every edge, the numerator the kept ones (scaled by 1 / (1 - p))
-    const float pv = drop_p > 0.f ? p * attn_dropout_scale(drop_seed, ei, lane / LPH, drop_p, inv_keep) : p;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) acc[j] = fmaf(acc[j], corr, pv * cur.v[j]);
-    m = m_new;
-  }
-
-  const float inv = (end > beg) ? 1.0f / l : 0.f;
-  float o[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) o[j] = acc[j] * inv;
-  if (addend != nullptr) {
-    float a[VEC];
-    load_vec<T, VEC>(addend + (int64_t)d * ldadd + c0, a);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) o[j] += a[j];
-  }
-  store_vec<T, VEC>(out + (int64_t)d * ldo + c0, o);
-  if (lse != nullptr && (lane % LPH) == 0) lse[(int64_t)d * H + lane / LPH] = (end > beg) ? m + __logf(l) : 0.f;
-}
-
-// <a, b> over a lane's VEC channels.  16-bit types use v_dot2c_f32_{bf16,f16} on the packed pairs as loaded (exact
-// products, fp32 accumulation): no per-element conversion of the K row.
-template <typename T, int VEC>
-__device__ __forceinline__ float dot_rows(const Vec<T, VEC>& a, const Vec<T, VEC>& b) {
-  float acc = 0.f;
-  if constexpr (sizeof(T) == 2 && (VEC % 2 == 0)) {
-    const uint32_t* pa = reinterpret_cast<const uint32_t*>(&a);
-    const uint32_t* pb = reinterpret_cast<const uint32_t*>(&b);
-#pragma unroll
-    for (int i = 0; i < VEC / 2; ++i) {
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-        acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2, pa[i]), __builtin_bit_cast(bf2, pb[i]), acc, false);
-      } else {
-        typedef __attribute__((ext_vector_type(2))) _Float16 h2;
-        acc = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, pa[i]), __builtin_bit_cast(h2, pb[i]), acc, false);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc = fmaf(to_float(a.v[i]), to_float(b.v[i]), acc);
-  }
-  return acc;
-}
-
-// Deferred running max: the rescale of the accumulators only runs (wave-uniform branch) when some head's score
-// exceeds its running max by more than this; otherwise p = exp(s - m_old) <= e^8 is accumulated directly (fp32
-// accumulators; the value after the final division is the same).
-constexpr float kDeferThr = 8.0f;
-
 // ---------------------------------------------------------------------------------------------- fused lin_edge
-// LDS image of W' = [W_e | b_e | 0]: per lane a chunk of VEC*FE_PAD floats (+4 floats of padding so that
-// 16 consecutive lanes' ds_read_b128 hit 16 distinct 16-byte bank slots).
-template <int VEC, int FE_PAD>
-struct WLayout {
-  static constexpr int kChunk = VEC * FE_PAD + 4;
-  static constexpr int kFloats = 64 * kChunk;
-};
-
+// (the LDS image of W' = [W_e | b_e | 0] is WLayout of gt_attention_plan.h)
 template <typename T, int VEC, int LPH, int FE_PAD, bool KVADJ>
 __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt_attn_fused_edge_fwd_kernel(
     const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk, const T* __restrict__ v, int64_t ldv,
@@ -400,303 +281,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt
   }
 }
 
-// ---------------------------------------------------------------------------------------------- generic path
-// Any (H, C): one thread per (destination, head), serial over edges and channels.  Used for shapes the
-// wave-per-row layout cannot express (D not a multiple of 64, non power-of-two lanes per head — e.g. the
-// reference's own test shapes H in {2,6}, C in {4,6}).  Correctness path, not a performance path.
-constexpr int kGenericMaxC = 256;
-
-template <typename T>
-__global__ void gt_attn_fwd_generic_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk,
-                                           const T* __restrict__ v, int64_t ldv, const T* __restrict__ e, int64_t lde,
-                                           const float* __restrict__ feat, int fe, int fe_pad,
-                                           const float* __restrict__ w_packed,
-                                           const int32_t* __restrict__ row, const int32_t* __restrict__ colptr,
-                                           const T* __restrict__ addend, int64_t ldadd, T* __restrict__ out,
-                                           int64_t ldo, float* __restrict__ lse, int n_dst, int H, int C, float scale,
-                                           float drop_p, uint64_t drop_seed) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)n_dst * H) return;
-  const int d = (int)(t / H), h = (int)(t % H);
-  const int beg = colptr[d], end = colptr[d + 1];
-  const float inv_keep = 1.0f / (1.0f - drop_p);
-  float acc[kGenericMaxC];  // private (scratch-memory) fp32 accumulator
-  for (int c = 0; c < C; ++c) acc[c] = 0.f;
-  float m = -INFINITY, l = 0.f;
-  const T* qp = q + (int64_t)d * ldq + h * C;
-  for (int ei = beg; ei < end; ++ei) {
-    const int s = row[ei];
-    const T* kp = k + (int64_t)s * ldk + h * C;
-    const T* vp = v + (int64_t)s * ldv + h * C;
-    float dot = 0.f;
-    for (int c = 0; c < C; ++c) {
-      float ee = 0.f;
-      if (e != nullptr) ee = to_float(e[(int64_t)ei * lde + h * C + c]);
-      if (feat != nullptr) {
-        ee = 0.f;  // the bias rides on the constant-1 feature column fe
-        for (int f = 0; f < fe_pad; ++f) ee = fmaf(feat[(int64_t)ei * fe_pad + f], w_packed[(int64_t)(h * C + c) * fe_pad + f], ee);
-      }
-      dot = fmaf(to_float(qp[c]) * scale, to_float(kp[c]) + ee, dot);
-    }
-    const float m_new = fmaxf(m, dot);
-    const float corr = expf(m - m_new), p = expf(dot - m_new);
-    l = l * corr + p;
-    const float pv = drop_p > 0.f ? p * attn_dropout_scale(drop_seed, ei, h, drop_p, inv_keep) : p;
-    for (int c = 0; c < C; ++c) {
-      float ee = 0.f;
-      if (e != nullptr) ee = to_float(e[(int64_t)ei * lde + h * C + c]);
-      if (feat != nullptr) {
-        ee = 0.f;  // the bias rides on the constant-1 feature column fe
-        for (int f = 0; f < fe_pad; ++f) ee = fmaf(feat[(int64_t)ei * fe_pad + f], w_packed[(int64_t)(h * C + c) * fe_pad + f], ee);
-      }
-      acc[c] = acc[c] * corr + pv * (to_float(vp[c]) + ee);
-    }
-    m = m_new;
-  }
-  const float inv = (end > beg) ? 1.0f / l : 0.f;
-  for (int c = 0; c < C; ++c) {
-    float o = acc[c] * inv;
-    if (addend != nullptr) o += to_float(addend[(int64_t)d * ldadd + h * C + c]);
-    out[(int64_t)d * ldo + h * C + c] = from_float<T>(o);
-  }
-  if (lse != nullptr) lse[(int64_t)d * H + h] = (end > beg) ? m + logf(l) : 0.f;
-}
-
-// W' = [W_e | b_e | 0] as fp32 [D][fe_pad]
-template <typename T>
-__global__ void pack_edge_weights_kernel(const T* __restrict__ w, const T* __restrict__ b, float* __restrict__ out, int D,
-                                         int fe, int fe_pad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= D * fe_pad) return;
-  const int c = i / fe_pad, f = i % fe_pad;
-  out[i] = f < fe ? to_float(w[(int64_t)c * fe + f]) : ((f == fe && b != nullptr) ? to_float(b[c]) : 0.f);
-}
-
-template <typename T>
-__global__ void pack_edge_features_kernel(const T* __restrict__ ea, int64_t ld, float* __restrict__ out, int M, int fe,
-                                          int fe_pad) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)M * fe_pad) return;
-  const int m = (int)(i / fe_pad), f = (int)(i % fe_pad);
-  out[i] = f < fe ? to_float(ea[(int64_t)m * ld + f]) : (f == fe ? 1.0f : 0.0f);
-}
-
-// ---------------------------------------------------------------------------------------------- dispatch
-struct AttnArgs {
-  const void *q, *k, *v, *e;
-  int64_t ldq, ldk, ldv, lde;
-  const float* feat;
-  int fe, fe_pad;
-  const float* w_packed;
-  const int32_t *row, *colptr;
-  const int32_t* order = nullptr;
-  const void* addend;
-  int64_t ldadd;
-  void* out;
-  int64_t ldo;
-  float* lse;
-  int n_dst, n_src, H, C;
-  hipStream_t stream;
-  float drop_p = 0.f;      // attention dropout (materialised-E op only): probability and the seed of the replayable mask
-  uint64_t drop_seed = 0;
-};
-
-static bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
-template <typename T, int VEC, int LPH>
-static int launch_fast(const AttnArgs& a) {
-  const float scale = 1.0f / sqrtf((float)a.C);
-  const dim3 block(64 * kWavesPerBlock);
-  if (a.feat == nullptr) {
-    const dim3 grid((a.n_dst + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (a.e != nullptr)
-      hipLaunchKernelGGL((gt_attn_fwd_kernel<T, VEC, LPH, true>), grid, block, 0, a.stream, (const T*)a.q, a.ldq,
-                         (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)a.e, a.lde, a.row, a.colptr,
-                         (const T*)a.addend, a.ldadd, (T*)a.out, a.ldo, a.lse, a.n_dst, a.H, scale, a.drop_p, a.drop_seed);
-    else
-      hipLaunchKernelGGL((gt_attn_fwd_kernel<T, VEC, LPH, false>), grid, block, 0, a.stream, (const T*)a.q, a.ldq,
-                         (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)nullptr, (int64_t)0, a.row, a.colptr,
-                         (const T*)a.addend, a.ldadd, (T*)a.out, a.ldo, a.lse, a.n_dst, a.H, scale, a.drop_p, a.drop_seed);
-    return check_launch("gt_attn_fwd_kernel");
-  }
-  // Fused lin_edge: each wave walks `dst_per_wave` consecutive destinations so the W' staging is amortised,
-  // while keeping >= ~8 blocks per CU worth of waves in flight.
-  auto go = [&](auto fe_pad_c) {
-    constexpr int FE_PAD = decltype(fe_pad_c)::value;
-    using L = WLayout<VEC, FE_PAD>;
-    if (L::kFloats * sizeof(float) > 64 * 1024) return 1;  // beyond the default dynamic-LDS limit: generic path
-    // persistent grid: a few workgroups per CU (LDS 25 KiB each, 5-7 waves/SIMD by registers); every wave walks destinations
-    // d, d + total_waves, ... so the W' staging is paid once per workgroup.  How many: with the locality-preserving work order
-    // the number of destinations in flight per XCD is also the size of the window whose K|V rows should stay in the L2 -
-    // measured on MI355X (profiles/r03_attention_blocks_per_cu.txt, three repetitions): 10 242 destinations 27.4 / 26.9 / 26.1 us
-    // at 5 / 6 / 7 workgroups per CU, 40 962 destinations 80.6 / 89.6 / 84.2 us (5 workgroups = 640 waves per XCD = exactly 8
-    // destinations per wave, and the smallest window); forwards: O96 2.991 / 2.991 / 2.973 ms, O96 -> res 6 8.69 / 8.81 / 8.76 ms,
-    // N320 15.21 / 15.68 / 15.39 ms.  ANEMOI_ATTN_BLOCKS_PER_CU overrides the rule.
-    static const int per_cu_env = [] { const char* e = getenv("ANEMOI_ATTN_BLOCKS_PER_CU"); return env_int(e, 0, 0, 32); }();
-    const int per_cu = per_cu_env > 0 ? per_cu_env : (a.n_dst >= 20000 ? 5 : 7);
-    static const int out_wt = [] { return env_int(getenv("ANEMOI_ATTN_OUT_WT"), 0, 0, 1); }();
-    const int max_blocks = 256 * per_cu;
-    int blocks = (a.n_dst + kWavesPerBlock - 1) / kWavesPerBlock;
-    blocks = blocks < max_blocks ? blocks : max_blocks;
-    blocks = (blocks + 7) & ~7;  // a whole number of workgroups per XCD
-    const dim3 grid(blocks);
-    // the fused [q|k|v|self] projection buffer: v sits right behind k in every row
-    const bool kv_adjacent = (const T*)a.v == (const T*)a.k + 64 * VEC && a.ldv == a.ldk &&
-                             (int64_t)a.n_src * a.ldk < (int64_t(1) << 32);
-    auto kern = kv_adjacent ? gt_attn_fused_edge_fwd_kernel<T, VEC, LPH, FE_PAD, true> : gt_attn_fused_edge_fwd_kernel<T, VEC, LPH, FE_PAD, false>;
-    hipLaunchKernelGGL(kern, grid, block, L::kFloats * sizeof(float),
-                       a.stream, (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, a.feat, a.w_packed,
-                       a.row, a.colptr, a.order, (const T*)a.addend, a.ldadd, (T*)a.out, a.ldo, a.lse, a.n_dst, a.H, scale, out_wt);
-    return check_launch("gt_attn_fused_edge_fwd_kernel");
-  };
-  switch (a.fe_pad) {
-    case 4: return go(std::integral_constant<int, 4>{});
-    case 8: return go(std::integral_constant<int, 8>{});
-    case 12: return go(std::integral_constant<int, 12>{});
-    case 16: return go(std::integral_constant<int, 16>{});
-    default: return 1;  // not covered by the fast path
-  }
-}
-
-template <typename T, int VEC>
-static int launch_vec(const AttnArgs& a) {
-  const int lph = a.C / VEC;
-  switch (lph) {
-    case 1: return launch_fast<T, VEC, 1>(a);
-    case 2: return launch_fast<T, VEC, 2>(a);
-    case 4: return launch_fast<T, VEC, 4>(a);
-    case 8: return launch_fast<T, VEC, 8>(a);
-    case 16: return launch_fast<T, VEC, 16>(a);
-    default: return 1;
-  }
-}
-
-template <typename T>
-static int launch(const AttnArgs& a) {
-  const int D = a.H * a.C;
-  int rc = 1;
-  // fast path: one wave covers the row exactly, rows 16-byte aligned for vector access
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool lds_ok = (a.ldq % 8 == 0) && (a.ldk % 8 == 0) && (a.ldv % 8 == 0) && (a.ldo % 8 == 0) &&
-                      (a.e == nullptr || a.lde % 8 == 0) && (a.addend == nullptr || a.ldadd % 8 == 0) && al16(a.q) &&
-                      al16(a.k) && al16(a.v) && al16(a.out) && al16(a.e) && al16(a.addend) && al16(a.feat) && al16(a.w_packed);
-  if (D % 64 == 0 && lds_ok) {
-    const int vec = D / 64;
-    if (a.C % vec == 0 && pow2(a.C / vec) && a.C / vec <= 16) {
-      if (vec == 1) rc = launch_vec<T, 1>(a);
-      else if (vec == 2) rc = launch_vec<T, 2>(a);
-      else if (vec == 4) rc = launch_vec<T, 4>(a);
-      else if (vec == 8) rc = launch_vec<T, 8>(a);
-      else if (vec == 16) rc = launch_vec<T, 16>(a);
-    }
-  }
-  if (rc <= 0) return rc;
-  // generic path
-  if (a.C > kGenericMaxC) {
-    set_error("gt_attention: channels per head C=%d not supported (fast path needs H*C %% 64 == 0 and a power-of-two "
-              "C*64/(H*C) <= 16; generic path needs C <= %d)", a.C, kGenericMaxC);
-    return ANEMOI_E_UNSUPPORTED;
-  }
-  const int64_t threads = (int64_t)a.n_dst * a.H;
-  if (threads == 0) return ANEMOI_OK;
-  const float scale = 1.0f / sqrtf((float)a.C);
-  hipLaunchKernelGGL((gt_attn_fwd_generic_kernel<T>), dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, a.stream,
-                     (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)a.e, a.lde, a.feat, a.fe,
-                     a.fe_pad, a.w_packed, a.row, a.colptr, (const T*)a.addend, a.ldadd,
-                     (T*)a.out, a.ldo, a.lse, a.n_dst, a.H, a.C, scale, a.drop_p, a.drop_seed);
-  return check_launch("gt_attn_fwd_generic_kernel");
-}
-
-static int dispatch(const AttnArgs& a, anemoi_dtype_t dtype) {
-  return dispatch_dtype(dtype, [&](auto t) { return launch<typename decltype(t)::type>(a); });
-}
-
 }  // namespace anemoi
 
-using namespace anemoi;
-
-extern "C" int anemoi_gt_attention_dropout_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                       const void* e, int64_t lde, const int32_t* row, const int32_t* colptr,
-                                       const void* addend, int64_t ldadd, void* out, int64_t ldo, float* lse,
-                                       int32_t n_dst, int32_t n_src, int32_t H, int32_t C, float drop_p, uint64_t drop_seed,
-                                       anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "gt_attention_dropout_fwd: dropout probability %g outside [0, 1)", (double)drop_p);
-  ANEMOI_REQUIRE(H < 65536, "gt_attention_dropout_fwd: the mask's counter holds 16 bits of head index, got H=%d", H);
-  ANEMOI_REQUIRE(n_dst >= 0 && n_src >= 0 && H > 0 && C > 0, "gt_attention_dropout_fwd: bad sizes n_dst=%d n_src=%d H=%d C=%d", n_dst, n_src, H, C);
-  if (n_dst == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(q && k && v && out && colptr, "gt_attention_dropout_fwd: null q/k/v/out/colptr");
-  const int D = H * C;
-  ANEMOI_REQUIRE(ldq >= D && ldk >= D && ldv >= D && ldo >= D && (!e || lde >= D) && (!addend || ldadd >= D),
-                 "gt_attention_dropout_fwd: leading dimension smaller than H*C=%d", D);
-  AttnArgs a{q, k, v, e, ldq, ldk, ldv, lde, nullptr, 0, 0, nullptr, row, colptr, nullptr, addend, ldadd, out, ldo, lse, n_dst, n_src, H, C, as_stream(stream)};
-  a.drop_p = drop_p;
-  a.drop_seed = drop_seed;
-  return dispatch(a, dtype);
-}
-
-extern "C" int anemoi_gt_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
-                                       const void* e, int64_t lde, const int32_t* row, const int32_t* colptr,
-                                       const void* addend, int64_t ldadd, void* out, int64_t ldo, float* lse,
-                                       int32_t n_dst, int32_t n_src, int32_t H, int32_t C, anemoi_dtype_t dtype,
-                                       void* stream) {
-  return anemoi_gt_attention_dropout_fwd(q, ldq, k, ldk, v, ldv, e, lde, row, colptr, addend, ldadd, out, ldo, lse, n_dst, n_src, H, C, 0.f, 0,
-                                         dtype, stream);
-}
-
-// keep-scale of every (edge, head) as the kernels derive it: what a caller (or a test) needs to restate the op with an explicit mask
-__global__ void attn_dropout_mask_kernel(float* __restrict__ out, int64_t n, int H, float p, uint64_t seed) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = attn_dropout_scale(seed, (int)(i / H), (int)(i % H), p, 1.0f / (1.0f - p));
-}
-
-extern "C" int anemoi_attention_dropout_mask(float* out, int32_t n_edges, int32_t H, float drop_p, uint64_t drop_seed, void* stream) {
-  ANEMOI_REQUIRE(n_edges >= 0 && H > 0 && H < 65536 && drop_p >= 0.f && drop_p < 1.f, "attention_dropout_mask: bad arguments M=%d H=%d p=%g", n_edges, H, (double)drop_p);
-  const int64_t n = (int64_t)n_edges * H;
-  if (n == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(out, "attention_dropout_mask: null output");
-  hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), out, n, H, drop_p, drop_seed);
-  return check_launch("attn_dropout_mask_kernel");
-}
-
-extern "C" int anemoi_gt_attention_fused_edge_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v,
-                                                  int64_t ldv, const float* edge_feat, int32_t fe_pad,
-                                                  const float* w_packed, const int32_t* row, const int32_t* colptr,
-                                                  const int32_t* dst_order, const void* addend, int64_t ldadd, void* out, int64_t ldo, float* lse,
-                                                  int32_t n_dst, int32_t n_src, int32_t H, int32_t C,
-                                                  anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(n_dst >= 0 && n_src >= 0 && H > 0 && C > 0, "gt_attention_fused_edge_fwd: bad sizes");
-  if (n_dst == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(q && k && v && out && colptr && edge_feat && w_packed, "gt_attention_fused_edge_fwd: null pointer");
-  ANEMOI_REQUIRE(fe_pad >= 4 && fe_pad % 4 == 0, "gt_attention_fused_edge_fwd: fe_pad must be a positive multiple of 4, got %d", fe_pad);
-  const int D = H * C;
-  ANEMOI_REQUIRE(ldq >= D && ldk >= D && ldv >= D && ldo >= D && (!addend || ldadd >= D), "gt_attention_fused_edge_fwd: leading dimension smaller than H*C=%d", D);
-  AttnArgs a{q, k, v, nullptr, ldq, ldk, ldv, 0, edge_feat, fe_pad - 1, fe_pad, w_packed, row, colptr, dst_order, addend, ldadd, out, ldo, lse, n_dst, n_src, H, C, as_stream(stream)};
-  return dispatch(a, dtype);
-}
-
-extern "C" int anemoi_pack_edge_weights(const void* w_edge, const void* b_edge, float* out, int32_t D, int32_t fe,
-                                        int32_t fe_pad, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(D > 0 && fe > 0 && fe_pad == 4 * ((fe + 1 + 3) / 4), "pack_edge_weights: bad sizes D=%d fe=%d fe_pad=%d", D, fe, fe_pad);
-  ANEMOI_REQUIRE(w_edge && out, "pack_edge_weights: null pointer");
-  const int n = D * fe_pad;
-  const dim3 grid((n + 255) / 256), block(256);
-  return dispatch_dtype(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((pack_edge_weights_kernel<T>), grid, block, 0, as_stream(stream), (const T*)w_edge, (const T*)b_edge, out, D, fe, fe_pad);
-    return check_launch("pack_edge_weights_kernel");
-  });
-}
-
-extern "C" int anemoi_pack_edge_features(const void* edge_attr, int64_t ld, float* out, int32_t M, int32_t fe,
-                                         int32_t fe_pad, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(M >= 0 && fe > 0 && fe_pad == 4 * ((fe + 1 + 3) / 4) && ld >= fe, "pack_edge_features: bad sizes M=%d fe=%d fe_pad=%d", M, fe, fe_pad);
-  if (M == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(edge_attr && out, "pack_edge_features: null pointer");
-  const int64_t n = (int64_t)M * fe_pad;
-  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  return dispatch_dtype(dtype, [&](auto t) {
-    using T = typename decltype(t)::type;
-    hipLaunchKernelGGL((pack_edge_features_kernel<T>), grid, block, 0, as_stream(stream), (const T*)edge_attr, ld, out, M, fe, fe_pad);
-    return check_launch("pack_edge_features_kernel");
-  });
-}
+#include "gt_attention_fwd_host.h"

@@ -16,13 +16,15 @@
 //    gathered q_d / dO_d rows only - no dot products, no E traffic, no atomics, deterministic.
 // HBM bytes (bf16): dst pass 2(3 N_dst D + 2 M D [k,v gathers, cached] + 2 M D [E in, dE out]) + 8 M H;
 // src pass 2(2 N_src D) + gathers of q/dO + 8 M H.
+//
+// Which kernels a call runs, on which lane layout and grids, is decided by plan_attention (gt_attention_plan.h); the launch
+// functions at the end of each half of this file launch what the plan names.
 #include "common.h"
+#include "gt_attention_plan.h"
 
 namespace anemoi {
 
 namespace {
-
-constexpr int kBwdWaves = 4;
 
 struct BwdArgs {
   const void *q, *k, *v, *e, *out, *d_out;
@@ -256,73 +258,46 @@ __global__ void gt_attn_bwd_src_generic_kernel(const T* __restrict__ q, int64_t 
 }
 
 // ---------------------------------------------------------------------------------------------- dispatch
-bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
-
+// the source pass of both backwards (materialised E and fused lin_edge)
 template <typename T, int VEC, int LPH>
-int launch_fast(const BwdArgs& a, float scale) {
-  const dim3 block(64 * kBwdWaves);
-  if (a.n_dst > 0) {
-    hipLaunchKernelGGL((gt_attn_bwd_dst_kernel<T, VEC, LPH>), dim3((a.n_dst + kBwdWaves - 1) / kBwdWaves), block, 0, a.stream,
-                       (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)a.e, a.lde, (const T*)a.out,
-                       a.ldo, a.lse, (const T*)a.d_out, a.lddo, a.row, a.colptr, (T*)a.dq, a.lddq, (T*)a.de, a.ldde, a.p_ws,
-                       a.ds_ws, a.n_dst, a.H, scale, a.drop_p, a.drop_seed);
-    const int rc = check_launch("gt_attn_bwd_dst_kernel");
-    if (rc != ANEMOI_OK) return rc;
-  }
-  if (a.n_src > 0) {
-    hipLaunchKernelGGL((gt_attn_bwd_src_kernel<T, VEC, LPH>), dim3((a.n_src + kBwdWaves - 1) / kBwdWaves), block, 0, a.stream,
-                       (const T*)a.q, a.ldq, (const T*)a.d_out, a.lddo, a.rowptr, a.edge_ids, a.edge_dst, a.p_ws, a.ds_ws,
-                       (T*)a.dk, a.lddk, (T*)a.dv, a.lddv, a.n_src, a.H);
-    return check_launch("gt_attn_bwd_src_kernel");
-  }
-  return ANEMOI_OK;
-}
-
-template <typename T, int VEC>
-int launch_vec(const BwdArgs& a, float scale) {
-  switch (a.C / VEC) {
-    case 1: return launch_fast<T, VEC, 1>(a, scale);
-    case 2: return launch_fast<T, VEC, 2>(a, scale);
-    case 4: return launch_fast<T, VEC, 4>(a, scale);
-    case 8: return launch_fast<T, VEC, 8>(a, scale);
-    case 16: return launch_fast<T, VEC, 16>(a, scale);
-    default: return 1;
-  }
+int launch_src_pass(const BwdArgs& a, const AttnPlan& p) {
+  if (p.grid_src == 0) return ANEMOI_OK;
+  hipLaunchKernelGGL((gt_attn_bwd_src_kernel<T, VEC, LPH>), dim3(p.grid_src), dim3(64 * kBwdWaves), 0, a.stream, (const T*)a.q, a.ldq,
+                     (const T*)a.d_out, a.lddo, a.rowptr, a.edge_ids, a.edge_dst, a.p_ws, a.ds_ws, (T*)a.dk, a.lddk, (T*)a.dv, a.lddv,
+                     a.n_src, a.H);
+  return check_launch("gt_attn_bwd_src_kernel");
 }
 
 template <typename T>
 int launch(const BwdArgs& a) {
-  const int D = a.H * a.C;
   const float scale = 1.0f / sqrtf((float)a.C);
-  const int64_t vb = 16 / (int64_t)sizeof(T);  // elements per 16 bytes
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool aligned = a.ldq % vb == 0 && a.ldk % vb == 0 && a.ldv % vb == 0 && a.lde % vb == 0 && a.ldo % vb == 0 &&
-                       a.lddo % vb == 0 && a.lddq % vb == 0 && a.lddk % vb == 0 && a.lddv % vb == 0 && a.ldde % vb == 0 &&
-                       al16(a.q) && al16(a.k) && al16(a.v) && al16(a.e) && al16(a.out) && al16(a.d_out) && al16(a.dq) &&
-                       al16(a.dk) && al16(a.dv) && al16(a.de);
-  int rc = 1;
-  if (D % 64 == 0 && aligned) {
-    const int vec = D / 64;
-    if (a.C % vec == 0 && pow2(a.C / vec) && a.C / vec <= 16) {
-      if (vec == 1) rc = launch_vec<T, 1>(a, scale);
-      else if (vec == 2) rc = launch_vec<T, 2>(a, scale);
-      else if (vec == 4) rc = launch_vec<T, 4>(a, scale);
-      else if (vec == 8) rc = launch_vec<T, 8>(a, scale);
-      else if (vec == 16) rc = launch_vec<T, 16>(a, scale);
-    }
-  }
-  if (rc <= 0) return rc;
-  const int64_t td = (int64_t)a.n_dst * a.H, ts = (int64_t)a.n_src * a.H;
-  if (td > 0) {
-    hipLaunchKernelGGL((gt_attn_bwd_dst_generic_kernel<T>), dim3((unsigned)((td + 127) / 128)), dim3(128), 0, a.stream,
+  const bool aligned = rows_aligned({{a.q, a.ldq}, {a.k, a.ldk}, {a.v, a.ldv}, {a.e, a.lde}, {a.out, a.ldo}, {a.d_out, a.lddo},
+                                     {a.dq, a.lddq}, {a.dk, a.lddk}, {a.dv, a.lddv}, {a.de, a.ldde}},
+                                    align_elems(AttnOp::Bwd, sizeof(T)));
+  const AttnPlan p = plan_attention(AttnOp::Bwd, a.H, a.C, 0, a.n_dst, a.n_src, aligned, false, 0);
+  if (p.route == AttnRoute::Wave)
+    return with_lane_layout(p, [&](auto vec_c, auto lph_c) {
+      constexpr int VEC = decltype(vec_c)::value, LPH = decltype(lph_c)::value;
+      if (p.grid_dst > 0) {
+        hipLaunchKernelGGL((gt_attn_bwd_dst_kernel<T, VEC, LPH>), dim3(p.grid_dst), dim3(64 * kBwdWaves), 0, a.stream, (const T*)a.q,
+                           a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)a.e, a.lde, (const T*)a.out, a.ldo, a.lse,
+                           (const T*)a.d_out, a.lddo, a.row, a.colptr, (T*)a.dq, a.lddq, (T*)a.de, a.ldde, a.p_ws, a.ds_ws, a.n_dst,
+                           a.H, scale, a.drop_p, a.drop_seed);
+        const int rc = check_launch("gt_attn_bwd_dst_kernel");
+        if (rc != ANEMOI_OK) return rc;
+      }
+      return launch_src_pass<T, VEC, LPH>(a, p);
+    });
+  if (p.grid_dst > 0) {
+    hipLaunchKernelGGL((gt_attn_bwd_dst_generic_kernel<T>), dim3(p.grid_dst), dim3(128), 0, a.stream,
                        (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, (const T*)a.e, a.lde, (const T*)a.out,
                        a.ldo, a.lse, (const T*)a.d_out, a.lddo, a.row, a.colptr, (T*)a.dq, a.lddq, (T*)a.de, a.ldde, a.p_ws,
                        a.ds_ws, a.n_dst, a.H, a.C, scale, a.drop_p, a.drop_seed);
-    rc = check_launch("gt_attn_bwd_dst_generic_kernel");
+    const int rc = check_launch("gt_attn_bwd_dst_generic_kernel");
     if (rc != ANEMOI_OK) return rc;
   }
-  if (ts > 0) {
-    hipLaunchKernelGGL((gt_attn_bwd_src_generic_kernel<T>), dim3((unsigned)((ts + 127) / 128)), dim3(128), 0, a.stream,
+  if (p.grid_src > 0) {
+    hipLaunchKernelGGL((gt_attn_bwd_src_generic_kernel<T>), dim3(p.grid_src), dim3(128), 0, a.stream,
                        (const T*)a.q, a.ldq, (const T*)a.d_out, a.lddo, a.rowptr, a.edge_ids, a.edge_dst, a.p_ws, a.ds_ws,
                        (T*)a.dk, a.lddk, (T*)a.dv, a.lddv, a.n_src, a.H, a.C);
     return check_launch("gt_attn_bwd_src_generic_kernel");
@@ -340,12 +315,6 @@ int launch(const BwdArgs& a) {
 //   df_e   = sum_h p_{e,h} gw_{d,h} + dS_{e,h} qw_{d,h} / sqrt(C)
 // Destination pass: dq, the per-edge scalars for the source pass (unchanged), and the per-(destination, head) vectors
 // sfP, sfS (and qw, gw when the edge attributes are trained) into fp32 workspaces; dW' and df are two small streaming kernels.
-template <int VEC, int FE_PAD>
-struct WLayoutB {
-  static constexpr int kChunk = VEC * FE_PAD + 4;
-  static constexpr int kFloats = 64 * kChunk;
-};
-
 template <typename T, int VEC, int LPH, int FE_PAD>
 __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_fused_kernel(
     const T* __restrict__ q, int64_t ldq, const T* __restrict__ k, int64_t ldk, const T* __restrict__ v, int64_t ldv,
@@ -356,7 +325,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_fused_kernel(
     int64_t lddadd, int n_dst, int H, float scale) {
   // addend != NULL: `out` is the forward's result INCLUDING the addend (o = out - addend); d_addend != NULL: receives dO (the
   // gradient of the addend) - both save an elementwise kernel around the op.
-  using L = WLayoutB<VEC, FE_PAD>;
+  using L = WLayout<VEC, FE_PAD>;
   extern __shared__ __attribute__((aligned(16))) float w_lds[];  // [64][kChunk], chunk layout [feature][channel]
   const int lane = threadIdx.x & 63;
   const int c0 = lane * VEC;
@@ -488,7 +457,6 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_fused_kernel(
 }
 
 // dW'[c][f] partial sums: persistent waves over the destinations, fixed-order in-block sum, one fp32 row per block.
-constexpr int kWgradBlocks = 256;
 template <typename T, int VEC, int LPH, int FE_PAD>
 __global__ __launch_bounds__(64 * kBwdWaves) void edge_weight_grad_kernel(const T* __restrict__ q, int64_t ldq, const T* __restrict__ d_out,
                                                                           int64_t lddo, const float* __restrict__ sf_ws,
@@ -615,32 +583,22 @@ struct FusedBwdArgs {
 };
 
 template <typename T, int VEC, int LPH, int FE_PAD>
-int launch_fused_cfg(const FusedBwdArgs& f, float scale) {
-  using L = WLayoutB<VEC, FE_PAD>;
+int launch_fused_cfg(const FusedBwdArgs& f, const AttnPlan& p, float scale) {
   const BwdArgs& a = f.b;
   const dim3 block(64 * kBwdWaves);
-  if (L::kFloats * sizeof(float) > 64 * 1024) return 1;
-  if (a.n_dst > 0) {
-    int blocks = (a.n_dst + kBwdWaves - 1) / kBwdWaves;
-    blocks = blocks < 256 * 6 ? blocks : 256 * 6;
-    hipLaunchKernelGGL((gt_attn_bwd_dst_fused_kernel<T, VEC, LPH, FE_PAD>), dim3(blocks), block, L::kFloats * sizeof(float), a.stream,
-                       (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, f.feat, f.w_packed, (const T*)a.out, a.ldo,
-                       a.lse, (const T*)a.d_out, a.lddo, a.row, a.colptr, (T*)a.dq, a.lddq, a.p_ws, a.ds_ws, f.sf_ws, f.qg_ws,
-                       (const T*)f.addend, f.ldadd, (T*)f.d_addend, f.lddadd, a.n_dst, a.H, scale);
-    int rc = check_launch("gt_attn_bwd_dst_fused_kernel");
-    if (rc != ANEMOI_OK) return rc;
-  }
+  hipLaunchKernelGGL((gt_attn_bwd_dst_fused_kernel<T, VEC, LPH, FE_PAD>), dim3(p.grid_dst), block, p.lds_bytes, a.stream,
+                     (const T*)a.q, a.ldq, (const T*)a.k, a.ldk, (const T*)a.v, a.ldv, f.feat, f.w_packed, (const T*)a.out, a.ldo,
+                     a.lse, (const T*)a.d_out, a.lddo, a.row, a.colptr, (T*)a.dq, a.lddq, a.p_ws, a.ds_ws, f.sf_ws, f.qg_ws,
+                     (const T*)f.addend, f.ldadd, (T*)f.d_addend, f.lddadd, a.n_dst, a.H, scale);
+  int rc = check_launch("gt_attn_bwd_dst_fused_kernel");
+  if (rc != ANEMOI_OK) return rc;
   const int nw = 64 * VEC * FE_PAD;
-  int wb = (a.n_dst + kBwdWaves - 1) / kBwdWaves;
-  wb = wb < kWgradBlocks ? wb : kWgradBlocks;
-  if (wb > 0) {
-    hipLaunchKernelGGL((edge_weight_grad_kernel<T, VEC, LPH, FE_PAD>), dim3(wb), block, nw * sizeof(float), a.stream, (const T*)a.q, a.ldq,
-                       (const T*)a.d_out, a.lddo, f.sf_ws, f.part_ws, a.n_dst, a.H);
-    int rc = check_launch("edge_weight_grad_kernel");
-    if (rc != ANEMOI_OK) return rc;
-  }
-  hipLaunchKernelGGL(sum_partial_rows_kernel, dim3((nw + 63) / 64), dim3(1024), 0, a.stream, f.part_ws, wb, nw, 64 * VEC, f.d_w_packed);
-  int rc = check_launch("sum_partial_rows_kernel");
+  hipLaunchKernelGGL((edge_weight_grad_kernel<T, VEC, LPH, FE_PAD>), dim3(p.grid_wgrad), block, nw * sizeof(float), a.stream, (const T*)a.q,
+                     a.ldq, (const T*)a.d_out, a.lddo, f.sf_ws, f.part_ws, a.n_dst, a.H);
+  rc = check_launch("edge_weight_grad_kernel");
+  if (rc != ANEMOI_OK) return rc;
+  hipLaunchKernelGGL(sum_partial_rows_kernel, dim3((nw + 63) / 64), dim3(1024), 0, a.stream, f.part_ws, (int)p.grid_wgrad, nw, 64 * VEC, f.d_w_packed);
+  rc = check_launch("sum_partial_rows_kernel");
   if (rc != ANEMOI_OK) return rc;
   if (f.d_feat != nullptr && f.n_edges > 0) {
     const int64_t threads = (int64_t)f.n_edges * 16;
@@ -649,53 +607,27 @@ int launch_fused_cfg(const FusedBwdArgs& f, float scale) {
     rc = check_launch("edge_feat_grad_kernel");
     if (rc != ANEMOI_OK) return rc;
   }
-  if (a.n_src > 0) {
-    hipLaunchKernelGGL((gt_attn_bwd_src_kernel<T, VEC, LPH>), dim3((a.n_src + kBwdWaves - 1) / kBwdWaves), block, 0, a.stream,
-                       (const T*)a.q, a.ldq, (const T*)a.d_out, a.lddo, a.rowptr, a.edge_ids, a.edge_dst, a.p_ws, a.ds_ws,
-                       (T*)a.dk, a.lddk, (T*)a.dv, a.lddv, a.n_src, a.H);
-    return check_launch("gt_attn_bwd_src_kernel");
-  }
-  return ANEMOI_OK;
+  return launch_src_pass<T, VEC, LPH>(a, p);
 }
 
-template <typename T, int VEC, int LPH>
-int launch_fused_fe(const FusedBwdArgs& f, float scale) {
-  switch (f.fe_pad) {
-    case 4: return launch_fused_cfg<T, VEC, LPH, 4>(f, scale);
-    case 8: return launch_fused_cfg<T, VEC, LPH, 8>(f, scale);
-    case 12: return launch_fused_cfg<T, VEC, LPH, 12>(f, scale);
-    case 16: return launch_fused_cfg<T, VEC, LPH, 16>(f, scale);
-    default: return 1;
-  }
-}
-
-// The fused backward covers the shapes the production configs use (H*C = 64 * VEC with VEC = 8 for 16-bit / 4 or 8 for fp32
-// models of 256 / 512 channels, and the 64-channel test models); anything else reports ANEMOI_E_UNSUPPORTED and the caller
-// trains through the materialised-E op.
+// Shapes the plan does not send to the wave kernels report ANEMOI_E_UNSUPPORTED and the caller trains through the materialised-E op.
 template <typename T>
 int launch_fused(const FusedBwdArgs& f) {
   const BwdArgs& a = f.b;
-  const int D = a.H * a.C;
   const float scale = 1.0f / sqrtf((float)a.C);
-  const int64_t vb = 16 / (int64_t)sizeof(T);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool aligned = a.ldq % vb == 0 && a.ldk % vb == 0 && a.ldv % vb == 0 && a.ldo % vb == 0 && a.lddo % vb == 0 && a.lddq % vb == 0 &&
-                       a.lddk % vb == 0 && a.lddv % vb == 0 && al16(a.q) && al16(a.k) && al16(a.v) && al16(a.out) && al16(a.d_out) &&
-                       al16(a.dq) && al16(a.dk) && al16(a.dv) && al16(f.addend) && al16(f.d_addend) && f.ldadd % vb == 0 && f.lddadd % vb == 0;
-  int rc = 1;
-  if (D % 64 == 0 && aligned) {
-    const int vec = D / 64, lph = a.C % vec == 0 ? a.C / vec : 0;
-    if (vec == 8 && lph == 4) rc = launch_fused_fe<T, 8, 4>(f, scale);        // 512 channels, C = 32
-    else if (vec == 8 && lph == 8) rc = launch_fused_fe<T, 8, 8>(f, scale);   // 512 channels, C = 64
-    else if (vec == 4 && lph == 8) rc = launch_fused_fe<T, 4, 8>(f, scale);   // 256 channels, C = 32
-    else if (vec == 1 && lph == 16) rc = launch_fused_fe<T, 1, 16>(f, scale); // 64 channels, C = 16 (test models)
-    else if (vec == 1 && lph == 8) rc = launch_fused_fe<T, 1, 8>(f, scale);   // 64 channels, C = 8
-  }
-  if (rc > 0) {
+  const bool aligned = rows_aligned({{a.q, a.ldq}, {a.k, a.ldk}, {a.v, a.ldv}, {a.out, a.ldo}, {a.d_out, a.lddo}, {a.dq, a.lddq},
+                                     {a.dk, a.lddk}, {a.dv, a.lddv}, {f.addend, f.ldadd}, {f.d_addend, f.lddadd}},
+                                    align_elems(AttnOp::BwdFusedEdge, sizeof(T)));
+  const AttnPlan p = plan_attention(AttnOp::BwdFusedEdge, a.H, a.C, f.fe_pad, a.n_dst, a.n_src, aligned, false, 0);
+  if (p.route != AttnRoute::Wave) {
     set_error("gt_attention_fused_edge_bwd: shape H=%d C=%d fe_pad=%d is not covered by the fused backward", a.H, a.C, f.fe_pad);
     return ANEMOI_E_UNSUPPORTED;
   }
-  return rc;
+  return with_lane_layout<true>(p, [&](auto vec_c, auto lph_c) {
+    return with_fe_pad(p, [&](auto fe_pad_c) {
+      return launch_fused_cfg<T, decltype(vec_c)::value, decltype(lph_c)::value, decltype(fe_pad_c)::value>(f, p, scale);
+    });
+  });
 }
 
 }  // namespace

@@ -273,13 +273,45 @@ def gt_attention_backward(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, e: Ten
     return dq, dk, dv, de
 
 
+ATTENTION_OPS = ("forward", "forward_fused_edge", "backward", "backward_fused_edge")  # which entry point: AttnOp of csrc/gt_attention_plan.h
+ATTENTION_ROUTES = ("unsupported", "generic", "wave")                                  # AttnRoute
+
+
+class AttentionPlan(NamedTuple):
+    """What an edge-attention entry point launches for a shape: ``route`` (one of ATTENTION_ROUTES), the wave kernel's lane layout
+    (``vec`` channels per lane, ``lph`` lanes per head), and the launch geometry; fields as in anemoi_gt_attention_plan_t."""
+    route: str
+    vec: int
+    lph: int
+    fe_pad: int
+    kv_adjacent: bool
+    lds_bytes: int
+    grid_dst: int
+    grid_src: int
+    grid_wgrad: int
+
+
+def gt_attention_plan(op: str, num_heads: int, C: int, *, fe_pad: int = 0, n_dst: int = 1, n_src: int = 1, dtype: torch.dtype = torch.bfloat16,
+                      rows_aligned: bool = True, kv_adjacent: bool = False) -> AttentionPlan:
+    """The kernel choice of ``gt_attention`` / ``gt_attention_fused_edge`` and their backwards (``op``: one of ATTENTION_OPS) for
+    ``num_heads`` heads of ``C`` channels, under ANEMOI_ATTN_BLOCKS_PER_CU of this process.  Host-only: nothing is launched and no GPU
+    is needed.  ``rows_aligned`` / ``kv_adjacent``: the two facts the entry points read off their operands (contiguous tensors are
+    aligned; k | v adjacent is the fused projection buffer).  ``route == "unsupported"`` where the entry point refuses the shape."""
+    out = _lib.AttentionPlan()
+    rc = _lib.load().anemoi_gt_attention_plan(ATTENTION_OPS.index(op), num_heads, C, fe_pad, n_dst, n_src, int(rows_aligned), int(kv_adjacent),
+                                              _DT[dtype], out)
+    if rc != _lib.E_UNSUPPORTED:
+        _lib.check(rc, "gt_attention_plan")
+    f = {name: getattr(out, name) for name, _ in out._fields_}
+    return AttentionPlan(**{**f, "route": ATTENTION_ROUTES[out.route], "kv_adjacent": bool(out.kv_adjacent)})
+
+
 def fused_edge_backward_supported(D: int, num_heads: int, fe: int) -> bool:
-    """Shapes the fused-edge backward kernels are instantiated for (csrc/gt_attention_bwd.hip: launch_fused)."""
-    if D % 64 or D % num_heads:
+    """Whether ``gt_attention_fused_edge_backward`` takes [*, D] rows of ``num_heads`` heads with ``fe`` edge attributes (contiguous
+    operands): the plan's answer, the same function the entry point launches from."""
+    if D <= 0 or num_heads <= 0 or D % num_heads:
         return False
-    vec, C = D // 64, D // num_heads
-    lph = C // vec if vec and C % vec == 0 else 0
-    return (vec, lph) in ((8, 4), (8, 8), (4, 8), (1, 16), (1, 8)) and edge_feature_pad(fe) <= 16
+    return gt_attention_plan("backward_fused_edge", num_heads, D // num_heads, fe_pad=edge_feature_pad(fe)).route == "wave"
 
 
 def gt_attention_fused_edge_backward(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, edge_feat: Tensor, w_packed: Tensor, out: Tensor,

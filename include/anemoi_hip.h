@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 23
+#define ANEMOI_HIP_ABI_VERSION 24
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -126,6 +126,25 @@ int anemoi_gt_attention_fused_edge_bwd(const void* q, int64_t ldq, const void* k
                                        float* d_edge_feat, float* p_ws, float* ds_ws, float* sf_ws, float* qg_ws, float* part_ws,
                                        const void* addend, int64_t ldadd, void* d_addend, int64_t lddadd, int32_t n_dst,
                                        int32_t n_src, int32_t n_edges, int32_t H, int32_t C, anemoi_dtype_t dtype, void* stream);
+
+/* Which kernel the four edge-attention ops above run for a shape, and on what launch geometry: the decision of
+ * csrc/gt_attention_plan.h, asked without launching anything.  HOST-ONLY: no HIP call, no device needed.  op: 0 anemoi_gt_attention_fwd
+ * (and _dropout_fwd), 1 anemoi_gt_attention_fused_edge_fwd, 2 anemoi_gt_attention_bwd (and _dropout_bwd), 3
+ * anemoi_gt_attention_fused_edge_bwd;  fe_pad is read by the fused-edge ops only.  Two facts about the operands come from the caller:
+ * rows_aligned (every pointer 16-byte aligned, every leading dimension a multiple of 8 elements for the forwards and of 16 bytes for
+ * the backwards - what contiguous torch tensors of these shapes satisfy) and kv_adjacent (v is the H*C columns behind k in one buffer
+ * whose row offsets fit 32 bits; op 1 only).  ANEMOI_ATTN_BLOCKS_PER_CU is that of the calling process.  ANEMOI_E_UNSUPPORTED where
+ * the op's entry point would refuse the shape (`out` is filled all the same).
+ *   route: 0 unsupported, 1 generic kernel (one thread per row and head), 2 wave kernel (one wave64 per row);  vec, lph: channels per
+ *   lane and lanes per head of the wave kernel (0 otherwise);  fe_pad, kv_adjacent: as instantiated;  lds_bytes: dynamic LDS of the
+ *   forward / destination pass;  grid_dst, grid_src, grid_wgrad: workgroups of the forward or destination pass, of the backward's
+ *   source pass and of the fused-edge backward's weight-gradient kernel (0: not launched). */
+typedef struct {
+  int32_t route, vec, lph, fe_pad, kv_adjacent, lds_bytes;
+  uint32_t grid_dst, grid_src, grid_wgrad;
+} anemoi_gt_attention_plan_t;
+int anemoi_gt_attention_plan(int32_t op, int32_t H, int32_t C, int32_t fe_pad, int32_t n_dst, int32_t n_src, int32_t rows_aligned,
+                             int32_t kv_adjacent, anemoi_dtype_t dtype, anemoi_gt_attention_plan_t* out);
 
 /* Pack lin_edge's parameters for the fused op: out fp32 [D, fe_pad] = [w_edge [D,Fe] | b_edge [D] (or 0) | 0...]. */
 int anemoi_pack_edge_weights(const void* w_edge, const void* b_edge, float* out, int32_t D, int32_t fe, int32_t fe_pad,

@@ -33,7 +33,9 @@ Branch coverage by construction (the inequalities are those of the launch code):
   (256 workgroups: second, partly clamped stride above 1 024) and ``sum_partial_rows_kernel`` (two-chain loop above 16 partial rows,
   i.e. 64 destinations): n_dst = 131, 600, 1 500, 7 177, 12 300 give 33, 150, 256, 256, 256 partial rows;
 * all 25 (VEC, LPH) in {1, 2, 4, 8, 16}^2 of the forward (materialised and fused, three dtypes) and of the materialised backward,
-  and the fall-back of the fused forward to the generic kernel when the W' image exceeds 64 KiB (VEC = 16, fe_pad = 16).
+  and the fall-back of the fused forward to the generic kernel when the W' image exceeds 64 KiB (VEC = 16, fe_pad = 16);
+* operands that fail the alignment rule (row stride D + 1, one element into the buffer): the generic forward and backward kernels
+  on a wave-kernel shape.  Which route every shape takes is asserted without a GPU in tests/test_attention_plan_cpu.py.
 
 What these tests found, and the fix: ``gt_attn_bwd_dst_kernel`` formed D = <dO, out> from the forward's ``out``.  A 16-bit ``out``
 carries its own rounding (2^-9 |o|) into D, and for an edge that dominates the softmax <dO, v + E> - D cancels, so that rounding is
@@ -526,3 +528,53 @@ def test_dispatch_backward(ops, vec, lph, dtype):
     c = _dispatch_case(H, C, dtype, 7)
     c["ea"] = None  # the materialised op only: the fused backward is instantiated for five of the 25
     _check_backward(ops, f"dispatch-bwd v{vec} l{lph} {NAME[dtype]}", c, H, dtype, zero_dst=c["no_in_edges"], zero_src=c["no_out_edges"])
+
+
+def _unaligned(t):
+    """The values of t [n, D] on the device as a view no wave kernel takes: row stride D + 1, starting one element into its buffer."""
+    n, D = t.shape
+    buf = torch.zeros(n * (D + 1) + 1, dtype=t.dtype, device=DEV)
+    view = buf[1:].view(n, D + 1)[:, :D]
+    view.copy_(t)
+    assert view.data_ptr() % 16 != 0 and view.stride() == (D + 1, 1)
+    return view
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=NAME.get)
+def test_operands_that_fail_the_alignment_rule_take_the_generic_kernels(ops, dtype):
+    """(4, 16) is a wave-kernel shape (VEC 1, LPH 16); with q / k / v / e / out / d_out / dq / dk / dv as unaligned views the plan sends
+    the forward and the materialised backward to the one-thread-per-head kernels (the wrappers pass views through, pointer and row
+    stride).  Same reference and bounds as the dispatch tests above."""
+    H, C = 4, 16
+    D = H * C
+    tag = f"dispatch-unaligned H{H} C{C} {NAME[dtype]}"
+    c = _dispatch_case(H, C, dtype, 7)
+    ei, n_src, n_dst = c["ei"], c["n_src"], c["n_dst"]
+    for op in ("forward", "backward"):
+        assert ops.gt_attention_plan(op, H, C, n_dst=n_dst, n_src=n_src, dtype=dtype).route == "wave"
+        assert ops.gt_attention_plan(op, H, C, n_dst=n_dst, n_src=n_src, dtype=dtype, rows_aligned=False).route == "generic"
+    csc = ops.build_csc(ei.to(DEV), (n_src, n_dst))
+    rev = ops.build_reverse_csr(csc)
+    qd, kd, vd, ed, gd = (_unaligned(c[n]) for n in "qkveg")
+    empty, unused = c["no_in_edges"].to(DEV), c["no_out_edges"].to(DEV)
+    want, want_lse = _attention(c["q"].double(), c["k"].double(), c["v"].double(), c["e"].double(), ei, n_dst, H)
+    out, lse = ops.gt_attention(qd, kd, vd, ed, csc, H, return_lse=True)
+    assert out.dtype == dtype and lse.dtype == F32
+    _close(tag, out, want, dtype, "out")
+    _close(tag, lse, want_lse, F32, "lse")
+    assert float(out[empty].abs().max()) == 0.0 and float(lse[empty].abs().max()) == 0.0
+    again = ops.gt_attention(qd, kd, vd, ed, csc, H, return_lse=True)
+    assert torch.equal(out, again[0]) and torch.equal(lse, again[1])
+
+    def backward():
+        into = tuple(_unaligned(torch.full((n, D), 7.0, dtype=dtype)) for n in (n_dst, n_src, n_src))
+        return ops.gt_attention_backward(gd, qd, kd, vd, ed, _unaligned(out), lse, csc, rev, H, grads_out=into)
+
+    got = backward()
+    for name, a, r in zip(("dq", "dk", "dv", "de"), got, _grads(c["g"], c["q"], c["k"], c["v"], ei, n_dst, H, e=c["e"])):
+        assert a.dtype == dtype
+        _close(tag, a, r, dtype, name)
+    assert float(got[0][empty].abs().max()) == 0.0
+    if unused.numel():
+        assert float(got[1][unused].abs().max()) == 0.0 and float(got[2][unused].abs().max()) == 0.0
+    assert all(torch.equal(x, y) for x, y in zip(got, backward()))
