@@ -577,7 +577,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
   }
 }
 
-static int chain_rows_per_tile(int n_rows, int cap = kPanel) {
+static int chain_rows_per_tile(int n_rows, int cap = kPanel) {  // mirrored by tests/chain_refs.py panel_split: change both together
   static const int forced = env_int(getenv("ANEMOI_CHAIN_ROWS"), 0, 0, 64);
   if (forced > 0) return forced < cap ? forced : cap;
   const int64_t rounds = ((int64_t)n_rows + 256 * cap - 1) / (256 * cap);
