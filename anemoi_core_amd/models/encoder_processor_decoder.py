@@ -115,7 +115,7 @@ class AnemoiModelEncProcDec(nn.Module):
         )
         self._calculate_shapes_and_indices(data_indices)
         self._build_networks(mc, edges)
-        self._build_residual(mc, residual_graph)
+        self._build_residual(mc, residual_graph, nodes)
         self.boundings = self._build_boundings(mc.get("bounding", []) or [])
         self._pad_zeros = self._hidden_padded = None
         self._bound_tables: dict = {}
@@ -170,11 +170,13 @@ class AnemoiModelEncProcDec(nn.Module):
                                            in_channels_dst=self.target_dim[ds], hidden_dim=self.num_channels,
                                            out_channels_dst=self.output_dim[ds], edge_dim=self.decoder_graph_provider[ds].edge_dim)
 
-    def _build_residual(self, mc, graph) -> None:
+    def _build_residual(self, mc, graph, nodes=None) -> None:
         """models/base.py:244-258: ``model.residual`` instantiated per dataset.  An absent or empty entry is the SkipConnection of the last
         step.  A TruncatedConnection gets the device-resident column vectors of its compact skip: the prognostic input columns it projects and
-        the map from output column to compact column (non-persistent buffers: nothing is added to the state_dict)."""
-        from ..layers.residual import SkipConnection, TruncatedConnection
+        the map from output column to compact column (non-persistent buffers: nothing is added to the state_dict); so does a
+        SpectralOrnsteinConnection, whose skip is compact as well (``_truncated`` = the skip is the compact normalised one).  It reads the data
+        nodes' coordinates only, so a graph without residual node sets hands it ``nodes`` (name -> coordinates)."""
+        from ..layers.residual import SkipConnection, SpectralOrnsteinConnection, TruncatedConnection
 
         cfg = mc.get("residual", None) or {}
         chunks = (mc.get("sparse_projector", None) or {}).get("num_chunks", 1)
@@ -184,14 +186,16 @@ class AnemoiModelEncProcDec(nn.Module):
                 self.residual[ds] = SkipConnection(step=int(cfg.get("step", -1)))
                 continue
             target = _retarget(cfg)["_target_"]
-            if target not in (_OUR_PREFIX + "residual.SkipConnection", _OUR_PREFIX + "residual.TruncatedConnection"):
-                raise NotImplementedError(f"residual '{cfg['_target_']}' is not implemented; supported: SkipConnection, TruncatedConnection "
-                                          "(layers/residual.py)")
+            if target not in (_OUR_PREFIX + "residual.SkipConnection", _OUR_PREFIX + "residual.TruncatedConnection",
+                              _OUR_PREFIX + "residual.SpectralOrnsteinConnection"):
+                raise NotImplementedError(f"residual '{cfg['_target_']}' is not implemented; supported: SkipConnection, TruncatedConnection, "
+                                          "SpectralOrnsteinConnection (layers/residual.py)")
             stats = self.statistics.get(ds) if isinstance(self.statistics, dict) else self.statistics
-            self.residual[ds] = instantiate(_retarget(cfg), _recursive_=False, graph=graph, data_node_name=ds if len(self.dataset_names) > 1 else "data",
+            ornstein = target.endswith("SpectralOrnsteinConnection")
+            self.residual[ds] = instantiate(_retarget(cfg), _recursive_=False, graph=nodes if ornstein and graph is None else graph, data_node_name=ds if len(self.dataset_names) > 1 else "data",
                                             statistics=stats, data_indices=self.data_indices[ds], dataset_name=ds,
                                             sparse_projector_num_chunks=chunks)
-            if isinstance(self.residual[ds], TruncatedConnection):
+            if isinstance(self.residual[ds], (TruncatedConnection, SpectralOrnsteinConnection)):
                 out_idx, in_idx = self._internal_output_idx[ds], self._internal_input_idx[ds]
                 cmap = torch.full((self.num_output_channels[ds],), -1, dtype=torch.int32)
                 cmap[torch.tensor(out_idx, dtype=torch.long)] = torch.arange(len(out_idx), dtype=torch.int32)
@@ -199,13 +203,17 @@ class AnemoiModelEncProcDec(nn.Module):
                 self.register_buffer(f"_prog_cols_{ds}", torch.tensor(in_idx, dtype=torch.int32), persistent=False)
         first = self.residual[self.dataset_names[0]]
         self._skip_step = int(first.step) if isinstance(first, SkipConnection) else -1
-        self._truncated = {ds: isinstance(self.residual[ds], TruncatedConnection) for ds in self.dataset_names}
+        self._ornstein = {ds: isinstance(self.residual[ds], SpectralOrnsteinConnection) for ds in self.dataset_names}
+        self._truncated = {ds: isinstance(self.residual[ds], TruncatedConnection) or self._ornstein[ds] for ds in self.dataset_names}
         self._skip_programs: dict = {}
 
     def _truncated_skip(self, ds: str, x_last: Tensor, raw: bool, norm, shard_sizes) -> Tensor:
         """The truncated residual of one forward: x_last [batch, ensemble, grid, vars] (the last input step, read in place) -> the
         NORMALISED compact skip [batch, ensemble, grid, prognostic columns].  ``raw``: x_last is the raw batch (``predict_step`` fused the
         input normaliser), whose column program then runs on every value the down projection gathers."""
+        if self._ornstein[ds]:
+            raise NotImplementedError("SpectralOrnsteinConnection is wired into AnemoiModelEncProcDec only (its forward computes the skip "
+                                      "before the input assembly); the ensemble model does not support it yet")
         if shard_sizes is not None:
             raise NotImplementedError("TruncatedConnection with a sharded data grid (grid_shard_sizes) needs the reference's grid-to-channel "
                                       "transposes (layers/residual.py:287-293) and is not implemented; pass the whole grid")
@@ -449,12 +457,22 @@ class AnemoiModelEncProcDec(nn.Module):
             shard_sizes_data = grid_shard_sizes[ds] if in_out_sharded[ds] else None
             norm_in, norm_out, *rest = (_fused_norm or {}).get(ds, (None, None))
             imputer, remapper, post_members = (tuple(rest) + (None, None, None))[:3]
-            x_data_latent, x_skip, raw, nan_mask, remap_fused = self._assemble_input(x[ds], batch_size, shard_sizes_data, model_comm_group, ds,
+            x_ds, ornstein_skip = x[ds], None
+            if self._ornstein[ds]:
+                # the Ornstein form acts on normalised values (predict_step does not fuse the normaliser for it).  The reference's residual
+                # runs first and leaves its low-pass filtered fields in the model input (layers/residual.py:560-563 through
+                # _assemble_input, models/encoder_processor_decoder.py:110-127): the encoder sees them, so it does here - on a copy
+                assert norm_in is None, "SpectralOrnsteinConnection takes normalised inputs"
+                res = self.residual[ds]
+                x_ds = x_ds.clone() if res.truncate else x_ds
+                ornstein_skip = res.compact(x_ds[:, -1], shard_sizes_data, write_back=res.truncate)
+            x_data_latent, x_skip, raw, nan_mask, remap_fused = self._assemble_input(x_ds, batch_size, shard_sizes_data, model_comm_group, ds,
                                                                                      norm=norm_in, imputer=imputer, remapper=remapper)
             if nan_mask is not None:  # the nan_locations the imputer's own transform would have left; no loss mask at inference
                 imputer.record_nan_locations(nan_mask.unsqueeze(0), nan_mask.shape[-1], loss_mask=False)
             if self._truncated[ds]:  # once per dataset and forward: down (columns, normaliser), up; the skip is then normalised
-                x_skip, raw = self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data), False
+                x_skip = ornstein_skip if self._ornstein[ds] else self._truncated_skip(ds, x_skip, raw, norm_in, shard_sizes_data)
+                raw = False
             skips[ds], data_shards[ds] = _EdgeState(x_skip, raw, norm_in, norm_out, imputer, nan_mask, remapper, remap_fused, post_members), shard_sizes_data
             if (_SIDE_JOB and carrier is not None and model_comm_group is None and not torch.is_grad_enabled()
                     and isinstance(self.decoder[ds], GraphTransformerBackwardMapper)):
@@ -562,7 +580,7 @@ class AnemoiModelEncProcDec(nn.Module):
                 same = pre is not None and post is not None and len(pre) == len(post) and pre[0] is post[0]
                 if same and len(pre) == 4:  # a Remapper or post-processors: the same modules in the same order (the normalisers may be two)
                     same = len(pre[3]) == len(post[3]) and all(a is b or (a is pre[1] and b is post[1]) for a, b in zip(pre[3], post[3]))
-                if same and x[ds].is_cuda:
+                if same and x[ds].is_cuda and not self._ornstein[ds]:  # (the Ornstein residual acts on normalised values)
                     imputer, remapper, members = pre[0], (pre[2] if len(pre) == 4 else None), (post[3] if len(post) == 4 else None)
                     pre, post = pre[1], post[1]
                     fused[ds] = (pre, post) if imputer is None and members is None else (pre, post, imputer, remapper, members)

@@ -1912,3 +1912,223 @@ def graph_transformer_attention_conv(query: Tensor, key: Tensor, value: Tensor, 
     rowptr, edge_ids, edge_dst = reverse
     out, _saved, _m = graph_transformer_attention(query, key, value, edges, row, colptr, rowptr, edge_ids, edge_dst)
     return out
+
+
+# ------------------------------------------------------------------------------------------ spherical-harmonic transforms
+@dataclass(frozen=True)
+class ShtGrid:
+    """A grid of latitude rings as the transform kernels want it (csrc/sht.hip): ring offsets int32 [K + 1] and the twiddle table fp32
+    [grid, 2] = (cos, -sin)(2 pi t / n_k) at s_k + t, evaluated in float64 and rounded once; both on ``device``."""
+    lons_per_lat: tuple
+    ring_offsets: Tensor
+    twiddles: Tensor
+
+    @property
+    def n_rings(self) -> int:
+        return len(self.lons_per_lat)
+
+    @property
+    def n_grid(self) -> int:
+        return int(sum(self.lons_per_lat))
+
+    @property
+    def max_ring(self) -> int:
+        return int(max(self.lons_per_lat))
+
+
+_SHT_GRIDS: dict = {}
+
+
+def sht_twiddles(lons_per_lat) -> "np.ndarray":
+    """float64 [grid, 2]: (cos, -sin)(2 pi t / n_k) for t < n_k, ring after ring."""
+    import numpy as np
+
+    out = []
+    for n in lons_per_lat:
+        ang = 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+        out.append(np.stack([np.cos(ang), -np.sin(ang)], axis=1))
+    return np.concatenate(out, axis=0)
+
+
+def sht_grid(lons_per_lat, device) -> ShtGrid:
+    """The ShtGrid of ``lons_per_lat`` on ``device``, built once per (grid, device)."""
+    import numpy as np
+
+    lons = tuple(int(n) for n in lons_per_lat)
+    if not lons or min(lons) <= 0:
+        raise ValueError(f"sht_grid: every ring needs at least one point, got {list(lons)[:8]}...")
+    key = (lons, str(torch.device(device)))
+    hit = _SHT_GRIDS.get(key)
+    if hit is None:
+        off = np.concatenate([[0], np.cumsum(lons)]).astype(np.int32)
+        hit = ShtGrid(lons, torch.from_numpy(off).to(device), torch.from_numpy(sht_twiddles(lons).astype(np.float32)).to(device))
+        _SHT_GRIDS[key] = hit
+    return hit
+
+
+def sht_plan(direction: str, n_fields: int, lons_per_lat, truncation: int) -> dict:
+    """How ``sht_forward`` / ``sht_inverse`` tile a call (csrc/sht_plan.h) - host only, no GPU.  Raises ValueError where the entry points
+    refuse the shape (truncation outside [1, nlat], a ring without points)."""
+    lons = [int(n) for n in lons_per_lat]
+    arr = (_lib.C.c_int32 * max(len(lons), 1))(*lons)
+    plan = _lib.ShtPlan()
+    rc = _lib.load().anemoi_sht_plan({"forward": 0, "inverse": 1}[direction], int(n_fields), arr, len(lons), int(truncation), _lib.C.byref(plan))
+    _lib.check(rc, "sht_plan")
+    return dict(field_tile=plan.field_tile, chunk=plan.chunk, lds_bytes=plan.lds_bytes, lds_bound=plan.lds_bound, ring_threads=plan.ring_threads,
+                leg_rows=plan.leg_rows, ring_grid=tuple(plan.ring_grid), leg_grid=tuple(plan.leg_grid), workspace_bytes=plan.workspace_bytes)
+
+
+def _sht_check(t: Tensor, name: str, dtype) -> None:
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {t.dtype} (the transforms are fp32 / complex64 only)")
+
+
+def _sht_table(table: Tensor, grid: ShtGrid, name: str) -> int:
+    """L = M of a Legendre table [L, K, M] (fp32, contiguous, on the device)."""
+    if table.dim() != 3 or table.shape[0] != table.shape[2] or table.shape[1] != grid.n_rings or table.dtype != torch.float32 or not table.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous fp32 table [L, {grid.n_rings}, L], got {tuple(table.shape)} {table.dtype}")
+    return table.shape[0]
+
+
+def _sht_grid_side(x: Tensor, grid: ShtGrid, cols: Optional[Tensor], columns: bool):
+    """(tensor to address, lead shape, n_groups, n_cols, gs, ps) of the grid side of a transform."""
+    if columns:
+        if x.dim() < 2 or x.shape[-2] != grid.n_grid:
+            raise ValueError(f"sht: expected [..., {grid.n_grid}, V], got {tuple(x.shape)}")
+        if x.shape[-1] > 1 and x.stride(-1) != 1:
+            raise ValueError("sht: the last dimension of x must be contiguous")
+        xk = _two_leading(x)
+        if xk.shape[0] > 1 and xk.shape[1] > 1:  # leading dimensions that need two strides: one copy (a [B > 1, T, E > 1, ..] step slice)
+            xk = xk.contiguous().view(1, -1, *xk.shape[2:])
+        G = xk.shape[0] * xk.shape[1]
+        V = xk.shape[-1]
+        if cols is not None:
+            if cols.dtype != torch.int32 or cols.dim() != 1 or not cols.is_contiguous():
+                raise ValueError("sht: cols must be a contiguous int32 vector")
+        C = V if cols is None else cols.shape[0]
+        gs = xk.stride(0) if xk.shape[0] > 1 else (xk.stride(1) if xk.shape[1] > 1 else 0)
+        ps = xk.stride(2) if grid.n_grid > 1 else max(V, 1)
+        if gs < 0 or ps < max(V, 1):
+            raise ValueError("sht: x must have a non-negative group stride and a point stride of at least its width")
+        return xk, x.shape[:-2], G, C, gs, ps
+    if x.dim() < 1 or x.shape[-1] != grid.n_grid:
+        raise ValueError(f"sht: expected [..., {grid.n_grid}], got {tuple(x.shape)}")
+    if cols is not None:
+        raise ValueError("sht: cols select columns of a [..., grid, V] tensor (columns=True)")
+    xk = x.reshape(-1, grid.n_grid)
+    xk = xk if xk.is_contiguous() else xk.contiguous()
+    return xk, x.shape[:-1], xk.shape[0], 1, grid.n_grid, 1
+
+
+def sht_forward(x: Tensor, grid: ShtGrid, wleg: Tensor, cols: Optional[Tensor] = None, columns: bool = False) -> Tensor:
+    """Spherical-harmonic analysis, two launches (csrc/sht.hip; the reference's SphericalHarmonicTransform.forward,
+    layers/spectral_helpers.py:317-340).  x fp32: ``[..., grid]`` fields, or with ``columns=True`` a ``[..., grid, V]`` tensor read IN PLACE
+    (any row / leading strides; ``cols`` int32 on the device selects columns whose values the caller has checked to lie in [0, V)).
+    wleg: fp32 [L, K, M] (``spectral_helpers.legendre_tables``).  Returns complex64 ``[..., L, M]`` (fields) or ``[..., C, L, M]`` (columns).
+    Forward only: the adjoint kernels are not built."""
+    _dev(x, grid.ring_offsets, wleg, cols)
+    _sht_check(x, "sht_forward: x", torch.float32)
+    if _needs_grad(x):
+        raise NotImplementedError("sht_forward: the adjoint kernels of the spherical-harmonic transforms are not built; call it under "
+                                  "torch.no_grad() or on tensors that do not require grad")
+    L = _sht_table(wleg, grid, "sht_forward: wleg")
+    xk, lead, G, C, gs, ps = _sht_grid_side(x, grid, cols, columns)
+    F = G * C
+    coeffs = torch.empty((F, L, L, 2), dtype=torch.float32, device=x.device)
+    ws = torch.empty((max(F, 1) * grid.n_rings * L * 2,), dtype=torch.float32, device=x.device)
+    rc = _lib.load().anemoi_sht_fwd(xk.data_ptr(), gs, ps, 0 if cols is None else cols.data_ptr(), G, C, grid.ring_offsets.data_ptr(), grid.n_rings,
+                                    grid.max_ring, L - 1, grid.twiddles.data_ptr(), wleg.data_ptr(), coeffs.data_ptr(), ws.data_ptr(),
+                                    ws.numel() * 4, _stream())
+    _lib.check(rc, "sht_fwd")
+    out = torch.view_as_complex(coeffs)
+    return out.view(*lead, C, L, L) if columns else out.view(*lead, L, L)
+
+
+def sht_inverse(coeffs: Tensor, grid: ShtGrid, pleg: Tensor, lscale: Optional[Tensor] = None, columns: bool = False,
+                out: Optional[Tensor] = None, cols: Optional[Tensor] = None) -> Tensor:
+    """Spherical-harmonic synthesis, two launches (the reference's InverseSphericalHarmonicTransform.forward,
+    layers/spectral_helpers.py:530-553).  coeffs complex64 ``[..., L, M]``; lscale fp32 [S, L]: field f (flattened leading index) is
+    multiplied by lscale[f % S, l] on the way in.  Returns fp32 ``[..., grid]``; with ``columns=True`` coeffs is ``[..., C, L, M]`` and the
+    result ``[..., grid, C]`` (point-major) - or, with ``out`` [..., grid, V] (+ ``cols``), written in place into its columns."""
+    _dev(coeffs, grid.ring_offsets, pleg, lscale, out, cols)
+    _sht_check(coeffs, "sht_inverse: coeffs", torch.complex64)
+    if _needs_grad(coeffs, lscale):
+        raise NotImplementedError("sht_inverse: the adjoint kernels of the spherical-harmonic transforms are not built; call it under "
+                                  "torch.no_grad() or on tensors that do not require grad")
+    L = _sht_table(pleg, grid, "sht_inverse: pleg")
+    if coeffs.dim() < 2 + int(columns) or tuple(coeffs.shape[-2:]) != (L, L):
+        raise ValueError(f"sht_inverse: coefficients {tuple(coeffs.shape)} do not end in [{L}, {L}]")
+    c = torch.view_as_real(coeffs if coeffs.is_contiguous() else coeffs.contiguous())
+    if lscale is not None and (lscale.dim() != 2 or lscale.shape[1] != L or lscale.dtype != torch.float32 or not lscale.is_contiguous() or lscale.shape[0] < 1):
+        raise ValueError(f"sht_inverse: lscale must be contiguous fp32 [S, {L}], got {tuple(lscale.shape)} {lscale.dtype}")
+    if columns:
+        lead, C = coeffs.shape[:-3], coeffs.shape[-3]
+        if out is None:
+            if cols is not None:
+                raise ValueError("sht_inverse: cols need an out tensor")
+            out = torch.empty((*lead, grid.n_grid, C), dtype=torch.float32, device=coeffs.device)
+        _sht_check(out, "sht_inverse: out", torch.float32)
+        yk, olead, G, Cy, gs, ps = _sht_grid_side(out, grid, cols, True)
+        if yk.data_ptr() != out.data_ptr() or Cy != C or G * C != coeffs.numel() // (L * L):
+            raise ValueError(f"sht_inverse: out {tuple(out.shape)} does not take the coefficients' {tuple(coeffs.shape[:-2])} fields in place")
+    else:
+        if out is not None or cols is not None:
+            raise ValueError("sht_inverse: out / cols address a [..., grid, V] tensor (columns=True)")
+        lead = coeffs.shape[:-2]
+        out = torch.empty((*lead, grid.n_grid), dtype=torch.float32, device=coeffs.device)
+        G, C, gs, ps = coeffs.numel() // (L * L), 1, grid.n_grid, 1
+    F = G * C
+    ws = torch.empty((max(F, 1) * grid.n_rings * L * 2,), dtype=torch.float32, device=coeffs.device)
+    rc = _lib.load().anemoi_sht_inv(c.data_ptr(), 0 if lscale is None else lscale.data_ptr(), 1 if lscale is None else lscale.shape[0],
+                                    grid.ring_offsets.data_ptr(), grid.n_rings, grid.max_ring, L - 1, grid.twiddles.data_ptr(), pleg.data_ptr(),
+                                    out.data_ptr(), gs, ps, 0 if cols is None else cols.data_ptr(), G, C, ws.data_ptr(), ws.numel() * 4, _stream())
+    _lib.check(rc, "sht_inv")
+    return out
+
+
+def ornstein_combine(x_last: Tensor, prog_cols: Tensor, fields: Tensor, reg_cols: Optional[Tensor] = None, trunc_map: Optional[Tensor] = None,
+                     lowpass: Optional[Tensor] = None, walias: Optional[Tensor] = None, write_back: bool = False) -> Tensor:
+    """The spectral Ornstein residual's row-wise step, one launch (anemoi_ornstein_combine_fwd; the reference's
+    SpectralOrnsteinConnection._learnable, layers/residual.py:565-576):
+    out[..., p, c] = gain[p, c] xt + mu[p, c] + sum_i beta_i[p, c] x[..., p, reg_cols[i]] with fields = [gain, mu, beta_0, ..] fp32
+    [2 + R, grid, n_prog]; xt = x[..., p, prog_cols[c]], or for columns with trunc_map[c] = t >= 0 the low-pass field lowpass[..., p, t],
+    blended with x by walias[p, t] when given.  x_last [..., grid, V] fp32 is read in place.  Returns the compact skip [..., grid, n_prog].
+    The column vectors are int32 on the device; the caller has checked that they lie inside x's columns.  ``write_back``: xt is also
+    written into the truncated columns of x_last itself (what the reference's residual leaves in its caller's input); the caller has
+    checked that no regressor is a truncated column."""
+    _dev(x_last, prog_cols, fields, reg_cols, trunc_map, lowpass, walias)
+    _sht_check(x_last, "ornstein_combine: x", torch.float32)
+    if _needs_grad(x_last, fields, lowpass, walias):
+        raise NotImplementedError("ornstein_combine: the backward kernel is not built; call it under torch.no_grad()")
+    n_grid, n_prog = x_last.shape[-2], prog_cols.shape[0]
+    R = 0 if reg_cols is None else reg_cols.shape[0]
+    if tuple(fields.shape) != (2 + R, n_grid, n_prog) or fields.dtype != torch.float32 or not fields.is_contiguous():
+        raise ValueError(f"ornstein_combine: fields must be contiguous fp32 [{2 + R}, {n_grid}, {n_prog}], got {tuple(fields.shape)}")
+    if x_last.shape[-1] > 1 and x_last.stride(-1) != 1:
+        raise ValueError("ornstein_combine: the last dimension of x must be contiguous")
+    xk = _two_leading(x_last)
+    if xk.shape[0] > 1 and xk.shape[1] > 1:
+        xk = xk.contiguous().view(1, -1, *xk.shape[2:])
+    G = xk.shape[0] * xk.shape[1]
+    gs = 0 if G <= 1 else (xk.stride(0) if xk.shape[0] > 1 else xk.stride(1))
+    ps = xk.stride(2) if n_grid > 1 else max(xk.shape[-1], 1)
+    n_trunc = 0
+    if trunc_map is not None:
+        if lowpass is None:
+            raise ValueError("ornstein_combine: trunc_map needs the low-pass fields")
+        n_trunc = lowpass.shape[-1]
+        if lowpass.numel() != G * n_grid * n_trunc or lowpass.dtype != torch.float32 or not lowpass.is_contiguous():
+            raise ValueError(f"ornstein_combine: lowpass must be contiguous fp32 [.., {n_grid}, T] over x's {G} leading entries, got {tuple(lowpass.shape)}")
+        if walias is not None and (tuple(walias.shape) != (n_grid, n_trunc) or walias.dtype != torch.float32 or not walias.is_contiguous()):
+            raise ValueError(f"ornstein_combine: walias must be contiguous fp32 [{n_grid}, {n_trunc}]")
+    elif lowpass is not None or walias is not None or write_back:
+        raise ValueError("ornstein_combine: lowpass / walias / write_back need a trunc_map")
+    if write_back and xk.data_ptr() != x_last.data_ptr():
+        raise ValueError("ornstein_combine: write_back needs an input whose leading dimensions are addressed in place")
+    out = torch.empty((*x_last.shape[:-2], n_grid, n_prog), dtype=torch.float32, device=x_last.device)
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    rc = _lib.load().anemoi_ornstein_combine_fwd(xk.data_ptr(), gs, ps, _vec(prog_cols, "prog_cols", n_prog, torch.int32), _vec(reg_cols, "reg_cols", R, torch.int32),
+                                                 R, fields.data_ptr(), _vec(trunc_map, "trunc_map", n_prog, torch.int32), ptr(lowpass), n_trunc, ptr(walias),
+                                                 xk.data_ptr() if write_back else 0, out.data_ptr(), G, n_grid, n_prog, _stream())
+    _lib.check(rc, "ornstein_combine_fwd")
+    return out

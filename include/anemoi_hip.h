@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ANEMOI_HIP_ABI_VERSION 24
+#define ANEMOI_HIP_ABI_VERSION 25
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -705,6 +705,68 @@ int anemoi_sparse_project_fwd(const void* x, int64_t ldx, int64_t bsx, int32_t b
                               const int32_t* indices, const float* w, const int32_t* cols, const float* mul, const float* add, void* y,
                               int64_t ldy, int64_t bsy, int32_t batch, int32_t n_dst, int32_t C, anemoi_dtype_t x_dtype, anemoi_dtype_t y_dtype,
                               void* stream);
+
+/* ---- spherical-harmonic transforms and the spectral Ornstein residual (ABI 25) ----------------------------------------------------
+ * A grid of K latitude rings, ring k holding n_k points at [s_k, s_k + n_k) of the flattened grid (ring_offsets: int32 [K + 1] = s_0 .. s_K,
+ * device); M = L = truncation + 1, 0 < truncation <= K.  Everything is fp32 with fp32 accumulation.  Constant tables of the caller (device):
+ *   twiddles  fp32 [grid, 2]: entry s_k + t = (cos, -sin)(2 pi t / n_k), built in float64 and rounded once;
+ *   wleg      fp32 [L, K, M]: the quadrature-weighted normalised associated Legendre functions W[m, l, k], stored m fastest;
+ *   pleg      fp32 [L, K, M]: the synthesis functions P[m, l, k], stored m fastest.
+ * The grid side of either direction is addressed in place: field f = g * n_cols + c (g < n_groups, c < n_cols) lives at
+ * base + g * gs + (cols ? cols[c] : c) + point * ps (elements): columns of a [G, grid, V] tensor (gs = grid V, ps = V) or the rows of a
+ * [F, grid] one (n_groups = F, n_cols = 1, gs = grid, ps = 1).  coeffs: [F, L, M] complex as interleaved (re, im) fp32.  workspace: the
+ * ring spectra, anemoi_sht_plan's workspace_bytes = F K M 8 bytes.  Each transform is two launches on `stream`; nothing is allocated or
+ * synchronised, so a call captures into a hipGraph.  Sums run in a fixed order without atomics: bitwise reproducible. */
+
+/* How a transform is tiled (csrc/sht_plan.h), asked without launching anything.  HOST-ONLY: no HIP call, no device needed, and
+ * lons_per_lat is a HOST array of n_rings ring lengths.  direction: 0 forward, 1 inverse.  ANEMOI_E_INVALID for a truncation outside
+ * [1, n_rings] or a ring without points (`out` is filled with zeros then).
+ * Replaces: nothing in the reference, which launches one torch.fft call per ring (layers/spectral_helpers.py:261-262, 472-475) and has
+ * no launch geometry of its own to ask about.
+ *   field_tile: fields per workgroup (1, 2, 4, 8);  chunk: points (forward) or modes (inverse) the ring kernel stages per pass;
+ *   lds_bytes: that kernel's dynamic LDS = field_tile chunk (4 | 8) <= lds_bound, whatever the ring length;  ring_grid: (rings, tiles of
+ *   ring_threads modes | points, field tiles);  leg_grid: (tiles of 64 modes, tiles of leg_rows degrees | rings, field tiles). */
+typedef struct {
+  int32_t field_tile, chunk, lds_bytes, lds_bound, ring_threads, leg_rows;
+  uint32_t ring_grid[3], leg_grid[3];
+  int64_t workspace_bytes;
+} anemoi_sht_plan_t;
+int anemoi_sht_plan(int32_t direction, int32_t n_fields, const int32_t* lons_per_lat, int32_t n_rings, int32_t truncation,
+                    anemoi_sht_plan_t* out);
+
+/* Forward transform, grid -> coefficients.
+ * Replaces: SphericalHarmonicTransform.forward (layers/spectral_helpers.py:317-340) with its per-ring rfft loop (:227-264) and the
+ * "(b t e v) p" transposing copy of its callers (layers/spectral_transforms.py:254-261, 360-369).
+ *   X[f, k, m] = (2 pi / n_k) sum_j x[f, s_k + j] exp(-2 pi i ((j m) mod n_k) / n_k) for m <= n_k / 2, 0 beyond (zero-filled, not aliased);
+ *   coeffs[f, l, m] = sum_k X[f, k, m] W[m, l, k]; zeros are written where l < m.
+ * max_ring = max n_k (the host does not read ring_offsets). */
+int anemoi_sht_fwd(const float* x, int64_t gs, int64_t ps, const int32_t* cols, int32_t n_groups, int32_t n_cols, const int32_t* ring_offsets,
+                   int32_t n_rings, int32_t max_ring, int32_t truncation, const float* twiddles, const float* wleg, float* coeffs,
+                   float* workspace, int64_t workspace_bytes, void* stream);
+
+/* Inverse transform, coefficients -> grid.
+ * Replaces: InverseSphericalHarmonicTransform.forward (layers/spectral_helpers.py:530-553) with its per-ring irfft loop (:448-477), and
+ * the per-degree filter multiply in front of it (layers/residual.py:549, 557).
+ *   Y[f, k, m] = sum_{l >= m} coeffs[f, l, m] lscale[f % n_scale, l] P[m, l, k]         (lscale: fp32 [n_scale, L] or NULL = 1)
+ *   y[f, s_k + j] = Re Y_0 + sum_{1 <= m < n_k / 2, m < M} 2 Re(Y_m exp(+2 pi i ((j m) mod n_k) / n_k)), plus Re(Y_{n_k / 2}) (-1)^j for
+ *   even n_k with n_k / 2 < M: irfft(., n_k, norm="forward").  Every point of every field of y is written. */
+int anemoi_sht_inv(const float* coeffs, const float* lscale, int32_t n_scale, const int32_t* ring_offsets, int32_t n_rings, int32_t max_ring,
+                   int32_t truncation, const float* twiddles, const float* pleg, float* y, int64_t gs, int64_t ps, const int32_t* cols,
+                   int32_t n_groups, int32_t n_cols, float* workspace, int64_t workspace_bytes, void* stream);
+
+/* The spectral Ornstein residual's row-wise step, one launch.
+ * Replaces: SpectralOrnsteinConnection._learnable and the blend of _truncate_with_anti_aliasing (layers/residual.py:546-576): two
+ * rearranges, an indexed in-place assignment, the gain / mu / regressor broadcasts and the zero-filled scatter of forward (:585-588).
+ *   out[g, p, c] = gain[p, c] xt + mu[p, c] + sum_i beta_i[p, c] x[g, p, reg_cols[i]],   x[g, p, v] at x + g gs + p ps + v
+ *   xt = x[g, p, prog_cols[c]] where trunc_map is NULL or trunc_map[c] < 0; otherwise, with t = trunc_map[c], xt = lowpass[g, p, t]
+ *   (walias NULL) or walias[p, t] x + (1 - walias[p, t]) lowpass[g, p, t].  x_filtered (NULL, or a tensor addressed like x; x itself is
+ *   allowed when no regressor is a truncated column): receives xt in the truncated columns, the side effect of the reference's
+ *   _apply_truncation on its caller's input (:560-563), which its model feeds to the encoder.
+ * fields: fp32 [2 + n_reg, n_grid, n_prog] = gain, mu, beta_0 ..; lowpass: [n_groups, n_grid, n_trunc]; walias: [n_grid, n_trunc];
+ * out: the compact skip [n_groups, n_grid, n_prog]; prog_cols [n_prog], reg_cols [n_reg], trunc_map [n_prog]: int32. */
+int anemoi_ornstein_combine_fwd(const float* x, int64_t gs, int64_t ps, const int32_t* prog_cols, const int32_t* reg_cols, int32_t n_reg,
+                                const float* fields, const int32_t* trunc_map, const float* lowpass, int32_t n_trunc, const float* walias,
+                                float* x_filtered, float* out, int32_t n_groups, int32_t n_grid, int32_t n_prog, void* stream);
 
 #ifdef __cplusplus
 }
