@@ -30,7 +30,7 @@ from ..distributed.partition import (
 from ..distributed.shapes import BipartiteGraphShardInfo, comm_rank, comm_size, get_shard_sizes, model_is_distributed
 from .block import GraphConvMapperBlock, GraphTransformerMapperBlock
 from .handoff import Carrier, SideJob, inference_in, plain_layer_norm
-from .kernels import PaddedLinear
+from .kernels import LayerNorm, PaddedLinear
 from .mlp import MLP
 from .utils import compute_mlp_hidden_dim, load_layer_kernels
 from ..utils.tensors import version
@@ -379,8 +379,12 @@ class GraphTransformerBackwardMapper(GraphTransformerBaseMapper):
 
     def __init__(self, *, out_channels_dst: Optional[int] = None, initialise_data_extractor_zero: bool = False, **kwargs) -> None:
         super().__init__(out_channels_dst=out_channels_dst, **kwargs)
-        self.node_data_extractor = nn.Sequential(self.layer_factory.LayerNorm(self.hidden_dim),
-                                                 self.layer_factory.Linear(self.hidden_dim, self.out_channels_dst))
+        norm = self.layer_factory.LayerNorm(self.hidden_dim)
+        if not isinstance(norm, nn.LayerNorm):
+            # the reference's extractor is a plain nn.LayerNorm whatever layer_kernels selects (layers/mapper.py:688-690): a conditional
+            # LayerNorm of the blocks (the transport model) does not reach it
+            norm = LayerNorm(self.hidden_dim)
+        self.node_data_extractor = nn.Sequential(norm, self.layer_factory.Linear(self.hidden_dim, self.out_channels_dst))
         if initialise_data_extractor_zero:
             for module in self.node_data_extractor.modules():
                 if isinstance(module, nn.Linear):

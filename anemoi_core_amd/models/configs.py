@@ -91,3 +91,27 @@ def ens_model_config(kind, num_channels, num_layers, num_heads, trainable, *, no
                                                          "condition_shape": noise_channels_dim, "zero_init": True, "autocast": False}}
     m["noise_injector"] = inj
     return cfg
+
+
+def transport_model_config(kind, num_channels, num_layers, num_heads, trainable, *, noise_embedder="SinusoidalEmbeddings", noise_channels=32,
+                           noise_cond_dim=16, objective="edm_diffusion", sigma_data=1.0, sigma_max=100.0, sigma_min=0.02, rho=7.0, source=None,
+                           inference_defaults=None, prefix="anemoi.models.layers", **embedder_kw):
+    """The nested config of the reference's AnemoiTransportModelEncProcDec (training/src/anemoi/training/config/model/
+    graphtransformer_transport_edm.yaml): ``model_config(kind, ...)`` whose encoder, processor and decoder take a ConditionalLayerNorm of
+    ``condition_shape = noise_cond_dim`` as ``layer_kernels.LayerNorm``, plus the ``model.model.transport`` section.  ``noise_embedder``:
+    "SinusoidalEmbeddings" (``max_period``) or "RandomFourierEmbeddings" (``scale``) of layers/diffusion.py; ``inference_defaults``:
+    {"sampling_schedule": {"schedule_type": ..., ...}, "sampler": {"sampler": ..., ...}}."""
+    cfg = model_config(kind, num_channels, num_layers, num_heads, trainable, prefix=prefix)
+    m = cfg["model"]
+    for part in ("encoder", "processor", "decoder"):
+        m[part]["layer_kernels"] = {"LayerNorm": {"_target_": f"{prefix}.normalization.ConditionalLayerNorm", "_partial_": True,
+                                                  "condition_shape": noise_cond_dim, "zero_init": True, "autocast": False}}
+    if inference_defaults is None:
+        inference_defaults = {"sampling_schedule": {"schedule_type": "karras", "sigma_max": sigma_max, "sigma_min": sigma_min, "rho": rho,
+                                                    "num_steps": 20},
+                              "sampler": {"sampler": "heun", "S_churn": 0.0, "S_min": 0.0, "S_max": float("inf"), "S_noise": 1.0}}
+    m["model"]["transport"] = {"objective": objective, "noise_channels": noise_channels, "noise_cond_dim": noise_cond_dim,
+                               "noise_embedder": dict({"_target_": f"{prefix}.diffusion.{noise_embedder}", "num_channels": noise_channels}, **embedder_kw),
+                               "sigma_data": sigma_data, "sigma_max": sigma_max, "sigma_min": sigma_min, "rho": rho, "source": dict(source or {}),
+                               "inference_defaults": inference_defaults}
+    return cfg

@@ -2132,3 +2132,141 @@ def ornstein_combine(x_last: Tensor, prog_cols: Tensor, fields: Tensor, reg_cols
                                                  xk.data_ptr() if write_back else 0, out.data_ptr(), G, n_grid, n_prog, _stream())
     _lib.check(rc, "ornstein_combine_fwd")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- EDM diffusion (csrc/transport.hip)
+NOISE_CHANNELS_MAX, NOISE_COND_MAX = 64, 32  # widths anemoi_noise_cond_fwd takes (csrc/transport.hip)
+HEUN_PREDICT, HEUN_CORRECT, HEUN_FINAL, DPMPP_FIRST, DPMPP_MULTI, DPMPP_FINAL = range(6)  # modes of edm_update_
+_REAL = {torch.float32: 0, torch.float64: 1}
+
+
+def _real(t: Tensor, what: str) -> int:
+    try:
+        return _REAL[t.dtype]
+    except KeyError:
+        raise ValueError(f"{what}: float32 or float64, got {t.dtype}") from None
+
+
+def _state5(t: Tensor, what: str) -> tuple:
+    """Element strides (batch, time, ensemble, grid) of a [B, T, E, N, V] tensor read in place; the last dimension is contiguous."""
+    if t.dim() != 5 or (t.shape[-1] > 1 and t.stride(-1) != 1):
+        raise ValueError(f"{what}: [batch, time, ensemble, grid, vars] with a contiguous last dimension, got {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0), t.stride(1), t.stride(2), t.stride(3)
+
+
+def noise_cond(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, *, pi: Optional[Tensor] = None,
+               log_quarter: bool = False, rows: tuple = (1,), out_dtype=None) -> tuple:
+    """The conditioning rows of one denoiser call, one launch (anemoi_noise_cond_fwd): values [G] (fp32 / fp64, cast to fp32), optionally
+    log(v) / 4 (the EDM c_noise), the sin | cos embedding over ``frequencies`` [C / 2] fp32 (times 2 pi[0] when ``pi`` is given), the
+    two Linear maps with SiLU between them, and the result [G, cond_dim] repeated ``rows[k]`` times per group into up to two outputs
+    [G rows[k], cond_dim] in ``out_dtype`` (default: the weights').  Returns one tensor per entry of ``rows`` (None for a 0 entry)."""
+    _dev(values, frequencies, w1, b1, w2, b2, pi)
+    if _needs_grad(values, w1, b1, w2, b2):
+        raise NotImplementedError("noise_cond: training the noise conditioning (a backward kernel) is not built; call it under torch.no_grad()")
+    C, cond_dim, G = w1.shape[0], w2.shape[0], values.numel()
+    if tuple(w1.shape) != (C, C) or tuple(w2.shape) != (cond_dim, C) or b1.numel() != C or b2.numel() != cond_dim or frequencies.numel() * 2 != C:
+        raise ValueError(f"noise_cond: w1 [C, C], b1 [C], w2 [cond, C], b2 [cond], frequencies [C / 2]; got {tuple(w1.shape)}, {tuple(b1.shape)}, "
+                         f"{tuple(w2.shape)}, {tuple(b2.shape)}, {tuple(frequencies.shape)}")
+    if frequencies.dtype != torch.float32 or (pi is not None and pi.dtype != torch.float32):
+        raise ValueError("noise_cond: frequencies and pi are fp32")
+    if not (w1.dtype == b1.dtype == w2.dtype == b2.dtype):
+        raise ValueError("noise_cond: the four parameters share one dtype")
+    if not 1 <= len(rows) <= 2:
+        raise ValueError("noise_cond: one or two destinations")
+    values, frequencies = values.reshape(-1).contiguous(), frequencies.contiguous()
+    w1, b1, w2, b2 = w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()
+    out_dtype = out_dtype or w1.dtype
+    outs = [None if r == 0 else torch.empty((G * r, cond_dim), dtype=out_dtype, device=values.device) for r in rows]
+    dst = [(0, 0, 0) if o is None else (o.data_ptr(), r, cond_dim) for o, r in zip(outs, rows)] + [(0, 0, 0)] * (2 - len(rows))
+    rc = _lib.load().anemoi_noise_cond_fwd(values.data_ptr(), _real(values, "noise_cond: values"), 1 if log_quarter else 0, frequencies.data_ptr(),
+                                           0 if pi is None else pi.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), _dt(w1),
+                                           *dst[0], *dst[1], G, C, cond_dim, _DT[out_dtype], _stream())
+    _lib.check(rc, "noise_cond_fwd")
+    return tuple(outs)
+
+
+def transport_assemble_input(x: Tensor, y: Tensor, attrs: Optional[Tensor], width: int, *, sigma: Optional[Tensor] = None, sigma_data: float = 1.0,
+                             out_dtype=None, out: Optional[Tensor] = None) -> Tensor:
+    """The denoiser network's input rows, one launch (anemoi_transport_assemble_input):
+    out[(b e n), :] = [x[b, t, e, n, :] | c_in[b, e] float(y[b, t, e, n, :]) | attrs[n, :] | zeros up to ``width``], c_in = 1 / sqrt(sigma_data^2
+    + sigma^2) in fp32 from the device ``sigma`` [B E] (None: no scale).  x fp32 and y fp32 / fp64 are read in place through their strides.
+    ``out``: a [B E N, >= width] row-major tensor to write into (its columns beyond ``width`` stay untouched)."""
+    _dev(x, y, attrs, sigma, out)
+    if _needs_grad(x, y, attrs, sigma):
+        raise NotImplementedError("transport_assemble_input: training (a backward kernel) is not built; call it under torch.no_grad()")
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"transport_assemble_input: the data dtype is float32, got {x.dtype}")
+    xs, ys = _state5(x, "transport_assemble_input: x"), _state5(y, "transport_assemble_input: y")
+    B, T_in, E, N, V_in = x.shape
+    T_out, V_out = y.shape[1], y.shape[4]
+    if (y.shape[0], y.shape[2], y.shape[3]) != (B, E, N):
+        raise ValueError(f"transport_assemble_input: x {tuple(x.shape)} and y {tuple(y.shape)} differ in batch, ensemble or grid")
+    A = 0 if attrs is None else attrs.shape[1]
+    if attrs is not None and (attrs.dim() != 2 or attrs.shape[0] != N or attrs.stride(1) != 1):
+        raise ValueError(f"transport_assemble_input: attrs [{N}, A] row-major, got {tuple(attrs.shape)}")
+    if sigma is not None and sigma.numel() != B * E:
+        raise ValueError(f"transport_assemble_input: sigma has {sigma.numel()} values for {B * E} groups")
+    if out is None:
+        out = torch.empty((B * E * N, width), dtype=out_dtype or (attrs.dtype if attrs is not None else x.dtype), device=x.device)
+    elif out.dim() != 2 or out.shape[0] != B * E * N or out.shape[1] < width or out.stride(1) != 1:
+        raise ValueError(f"transport_assemble_input: out [{B * E * N}, >= {width}] row-major, got {tuple(out.shape)}")
+    if attrs is not None and attrs.dtype != out.dtype:
+        raise ValueError(f"transport_assemble_input: attrs {attrs.dtype} and out {out.dtype} are both the model dtype")
+    sig = None if sigma is None else sigma.reshape(-1).contiguous()
+    rc = _lib.load().anemoi_transport_assemble_input(x.data_ptr(), *xs, y.data_ptr(), _real(y, "transport_assemble_input: y"), *ys,
+                                                     0 if sig is None else sig.data_ptr(), 0 if sig is None else _real(sig, "transport_assemble_input: sigma"),
+                                                     float(sigma_data), 0 if sig is None else 1, 0 if attrs is None else attrs.data_ptr(),
+                                                     0 if attrs is None else attrs.stride(0), A, out.data_ptr(), out.stride(0), width, B, E, N, T_in, V_in,
+                                                     T_out, V_out, _dt(out), _stream())
+    _lib.check(rc, "transport_assemble_input")
+    return out
+
+
+def edm_output(pred: Tensor, y: Optional[Tensor], sigma: Optional[Tensor], shape: tuple, *, sigma_data: float = 1.0, out_dtype=torch.float32,
+               out: Optional[Tensor] = None) -> Tensor:
+    """The denoised state from the network's output rows, one launch (anemoi_edm_output): with ``shape`` = (B, T_out, E, N, V_out),
+    out[b, t, e, n, v] = c_skip float(y[b, t, e, n, v]) + c_out pred[(b e n), t V_out + v] with the fp32 EDM coefficients of the device
+    ``sigma`` [B E]; y and sigma None: "(batch ensemble grid) (time vars) -> batch time ensemble grid vars" and the cast alone.  The result
+    is float32 or float64 (``out_dtype``, or the contiguous ``out``)."""
+    _dev(pred, y, sigma, out)
+    if _needs_grad(pred, y, sigma):
+        raise NotImplementedError("edm_output: training (a backward kernel) is not built; call it under torch.no_grad()")
+    B, T_out, E, N, V_out = shape
+    if pred.dim() != 2 or pred.shape[0] != B * E * N or pred.shape[1] < T_out * V_out or pred.stride(1) != 1:
+        raise ValueError(f"edm_output: pred [{B * E * N}, >= {T_out * V_out}] row-major, got {tuple(pred.shape)}")
+    if (y is None) != (sigma is None):
+        raise ValueError("edm_output: y and sigma go together")
+    ys = (0, 0, 0, 0)
+    if y is not None:
+        if tuple(y.shape) != tuple(shape) or sigma.numel() != B * E:
+            raise ValueError(f"edm_output: y {tuple(y.shape)} against {tuple(shape)}, sigma {sigma.numel()} values for {B * E} groups")
+        ys = _state5(y, "edm_output: y")
+        sigma = sigma.reshape(-1).contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=pred.device)
+    elif tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"edm_output: out is contiguous {tuple(shape)}, got {tuple(out.shape)}")
+    rc = _lib.load().anemoi_edm_output(pred.data_ptr(), pred.stride(0), _dt(pred), 0 if y is None else y.data_ptr(), 0 if y is None else _real(y, "edm_output: y"),
+                                       *ys, 0 if sigma is None else sigma.data_ptr(), 0 if sigma is None else _real(sigma, "edm_output: sigma"),
+                                       float(sigma_data), 0 if y is None else 1, out.data_ptr(), _real(out, "edm_output: out"), B, E, N, T_out, V_out,
+                                       _stream())
+    _lib.check(rc, "edm_output")
+    return out
+
+
+def edm_update_(mode: int, params: Tensor, y: Tensor, D: Tensor, aux1: Optional[Tensor] = None, aux2: Optional[Tensor] = None) -> Tensor:
+    """The solver arithmetic of one sampler step, in place, one launch (anemoi_edm_update; the modes and the layout of the 8 fp64 device
+    ``params`` are those of include/anemoi_hip.h).  y, D, aux1 (d1 | D_old), aux2 (y_next): contiguous tensors of one shape in the solver
+    dtype (float32 / float64).  Returns y."""
+    _dev(params, y, D, aux1, aux2)
+    if params.dtype != torch.float64 or params.numel() != 8 or not params.is_contiguous():
+        raise ValueError("edm_update_: params is 8 contiguous float64 values on the device")
+    for name, t in (("y", y), ("D", D), ("aux1", aux1), ("aux2", aux2)):
+        if t is not None and (t.dtype != y.dtype or t.shape != y.shape or not t.is_contiguous()):
+            raise ValueError(f"edm_update_: {name} is a contiguous {y.dtype} tensor of shape {tuple(y.shape)}, got {t.dtype} {tuple(t.shape)}")
+    if _needs_grad(y, D, aux1, aux2):
+        raise NotImplementedError("edm_update_: differentiating through the sampler is not built; call it under torch.no_grad()")
+    rc = _lib.load().anemoi_edm_update(int(mode), params.data_ptr(), y.data_ptr(), D.data_ptr(), 0 if aux1 is None else aux1.data_ptr(),
+                                       0 if aux2 is None else aux2.data_ptr(), y.numel(), _real(y, "edm_update_: y"), _stream())
+    _lib.check(rc, "edm_update")
+    return y

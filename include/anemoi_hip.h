@@ -29,6 +29,8 @@
 extern "C" {
 #endif
 
+/* (The EDM diffusion entries - anemoi_noise_cond_fwd, anemoi_transport_assemble_input, anemoi_edm_output, anemoi_edm_update - were added at
+ * 25 without a bump: they only add entry points, every earlier signature keeps its meaning.) */
 #define ANEMOI_HIP_ABI_VERSION 25
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
@@ -767,6 +769,64 @@ int anemoi_sht_inv(const float* coeffs, const float* lscale, int32_t n_scale, co
 int anemoi_ornstein_combine_fwd(const float* x, int64_t gs, int64_t ps, const int32_t* prog_cols, const int32_t* reg_cols, int32_t n_reg,
                                 const float* fields, const int32_t* trunc_map, const float* lowpass, int32_t n_trunc, const float* walias,
                                 float* x_filtered, float* out, int32_t n_groups, int32_t n_grid, int32_t n_prog, void* stream);
+
+/* ---- The EDM diffusion model's edges and solver step (csrc/transport.hip).  anemoi_dtype_t has no float64: a tensor that may be held in
+ * the solver's precision carries its own flag `*_f64` (0 = fp32, 1 = fp64).  Every per-call scalar - sigma, the solver's coefficients - is
+ * read from DEVICE memory, so a captured launch replays for every step of a sampler.  G = batch x ensemble groups, rows ordered
+ * "(batch ensemble grid)"; x, y: [B, T, E, N, V] addressed by element strides with a contiguous last dimension. ---- */
+
+/* The conditioning rows of one denoiser call.
+ * Replaces: AnemoiTransportModelEncProcDec._embed_noise_conditioning, _make_noise_emb (twice) and _generate_noise_conditioning
+ * (models/transport_encoder_processor_decoder.py:138-151, 171-201), the embedders (layers/diffusion.py:23-25, 36-38), the c_noise of
+ * EDMDiffusionModelObjective._get_preconditioning (transport/objectives.py:212) and the cast of _expand_scalar_condition
+ * (samplers/transport_samplers.py:34-39).
+ *   v = float(values[g]);  transform 1: v = log(v) / 4;  arg_j = v frequencies[j], with pi != NULL ((v f_j) 2) pi[0], every product rounded
+ *   to fp32;  emb = [sin(arg) | cos(arg)] (C values);  cond = W2 silu(W1 emb + b1) + b2, fp32 accumulation;
+ *   out_k[(g rows_k + r), 0:cond_dim] = cond for r < rows_k, k = 0, 1 (a NULL destination is skipped; rows_k = 1 yields cond itself).
+ * w1 [C, C], b1 [C], w2 [cond_dim, C], b2 [cond_dim] in w_dtype; outputs in dtype; C even, <= 64; cond_dim <= 32 (ANEMOI_E_UNSUPPORTED
+ * beyond). */
+int anemoi_noise_cond_fwd(const void* values, int32_t values_f64, int32_t transform, const float* frequencies, const float* pi, const void* w1,
+                          const void* b1, const void* w2, const void* b2, anemoi_dtype_t w_dtype, void* out0, int64_t rows0, int64_t ld0,
+                          void* out1, int64_t rows1, int64_t ld1, int32_t G, int32_t C, int32_t cond_dim, anemoi_dtype_t dtype, void* stream);
+
+/* The denoiser network's input rows.
+ * Replaces: AnemoiTransportModelEncProcDec._assemble_input (models/transport_encoder_processor_decoder.py:99-125), the c_in y_noised of
+ * EDMDiffusionModelObjective.forward (transport/objectives.py:118, 211), the cast of the sampler's y_model
+ * (samplers/transport_samplers.py:159) and the zero padding of the embedding GEMM's K dimension.
+ *   out[(g, n), :] = [ x[g, t, n, :] t < T_in | c_in[g] float(y[g, t, n, :]) t < T_out | attrs[n, :] | zeros up to W ]
+ *   c_in[g] = 1 / sqrt(sigma_data^2 + sigma[g]^2) in fp32 (scale = 0: 1, sigma is not read).
+ * x: fp32; y: fp32 or fp64; sigma [G]: fp32 or fp64, cast to fp32 first; attrs [N, A] and out [G N, W] (ldo >= W) in dtype. */
+int anemoi_transport_assemble_input(const float* x, int64_t xs_b, int64_t xs_t, int64_t xs_e, int64_t xs_n, const void* y, int32_t y_f64,
+                                    int64_t ys_b, int64_t ys_t, int64_t ys_e, int64_t ys_n, const void* sigma, int32_t sigma_f64,
+                                    double sigma_data, int32_t scale, const void* attrs, int64_t lda, int32_t A, void* out, int64_t ldo,
+                                    int32_t W, int32_t B, int32_t E, int32_t N, int32_t T_in, int32_t V_in, int32_t T_out, int32_t V_out,
+                                    anemoi_dtype_t dtype, void* stream);
+
+/* The denoised state from the network's output rows.
+ * Replaces: AnemoiTransportModelEncProcDec._assemble_output (models/transport_encoder_processor_decoder.py:127-136), the
+ * c_skip y_noised + c_out pred of EDMDiffusionModelObjective.forward (transport/objectives.py:124, 209-210) and the cast of the
+ * sampler's D1_solver (samplers/transport_samplers.py:170, 197, 254).
+ *   out[b, t, e, n, v] = c_skip[g] float(y[b, t, e, n, v]) + c_out[g] pred[(g, n), t V_out + v],  g = b E + e,
+ *   c_skip = sd^2 / (sigma^2 + sd^2), c_out = sigma sd / sqrt(sigma^2 + sd^2), all in fp32 (precondition = 0: the rearrange and cast alone).
+ * pred in pred_dtype (ldp >= T_out V_out); out: contiguous [B, T_out, E, N, V_out], fp32 or fp64. */
+int anemoi_edm_output(const void* pred, int64_t ldp, anemoi_dtype_t pred_dtype, const void* y, int32_t y_f64, int64_t ys_b, int64_t ys_t,
+                      int64_t ys_e, int64_t ys_n, const void* sigma, int32_t sigma_f64, double sigma_data, int32_t precondition, void* out,
+                      int32_t out_f64, int32_t B, int32_t E, int32_t N, int32_t T_out, int32_t V_out, void* stream);
+
+/* The solver arithmetic of one sampler step, element-wise over n values in the solver's precision.
+ * Replaces: EDMHeunSampler.sample's update (samplers/transport_samplers.py:170-210) and DPMpp2MSampler.sample's
+ * (samplers/transport_samplers.py:254-283).
+ * params: 8 fp64 values on the device, rounded to the solver's precision first:
+ *   [0] sigma_eff  [1] sigma_next  [2] eps  [3] sigma_next / sigma  [4] exp(-h) - 1  [5] c1  [6] c2  [7] round32 (modes 3, 4).
+ *   mode 0 HEUN_PREDICT: d1 = (y - D) / (sigma_eff + eps); aux1 = d1; aux2 = y + (sigma_next - sigma_eff) d1
+ *   mode 1 HEUN_CORRECT: d2 = (aux2 - D) / (sigma_next + eps); y += (sigma_next - sigma_eff) (aux1 + d2) / 2
+ *   mode 2 HEUN_FINAL:   y = the predictor's y_next (computed from y and D; aux1, aux2 unused)
+ *   mode 3 DPMPP_FIRST:  y = [3] y - [4] D; aux1 = D                 (aux1 is not read)
+ *   mode 4 DPMPP_MULTI:  y = [3] y - [4] ([5] D + [6] aux1); aux1 = D
+ *                        (both: with [7] != 0 the new y is rounded to fp32 first, the data dtype the reference keeps it in, :283)
+ *   mode 5 DPMPP_FINAL:  y = D */
+int anemoi_edm_update(int32_t mode, const double* params, void* y, const void* D, void* aux1, void* aux2, int64_t n, int32_t solver_f64,
+                      void* stream);
 
 #ifdef __cplusplus
 }
