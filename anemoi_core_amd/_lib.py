@@ -38,6 +38,18 @@ class ShtPlan(C.Structure):
                [("ring_grid", C.c_uint32 * 3), ("leg_grid", C.c_uint32 * 3), ("workspace_bytes", _i64)]
 
 
+class ChainProblem(C.Structure):
+    """anemoi_chain_problem_t: the shape a chain entry point is asked about (csrc/chain_plan.h), field for field."""
+    _fields_ = [(name, _i32) for name in ("kind", "n_rows", "in_features", "hidden", "q_out_features", "rows_per_tile", "dtype", "timeline", "first_panel",
+                                          "panels", "side_rows", "side_in_features", "side_q_out_features", "side_rows_per_tile", "side_cap")]
+
+
+class ChainPlan(C.Structure):
+    """anemoi_chain_plan_t: the plan of one chain launch (csrc/chain_plan.h), field for field."""
+    _fields_ = [(name, _i32) for name in ("kernel", "rows_per_panel", "panels", "grid", "threads", "lds_bytes", "rounds", "idle_cus", "host_grid", "riders",
+                                          "first", "end", "side_pipelined", "job_panels", "pipelined", "n_rows")] + [("row_begin", _i64)]
+
+
 # name -> argtypes, exactly as in include/anemoi_hip.h
 SIGNATURES = {
     "anemoi_hip_abi_version": ([], C.c_int),
@@ -100,6 +112,7 @@ SIGNATURES = {
     "anemoi_peer_open": ([_p, C.POINTER(_p)], C.c_int),
     "anemoi_peer_close": ([_p], C.c_int),
     "anemoi_gt_chain_rows_per_tile": ([_i32], C.c_int),
+    "anemoi_chain_plan": ([C.POINTER(ChainProblem), C.POINTER(ChainPlan)], C.c_int),
     "anemoi_gt_chain2_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_rowchain_fwd": ([_p, C.c_int, _p], C.c_int),
     "anemoi_gt_rowchain_panels_fwd": ([_p, C.c_int32, C.c_int32, C.c_int, _p], C.c_int),

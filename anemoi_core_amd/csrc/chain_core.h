@@ -5,7 +5,7 @@
 // experiments/gt_chain.hip for the measurements behind each choice).  Here: the 64-column GEMM segment, the panel layout, the lanes'
 // coordinates in it, the LayerNorm statistics and the epilogue forms of both wave layouts.
 #pragma once
-#include "common.h"
+#include "chain_host.h"
 
 namespace anemoi {
 
@@ -72,15 +72,9 @@ __device__ __forceinline__ void load_cols(const T* __restrict__ p, int wave, int
   for (int ni = 0; ni < 4; ++ni) o[ni] = *reinterpret_cast<const u32x2*>(p + wave * 64 + ni * 16 + g * 4);
 }
 
-constexpr int kCh = 512;                    // channels of the residual stream (8 waves x 64 columns)
-constexpr int kPanel = 48;                  // panel rows (3 MFMA row bands)
-constexpr int kRowBytes = kCh * 2;          // one 16-bit row in LDS
-constexpr int kBufBytes = kPanel * kRowBytes;
+// kCh, kPanel and the LDS map of every kernel of the family (three panel buffers | [48 rows][waves][2] fp32 LayerNorm partials | the per-column
+// vectors: kRowBytes, kBufBytes, kRedOff, vec_off, kChainSmem) are chain_plan.h's: the launch plan prices the same layout
 constexpr int kSlab = 16 * 4096;            // one segment of a wave's weight stream: 16 K-steps x (4 fragments x 1 KiB)
-// LDS map of every kernel of the family: three panel buffers | [48 rows][waves][2] fp32 LayerNorm partials | the per-column vectors
-constexpr int kRedOff = 3 * kBufBytes;
-constexpr int vec_off(int waves) { return kRedOff + kPanel * waves * 2 * 4; }
-constexpr int kChainSmem = vec_off(8);      // (no vectors in LDS: the GraphConv chains keep theirs in registers)
 constexpr int kTlOff = kChainSmem;          // instrumented instantiation only: [8 waves][kTlSlots] stamps, copied out at the end
 
 // a pointer the compiler must keep in scalar registers (it is wave-uniform by construction): the loads then take the

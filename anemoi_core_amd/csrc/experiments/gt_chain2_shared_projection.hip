@@ -67,9 +67,7 @@ struct Chain2Args {
 constexpr int kTl2Slots = 48;
 constexpr int kRed2Off = kRedOff;                        // [48 rows][8 waves][2] fp32 LayerNorm partials (x1: eight 64-column waves; x2: four 128-column waves, [48][4][2] in the first 1 536 bytes)
 constexpr int kVecOff = vec_off(8);                       // the per-column vectors (16-bit)
-constexpr int kVecMaxElems = 6144;                        // 12 KiB: 512 + hidden + 512 + q_out <= 6144 (hidden = q_out = 2048: 5120)
-constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;
-constexpr int kVecMaxElemsTl = 5120;                      // the instrumented instantiation gives 2 KiB of the vector region to its stamps
+constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;   // (kVecMaxElems, kVecMaxElemsTl: chain_plan.h)
 constexpr int kTl2Off = kVecOff + kVecMaxElemsTl * 2;
 static_assert(kChain2Smem <= 160 * 1024 && kTl2Off + 8 * kTl2Slots * 8 <= 160 * 1024, "LDS budget");
 

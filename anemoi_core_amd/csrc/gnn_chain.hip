@@ -30,6 +30,7 @@ constexpr int kETlSlots = 48;  // entry + 8 stamps per panel of a workgroup's fi
 constexpr int kENB = 4, kERows = 16 * kENB, kEBuf = kERows * kRowBytes;
 constexpr int kERedOff = 2 * kEBuf;
 constexpr int kEdgeSmem = kERedOff + kERows * 8 * 2 * 4;
+static_assert(kERows == kGnnEdgeRows && kEdgeSmem == kGnnEdgeLds, "chain_plan.h prices this layout");
 
 // MLP = true: the same chain without the gathered rows, the residual optional and the first GEMM's K a multiple of 128 up to 512 -
 // the embedding MLPs of the GNN mappers / processor (reference layers/mlp.py:29-100 as built at layers/mapper.py:640-700:
@@ -577,12 +578,14 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
   }
 }
 
-static int chain_rows_per_tile(int n_rows, int cap = kPanel) {  // mirrored by tests/chain_refs.py panel_split: change both together
-  static const int forced = env_int(getenv("ANEMOI_CHAIN_ROWS"), 0, 0, 64);
-  if (forced > 0) return forced < cap ? forced : cap;
-  const int64_t rounds = ((int64_t)n_rows + 256 * cap - 1) / (256 * cap);
-  const int64_t r = ((int64_t)n_rows + 256 * rounds - 1) / (256 * rounds);
-  return (int)(r < 1 ? 1 : (r > cap ? cap : r));
+// The shape's plan (rows per panel: gnn_rows_per_tile of chain_plan.h) behind the checks every entry point of this file starts with
+static int gnn_plan(const char* who, ChainKind kind, int32_t n_rows, int32_t in_features, int32_t channels, anemoi_dtype_t dtype, ChainPlan& plan) {
+  ANEMOI_REQUIRE(channels == kCh, "%s: channels=%d (this kernel is built for %d)", who, channels, kCh);
+  ChainProblem q;
+  q.kind = kind;
+  q.n_rows = n_rows, q.in_features = in_features, q.dtype = dtype;
+  plan = plan_chain(q, chain_switches());
+  return chain_refused(who, q, plan);
 }
 
 }  // namespace anemoi
@@ -595,16 +598,16 @@ extern "C" int anemoi_gnn_edge_chain_fwd(const void* e, int64_t ld_e, const void
                                          int64_t ld_g2, const int32_t* idx2, const void* w0, const void* b0, const void* w1, const void* b1,
                                          const void* w2, const void* b2, const void* ln_w, const void* ln_b, float eps, void* e_new,
                                          int64_t ld_o, int32_t n_rows, int32_t channels, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gnn_edge_chain_fwd: 16-bit model dtypes only");
-  ANEMOI_REQUIRE(n_rows >= 0 && channels == kCh, "gnn_edge_chain_fwd: channels=%d (this kernel is built for %d)", channels, kCh);
-  if (n_rows == 0) return ANEMOI_OK;
+  ChainPlan plan;
+  const int rc = gnn_plan("gnn_edge_chain_fwd", ChainKind::GnnEdge, n_rows, 0, channels, dtype, plan);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
   ANEMOI_REQUIRE(e && g1 && idx1 && g2 && idx2 && w0 && b0 && w1 && b1 && w2 && b2 && ln_w && e_new, "gnn_edge_chain_fwd: null operand");
   ANEMOI_REQUIRE(al(e, 16) && al(e_new, 16) && al(w0, 16) && al(w1, 16) && al(w2, 16) && al(g1, 8) && al(g2, 8) && al(b0, 8) && al(b1, 8) && al(b2, 8) &&
                      al(ln_w, 8) && al(ln_b, 8) && ld_e % 8 == 0 && ld_o % 8 == 0 && ld_g1 % 4 == 0 && ld_g2 % 4 == 0 && ld_e >= kCh && ld_o >= kCh &&
                      ld_g1 >= kCh && ld_g2 >= kCh,
                  "gnn_edge_chain_fwd: operand alignment / leading dimensions");
   EdgeChainArgs a{e, ld_e, g1, ld_g1, idx1, g2, ld_g2, idx2, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, e_new, ld_o,
-                  n_rows, chain_rows_per_tile(n_rows, kERows), 0, 0};
+                  n_rows, plan.rows_per_panel, plan.panels, 0};
   // round 5: ANEMOI_GNN_CHAIN_V2=1 selects the two-group launch (gnn_chain2.hip): built, parity-green, and slower than the symmetric
   // kernel below (212 against 195 us at 81 840 rows: its 40 / 48-row panels need 7-8 passes over the weights instead of 5,
   // profiles/r05_gnn_edge_chain_role_split.txt) - kept for the A/B
@@ -614,18 +617,9 @@ extern "C" int anemoi_gnn_edge_chain_fwd(const void* e, int64_t ld_e, const void
 #endif
   static const int dbg = ANEMOI_EXPERIMENT_ENV("ANEMOI_EDGE_CHAIN_DBG", 0, 0, 31);
   a.dbg = dbg;
-  a.n_tiles = (n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
-  const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
   hipStream_t st = as_stream(stream);
-  if (dtype == ANEMOI_BF16) {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_edge_chain_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeSmem); });
-    hipLaunchKernelGGL((gnn_edge_chain_kernel<bf16_t>), dim3(grid), dim3(512), kEdgeSmem, st, a);
-  } else {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_edge_chain_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeSmem); });
-    hipLaunchKernelGGL((gnn_edge_chain_kernel<f16_t>), dim3(grid), dim3(512), kEdgeSmem, st, a);
-  }
+  if (dtype == ANEMOI_BF16) ANEMOI_CHAIN_LAUNCH((gnn_edge_chain_kernel<bf16_t>), kEdgeSmem, plan, st, a);
+  else ANEMOI_CHAIN_LAUNCH((gnn_edge_chain_kernel<f16_t>), kEdgeSmem, plan, st, a);
   return check_launch("gnn_edge_chain_kernel");
 }
 
@@ -642,17 +636,16 @@ extern "C" int anemoi_gnn_edge_chain_timeline(const void* e, int64_t ld_e, const
                      al(ln_w, 8) && al(ln_b, 8) && ld_e % 8 == 0 && ld_o % 8 == 0 && ld_g1 % 4 == 0 && ld_g2 % 4 == 0 && ld_e >= kCh && ld_o >= kCh &&
                      ld_g1 >= kCh && ld_g2 >= kCh,
                  "gnn_edge_chain_timeline: operand alignment / leading dimensions");
+  ChainPlan plan;
+  const int rc = gnn_plan("gnn_edge_chain_timeline", ChainKind::GnnEdge, n_rows, 0, kCh, ANEMOI_BF16, plan);
+  if (rc != ANEMOI_OK) return rc;
   EdgeChainArgs a{e, ld_e, g1, ld_g1, idx1, g2, ld_g2, idx2, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, e_new, ld_o,
-                  n_rows, chain_rows_per_tile(n_rows, kERows), 0, 0};
+                  n_rows, plan.rows_per_panel, plan.panels, 0};
   a.timeline = timeline;
   static const int dbg = ANEMOI_EXPERIMENT_ENV("ANEMOI_EDGE_CHAIN_DBG", 0, 0, 31);
   a.dbg = dbg;
-  a.n_tiles = (n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
-  const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
-  constexpr int smem = kEdgeSmem + 8 * kETlSlots * 8;
-  static PerDeviceOnce once;
-  once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_edge_chain_kernel<bf16_t, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, smem); });
-  hipLaunchKernelGGL((gnn_edge_chain_kernel<bf16_t, false, true>), dim3(grid), dim3(512), smem, as_stream(stream), a);
+  plan.lds_bytes = kEdgeSmem + 8 * kETlSlots * 8;  // (the instrumented instantiation's stamps behind the product's LDS)
+  ANEMOI_CHAIN_LAUNCH((gnn_edge_chain_kernel<bf16_t, false, true>), plan.lds_bytes, plan, as_stream(stream), a);
   return check_launch("gnn_edge_chain_kernel<timeline>");
 }
 #endif
@@ -660,16 +653,15 @@ extern "C" int anemoi_gnn_edge_chain_timeline(const void* e, int64_t ld_e, const
 extern "C" int anemoi_gnn_mlp_chain_fwd(const void* x, int64_t ld_x, int32_t in_features, const void* w0, const void* b0, const void* w1, const void* b1,
                                         const void* w2, const void* b2, const void* ln_w, const void* ln_b, float eps, const void* res, int64_t ld_res,
                                         void* out, int64_t ld_o, int32_t n_rows, int32_t channels, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gnn_mlp_chain_fwd: 16-bit model dtypes only");
-  ANEMOI_REQUIRE(n_rows >= 0 && channels == kCh, "gnn_mlp_chain_fwd: channels=%d (this kernel is built for %d)", channels, kCh);
-  ANEMOI_REQUIRE(in_features >= 128 && in_features <= kCh && in_features % 128 == 0, "gnn_mlp_chain_fwd: in_features=%d (zero-padded width: 128, 256, 384 or 512)", in_features);
-  if (n_rows == 0) return ANEMOI_OK;
+  ChainPlan plan;
+  const int rc = gnn_plan("gnn_mlp_chain_fwd", ChainKind::GnnMlp, n_rows, in_features, channels, dtype, plan);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
   ANEMOI_REQUIRE(x && w0 && b0 && w1 && b1 && w2 && b2 && ln_w && out, "gnn_mlp_chain_fwd: null operand");
   ANEMOI_REQUIRE(al(x, 16) && al(out, 16) && al(w0, 16) && al(w1, 16) && al(w2, 16) && al(res, 8) && al(b0, 8) && al(b1, 8) && al(b2, 8) && al(ln_w, 8) &&
                      al(ln_b, 8) && ld_x % 8 == 0 && ld_o % 8 == 0 && ld_x >= in_features && ld_o >= kCh && (!res || (ld_res % 4 == 0 && ld_res >= kCh)),
                  "gnn_mlp_chain_fwd: operand alignment / leading dimensions");
   EdgeChainArgs a{x, ld_x, nullptr, 0, nullptr, nullptr, 0, nullptr, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, out, ld_o,
-                  n_rows, chain_rows_per_tile(n_rows, kERows), 0, 0};
+                  n_rows, plan.rows_per_panel, plan.panels, 0};
   a.res = res;
   a.ld_res = ld_res;
   a.k0_groups = in_features / 128;
@@ -677,18 +669,9 @@ extern "C" int anemoi_gnn_mlp_chain_fwd(const void* x, int64_t ld_x, int32_t in_
   static const int v2 = env_int(getenv("ANEMOI_GNN_CHAIN_V2"), 0, 0, 1);
   if (v2) return launch_edge_chain2(a, dtype, stream, true);
 #endif
-  a.n_tiles = (n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
-  const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
   hipStream_t st = as_stream(stream);
-  if (dtype == ANEMOI_BF16) {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_edge_chain_kernel<bf16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeSmem); });
-    hipLaunchKernelGGL((gnn_edge_chain_kernel<bf16_t, true>), dim3(grid), dim3(512), kEdgeSmem, st, a);
-  } else {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_edge_chain_kernel<f16_t, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kEdgeSmem); });
-    hipLaunchKernelGGL((gnn_edge_chain_kernel<f16_t, true>), dim3(grid), dim3(512), kEdgeSmem, st, a);
-  }
+  if (dtype == ANEMOI_BF16) ANEMOI_CHAIN_LAUNCH((gnn_edge_chain_kernel<bf16_t, true>), kEdgeSmem, plan, st, a);
+  else ANEMOI_CHAIN_LAUNCH((gnn_edge_chain_kernel<f16_t, true>), kEdgeSmem, plan, st, a);
   return check_launch("gnn_mlp_chain_kernel");
 }
 
@@ -696,9 +679,9 @@ static int node_chain_launch(const void* x, int64_t ld_x, const void* agg, int64
                              const void* bb, const void* wc, const void* bc, const void* ln_w, const void* ln_b, float eps, void* x_out,
                              int64_t ld_o, const void* wt, const void* bt, int32_t t_out_features, void* t_out, int64_t ld_t,
                              int32_t n_rows, int32_t channels, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gnn_node_chain_fwd: 16-bit model dtypes only");
-  ANEMOI_REQUIRE(n_rows >= 0 && channels == kCh, "gnn_node_chain_fwd: channels=%d (this kernel is built for %d)", channels, kCh);
-  if (n_rows == 0) return ANEMOI_OK;
+  ChainPlan plan;
+  const int rc = gnn_plan("gnn_node_chain_fwd", ChainKind::GnnNode, n_rows, 0, channels, dtype, plan);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
   // (agg may be NULL when the segment pointer says every destination has no in-edge at all: an empty edge table has no rows to point at)
   ANEMOI_REQUIRE(x && (agg || seg_ptr) && wa && ba && wb && bb && wc && bc && ln_w && x_out, "gnn_node_chain_fwd: null operand");
   ANEMOI_REQUIRE(t_out_features >= 0 && t_out_features % kCh == 0 && (t_out_features == 0 || (wt && t_out && ld_t >= t_out_features && ld_t % 8 == 0 && al(t_out, 16) && al(wt, 16))),
@@ -707,24 +690,11 @@ static int node_chain_launch(const void* x, int64_t ld_x, const void* agg, int64
                      al(ln_w, 8) && al(ln_b, 8) && ld_x % 8 == 0 && ld_a % 8 == 0 && ld_o % 8 == 0 && ld_x >= kCh && ld_a >= kCh && ld_o >= kCh,
                  "gnn_node_chain_fwd: operand alignment / leading dimensions");
   NodeChainArgs a{x, ld_x, agg, ld_a, (const char*)wa, ba, (const char*)wb, bb, (const char*)wc, bc, ln_w, ln_b, eps, x_out, ld_o,
-                  (const char*)wt, bt, t_out_features / kCh, t_out, ld_t, n_rows, chain_rows_per_tile(n_rows), 0};
-  // ANEMOI_GNN_NODE_ROWS: rows per panel of this launch alone (A/B of the even-spread rule against full 48-row panels on fewer CUs,
-  // the rule that won for gt_chain2_kernel; profiles/r05_gnn_node_rows_ab.txt)
-  static const int node_rows = ANEMOI_EXPERIMENT_ENV("ANEMOI_GNN_NODE_ROWS", 0, 0, kPanel);
-  if (node_rows > 0) a.rows_per_tile = node_rows;
+                  (const char*)wt, bt, t_out_features / kCh, t_out, ld_t, n_rows, plan.rows_per_panel, plan.panels};
   a.seg_ptr = seg_ptr;
-  a.n_tiles = (n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
-  const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
   hipStream_t st = as_stream(stream);
-  if (dtype == ANEMOI_BF16) {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_node_chain_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainSmem); });
-    hipLaunchKernelGGL((gnn_node_chain_kernel<bf16_t>), dim3(grid), dim3(512), kChainSmem, st, a);
-  } else {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gnn_node_chain_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainSmem); });
-    hipLaunchKernelGGL((gnn_node_chain_kernel<f16_t>), dim3(grid), dim3(512), kChainSmem, st, a);
-  }
+  if (dtype == ANEMOI_BF16) ANEMOI_CHAIN_LAUNCH((gnn_node_chain_kernel<bf16_t>), kChainSmem, plan, st, a);
+  else ANEMOI_CHAIN_LAUNCH((gnn_node_chain_kernel<f16_t>), kChainSmem, plan, st, a);
   return check_launch("gnn_node_chain_kernel");
 }
 

@@ -43,7 +43,6 @@
 // (b_p | d1 | b_2 | dq, model dtype) sit in LDS for the whole launch.
 #include <type_traits>
 
-#include "chain2_side_plan.h"
 #include "rowchain_core.h"
 
 namespace anemoi {
@@ -80,10 +79,9 @@ struct Chain2SideArgs : Chain2Args {
 };
 constexpr int kTl2Slots = 48;
 constexpr int kVecOff = vec_off(4);                       // the per-column vectors (16-bit), behind the [48 rows][4 waves][2] partials
-constexpr int kVecMaxElems = 6144;                        // 12 KiB: 512 + hidden + 512 + q_out <= 6144 (hidden = q_out = 2048: 5120)
-constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;
-constexpr int kVecMaxElemsTl = 5120;                      // the instrumented instantiation gives 2 KiB of the vector region to its stamps
+constexpr int kChain2Smem = kVecOff + kVecMaxElems * 2;   // (kVecMaxElems, kVecMaxElemsTl: chain_plan.h)
 constexpr int kTl2Off = kVecOff + kVecMaxElemsTl * 2;
+static_assert(kChain2Smem == kChain2Lds && kTl2Off + 8 * kTl2Slots * 8 == kChain2TlLds, "chain_plan.h prices this layout");
 static_assert(kChain2Smem <= 160 * 1024 && kTl2Off + 8 * kTl2Slots * 8 <= 160 * 1024, "LDS budget");
 
 // What both roles share: the launch's constants and the wave's place in it
@@ -439,51 +437,39 @@ __global__ __launch_bounds__(512, 1) void gt_chain2_kernel(std::conditional_t<SI
   }
 }
 
-// Several rounds: as many workgroups as make the rounds even (854 panels: 4 rounds of 214 instead of 3 of 256 + 86) - the CUs of an XCD share
-// that L2's bandwidth, so a round of 27 CUs per XCD is faster than one of 32 (ANEMOI_CHAIN2_EVEN_GRID=0: always 256)
-static int chain2_launch_grid(int n_tiles) {
-  static const int even_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_EVEN_GRID", 1, 0, 1);
-  static const int max_grid = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_MAX_GRID", 256, 8, 256);  // (experiments: fewer CUs per round)
-  return chain2_grid(n_tiles, even_grid != 0, max_grid);
-}
-
 #ifndef ANEMOI_CHAIN2_SIDE_TU
+// (which instantiation, on how many workgroups: plan_chain - several rounds get as many workgroups as make the rounds even)
 template <typename T>
-static int launch_chain2(const Chain2Args& a, hipStream_t st) {
-  static PerDeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2Smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2Smem);
-  });
-  const int grid = chain2_launch_grid(a.n_tiles);
+static int launch_chain2(const Chain2Args& a, const ChainPlan& plan, hipStream_t st) {
+  switch (plan.kernel) {
+    case ChainKernel::Chain2Full:
+      ANEMOI_CHAIN_LAUNCH((gt_chain2_kernel<T>), kChain2Smem, plan, st, a);
+      return check_launch("gt_chain2_kernel");
+    case ChainKernel::Chain2Part:
+      ANEMOI_CHAIN_LAUNCH((gt_chain2_kernel<T, false, true>), kChain2Smem, plan, st, a);
+      return check_launch("gt_chain2_kernel");
 #ifdef ANEMOI_EXPERIMENTS
-  if (a.timeline != nullptr) {
-    static PerDeviceOnce tl_once;
-    tl_once.run([&] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kTl2Off + 8 * kTl2Slots * 8);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kTl2Off + 8 * kTl2Slots * 8);
-    });
-    if (grid < 256) hipLaunchKernelGGL((gt_chain2_kernel<T, true, true>), dim3(grid), dim3(512), kTl2Off + 8 * kTl2Slots * 8, st, a);
-    else hipLaunchKernelGGL((gt_chain2_kernel<T, true>), dim3(grid), dim3(512), kTl2Off + 8 * kTl2Slots * 8, st, a);
-    return check_launch("gt_chain2_kernel<timeline>");
-  }
+    case ChainKernel::Chain2TlFull:
+      ANEMOI_CHAIN_LAUNCH((gt_chain2_kernel<T, true>), kChain2TlLds, plan, st, a);
+      return check_launch("gt_chain2_kernel<timeline>");
+    case ChainKernel::Chain2TlPart:
+      ANEMOI_CHAIN_LAUNCH((gt_chain2_kernel<T, true, true>), kChain2TlLds, plan, st, a);
+      return check_launch("gt_chain2_kernel<timeline>");
 #endif
-  if (grid < 256) hipLaunchKernelGGL((gt_chain2_kernel<T, false, true>), dim3(grid), dim3(512), kChain2Smem, st, a);
-  else hipLaunchKernelGGL((gt_chain2_kernel<T>), dim3(grid), dim3(512), kChain2Smem, st, a);
-  return check_launch("gt_chain2_kernel");
+    default:
+      set_error("gt_chain2_fwd: no kernel is built for the planned instantiation %s", chain_kernel_name(plan.kernel));
+      return ANEMOI_E_UNSUPPORTED;
+  }
 }
 
 #else  // ANEMOI_CHAIN2_SIDE_TU (gt_chain2_side.hip): the SIDE instantiation lives in a translation unit of its own - compiled beside it, the other
 // instantiations come out with other scalar register numbers than they were tuned and measured with
 constexpr int kSideMax2 = kRowChainSmem > kRowChain2Smem ? kRowChainSmem : kRowChain2Smem;
 constexpr int kChain2SideSmem = kChain2Smem > kSideMax2 ? kChain2Smem : kSideMax2;  // the tail's LDS or the riders', whichever is larger
+static_assert(kChain2SideSmem == kChain2SideLds, "chain_plan.h prices this layout");
 // the tail on the plan's host_grid workgroups with plan.riders workgroups of the side job behind them
 template <typename T>
-static int launch_chain2_side(const Chain2Args& a, const RowChainArgs& side, const Chain2SidePlan& plan, hipStream_t st) {
-  static PerDeviceOnce attr_once;
-  attr_once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_chain2_kernel<T, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kChain2SideSmem);
-  });
+static int launch_chain2_side(const Chain2Args& a, const RowChainArgs& side, const ChainPlan& plan, hipStream_t st) {
   Chain2SideArgs s{};
   static_cast<Chain2Args&>(s) = a;
   s.host_grid = plan.host_grid;
@@ -491,8 +477,8 @@ static int launch_chain2_side(const Chain2Args& a, const RowChainArgs& side, con
   s.side_first = plan.first;
   s.side_end = plan.end;
   s.side_blocks = plan.riders;
-  s.side_pipe = rowchain_pipelined(side.n_tiles, side.k_in) ? 1 : 0;
-  hipLaunchKernelGGL((gt_chain2_kernel<T, false, true, true>), dim3(plan.host_grid + plan.riders), dim3(512), kChain2SideSmem, st, s);
+  s.side_pipe = plan.side_pipelined ? 1 : 0;
+  ANEMOI_CHAIN_LAUNCH((gt_chain2_kernel<T, false, true, true>), kChain2SideSmem, plan, st, s);
   return check_launch("gt_chain2_kernel<side>");
 }
 
@@ -504,33 +490,40 @@ using namespace anemoi;
 
 #ifndef ANEMOI_CHAIN2_SIDE_TU
 
-extern "C" int anemoi_gt_chain_rows_per_tile(int32_t n_rows) {
-  // Rows per LDS panel of the chain launch: always the TALLEST panels (48 rows), i.e. the fewest CUs - every busy CU streams the whole
-  // layer's weights whatever its panel's height, and the CUs of an XCD share that L2's bandwidth: 10 242 rows as 214 panels of 48 instead of
-  // 250 of 41 is 4 % of the O96 forward; multi-round launches even out the ROUNDS instead (launch_chain2), not the panel heights
-  // (profiles/r05_chain2_touch_coverage.txt).  ANEMOI_CHAIN_ROWS=n forces n rows (<= 48).
-  static const int forced = env_int(getenv("ANEMOI_CHAIN_ROWS"), 0, 0, kPanel);
-  (void)n_rows;
-  return forced > 0 ? forced : kPanel;
+// Rows per LDS panel of a block-tail launch (tail_rows_per_tile, chain_plan.h)
+extern "C" int anemoi_gt_chain_rows_per_tile(int32_t) { return tail_rows_per_tile(chain_switches()); }
+
+extern "C" int anemoi_chain_plan(const anemoi_chain_problem_t* q, anemoi_chain_plan_t* out) {
+  ANEMOI_REQUIRE(q != nullptr && out != nullptr, "chain_plan: null problem or out");
+  ANEMOI_REQUIRE(q->kind >= (int)ChainKind::BlockTail && q->kind <= (int)ChainKind::GnnNode, "chain_plan: unknown kind %d", q->kind);
+  ChainProblem c;
+  c.kind = (ChainKind)q->kind;
+  c.n_rows = q->n_rows, c.in_features = q->in_features, c.hidden = q->hidden, c.q_out_features = q->q_out_features, c.rows_per_tile = q->rows_per_tile;
+  c.dtype = (anemoi_dtype_t)q->dtype, c.timeline = q->timeline != 0, c.first_panel = q->first_panel, c.panels = q->panels;
+  c.side_rows = q->side_rows, c.side_in_features = q->side_in_features, c.side_q_out_features = q->side_q_out_features;
+  c.side_rows_per_tile = q->side_rows_per_tile, c.side_cap = q->side_cap;
+  const ChainPlan p = plan_chain(c, chain_switches());
+  if (p.status != ANEMOI_OK) return chain_refused("chain_plan", c, p);
+  *out = anemoi_chain_plan_t{(int32_t)p.kernel, p.rows_per_panel, p.panels, p.grid, p.grid ? p.threads : 0, p.lds_bytes, p.rounds, p.idle_cus,
+                             p.host_grid,       p.riders,         p.first,  p.end,  p.side_pipelined,         p.job_panels, p.pipelined, p.n_rows, p.row_begin};
+  return ANEMOI_OK;
 }
 
 #endif
-// The argument block of the C ABI -> the kernel's, behind every check of the entry points.  ANEMOI_OK with n_tiles = 0: nothing to do.
-static int chain2_args(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, Chain2Args& a) {
+static ChainProblem chain2_problem(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype) {
+  ChainProblem q;
+  q.n_rows = p->n_rows, q.hidden = p->hidden, q.q_out_features = p->q_out_features, q.rows_per_tile = p->rows_per_tile, q.dtype = dtype;
+  q.timeline = p->timeline != nullptr;
+  return q;
+}
+
+// The argument block of the C ABI -> the kernel's, behind the operand checks of the entry points (the shape is the plan's to judge).
+static int chain2_args(const anemoi_gt_chain2_args_t* p, const ChainPlan& plan, Chain2Args& a) {
   a = Chain2Args{};
-  ANEMOI_REQUIRE(p != nullptr, "gt_chain2_fwd: null argument block");
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gt_chain2_fwd: 16-bit model dtypes only");
-  ANEMOI_REQUIRE(p->n_rows >= 0 && p->channels == kCh, "gt_chain2_fwd: channels=%d (this kernel is built for %d)", p->channels, kCh);
   if (p->n_rows == 0) return ANEMOI_OK;
-  const bool narrow = p->q_out_features > 0 && p->q_out_features < kCh;  // a narrow trailing projection: 128, 256 or 384 columns
-  ANEMOI_REQUIRE(p->hidden > 0 && p->hidden % kCh == 0 && p->q_out_features >= 0 && (narrow ? p->q_out_features % 128 == 0 : p->q_out_features % kCh == 0),
-                 "gt_chain2_fwd: hidden=%d must be a multiple of %d, q_out_features=%d a multiple of %d (or 128, 256, 384)", p->hidden, kCh, p->q_out_features, kCh);
-  const int n_vec = 2 * kCh + p->hidden + p->q_out_features;
-  if (n_vec > (p->timeline != nullptr ? kVecMaxElemsTl : kVecMaxElems)) return ANEMOI_E_UNSUPPORTED;  // the per-column vectors must fit their LDS region
   ANEMOI_REQUIRE(p->attn && p->x_res && p->wp && p->w1 && p->w2 && p->vec && (p->x_out || p->q_out_features > 0), "gt_chain2_fwd: null operand");
   ANEMOI_REQUIRE(p->q_out_features == 0 || (p->wq && p->q_out), "gt_chain2_fwd: the trailing projection needs wq and q_out");
   ANEMOI_REQUIRE(p->extra == nullptr || p->x_out != nullptr, "gt_chain2_fwd: a second residual needs x_out");
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   ANEMOI_REQUIRE(al16(p->attn) && al16(p->x_res) && al16(p->wp) && al16(p->w1) && al16(p->w2) && al16(p->x_out) && al16(p->wq) && al16(p->q_out) &&
                      al16(p->extra) && al16(p->vec),
                  "gt_chain2_fwd: operands must be 16-byte aligned");
@@ -538,6 +531,7 @@ static int chain2_args(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, C
                      (p->extra == nullptr || (p->ld_extra >= kCh && p->ld_extra % 8 == 0)) &&
                      (p->q_out_features == 0 || (p->ld_q >= p->q_out_features && p->ld_q % 8 == 0)),
                  "gt_chain2_fwd: leading dimensions too small or not multiples of 8 elements (rows move as 16-byte pieces)");
+  const bool narrow = p->q_out_features > 0 && p->q_out_features < kCh;  // a narrow trailing projection: 128, 256 or 384 columns
   a.attn = p->attn; a.ld_attn = p->ld_attn;
   a.xres = p->x_res; a.ld_x = p->ld_x;
   a.wp = (const char*)p->wp;
@@ -550,10 +544,6 @@ static int chain2_args(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, C
   a.extra = p->extra; a.ld_extra = p->ld_extra;
   a.xout = p->x_out; a.ld_out = p->ld_out;
   a.qout = p->q_out; a.ld_q = p->ld_q;
-  if (!kExperiments && p->timeline != nullptr) {
-    set_error("gt_chain2_fwd: the in-kernel timeline is part of the experiments build only (python -m anemoi_core_amd.build --experiments)");
-    return ANEMOI_E_UNSUPPORTED;
-  }
   a.timeline = reinterpret_cast<unsigned long long*>(p->timeline);
   static const int prio_a = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_PRIO_A", 0, 0, 2);
   a.prio_a = prio_a;
@@ -566,43 +556,46 @@ static int chain2_args(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, C
   static const int b_delay = ANEMOI_EXPERIMENT_ENV("ANEMOI_CHAIN2_B_DELAY", 0, 0, 40);
   a.b_delay = b_delay;
   a.n_rows = p->n_rows;
-  a.rows_per_tile = p->rows_per_tile > 0 ? p->rows_per_tile : anemoi_gt_chain_rows_per_tile(p->n_rows);
-  ANEMOI_REQUIRE(a.rows_per_tile <= kPanel, "gt_chain2_fwd: rows_per_tile=%d exceeds the %d-row panel", a.rows_per_tile, kPanel);
-  a.n_tiles = (a.n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
+  a.rows_per_tile = plan.rows_per_panel;
+  a.n_tiles = plan.panels;
   return ANEMOI_OK;
 }
 
 #ifndef ANEMOI_CHAIN2_SIDE_TU
 extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t* p, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(p != nullptr, "gt_chain2_fwd: null argument block");
+  ANEMOI_REQUIRE(p->channels == kCh, "gt_chain2_fwd: channels=%d (this kernel is built for %d)", p->channels, kCh);
+  const ChainProblem q = chain2_problem(p, dtype);
+  const ChainPlan plan = plan_chain(q, chain_switches());
+  if (plan.status != ANEMOI_OK) return chain_refused("gt_chain2_fwd", q, plan);
   Chain2Args a;
-  const int rc = chain2_args(p, dtype, a);
-  if (rc != ANEMOI_OK || a.n_tiles == 0) return rc;
+  const int rc = chain2_args(p, plan, a);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
   hipStream_t st = as_stream(stream);
-  return dtype == ANEMOI_BF16 ? launch_chain2<bf16_t>(a, st) : launch_chain2<f16_t>(a, st);
+  return dtype == ANEMOI_BF16 ? launch_chain2<bf16_t>(a, plan, st) : launch_chain2<f16_t>(a, plan, st);
 }
 
 #else
 extern "C" int anemoi_gt_chain2_side_fwd(const anemoi_gt_chain2_args_t* p, const anemoi_gt_rowchain_args_t* side, int32_t side_first_panel,
                                          int32_t side_panels, int32_t side_blocks, anemoi_dtype_t dtype, void* stream) {
+  const char* who = "gt_chain2_side_fwd";
+  ANEMOI_REQUIRE(p != nullptr && side != nullptr, "%s: null argument block or side job", who);
+  ANEMOI_REQUIRE(p->channels == kCh, "%s: channels=%d (this kernel is built for %d)", who, p->channels, kCh);
+  ChainProblem q = chain2_problem(p, dtype);
+  q.kind = ChainKind::BlockTailSide;
+  q.first_panel = side_first_panel, q.panels = side_panels, q.side_cap = side_blocks;
+  q.side_rows = side->n_rows, q.side_in_features = side->in_features, q.side_q_out_features = side->q_out_features, q.side_rows_per_tile = side->rows_per_tile;
+  const ChainPlan plan = plan_chain(q, chain_switches());
+  if (plan.status != ANEMOI_OK) return chain_refused(who, q, plan);
   Chain2Args a;
-  int rc = chain2_args(p, dtype, a);
+  const int rc = chain2_args(p, plan, a);
   if (rc != ANEMOI_OK) return rc;
-  ANEMOI_REQUIRE(side != nullptr, "gt_chain2_side_fwd: null side job");
-  ANEMOI_REQUIRE(p->timeline == nullptr, "gt_chain2_side_fwd: no in-kernel timeline beside a side job");
-  ANEMOI_REQUIRE(side_first_panel >= 0 && side_panels >= 0 && side_blocks >= 0,
-                 "gt_chain2_side_fwd: side_first_panel=%d, side_panels=%d, side_blocks=%d must not be negative", side_first_panel, side_panels, side_blocks);
   RowChainArgs r;
-  // (the side job's own preconditions: a job the row chain cannot take is the caller's to launch some other way)
-  if (rowchain_args(side, dtype, "gt_chain2_side_fwd (side job)", r) != ANEMOI_OK) return ANEMOI_E_UNSUPPORTED;
-  ANEMOI_REQUIRE((int64_t)side_first_panel + side_panels <= r.n_tiles, "gt_chain2_side_fwd: panels [%d, %d + %d) of a side job of %d panels",
-                 side_first_panel, side_first_panel, side_panels, r.n_tiles);
-  Chain2SidePlan plan;
-  if (!plan_chain2_side(a.n_tiles, chain2_launch_grid(a.n_tiles), side_first_panel, side_panels, side_blocks, plan)) {
-    set_error("gt_chain2_side_fwd: a tail of %d panels leaves no compute unit idle (launch the two pieces separately)", a.n_tiles);
-    return ANEMOI_E_UNSUPPORTED;
-  }
-  hipStream_t st = as_stream(stream);
+  ChainPlan job;
+  // (the side job's operands: a job the row chain cannot take is the caller's to launch some other way)
+  if (rowchain_args(side, rowchain_problem(side, dtype), "gt_chain2_side_fwd (side job)", r, job) != ANEMOI_OK) return ANEMOI_E_UNSUPPORTED;
   if (plan.riders == 0) return anemoi_gt_chain2_fwd(p, dtype, stream);  // (no panels asked for)
+  hipStream_t st = as_stream(stream);
   return dtype == ANEMOI_BF16 ? launch_chain2_side<bf16_t>(a, r, plan, st) : launch_chain2_side<f16_t>(a, r, plan, st);
 }
 #endif

@@ -26,7 +26,6 @@
 
 namespace anemoi {
 
-constexpr int kClusterSize = 4;
 
 struct ClusterArgs {
   const void* attn;  int64_t ld_attn;
@@ -50,6 +49,7 @@ constexpr int kClVecOff = vec_off(8);  // the per-column vectors, behind the [48
 constexpr int kClVecMax = 5120;  // 512 + 2048 + 512 + 2048
 constexpr int kClusterSmem = kClVecOff + kClVecMax * 2;
 static_assert(kClusterSmem <= 160 * 1024, "LDS budget");
+static_assert(kClusterSmem == kClusterLds, "chain_plan.h prices this layout");
 constexpr size_t kClSlotFloats = (size_t)8 * 3 * 4 * 64 * 4;  // one member's partial [48 x 512] in accumulator layout
 
 __device__ __forceinline__ void store_sc1(float* p, f32x4 v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
@@ -275,12 +275,6 @@ __global__ __launch_bounds__(512, 1) void gt_cluster_chain_kernel(ClusterArgs a)
 
 using namespace anemoi;
 
-static int cluster_grid(int n_tiles) {
-  int per_xcd = (n_tiles + 7) / 8;  // clusters per XCD
-  if (per_xcd > 8) per_xcd = 8;     // 8 clusters x 4 members = the XCD's 32 CUs
-  return per_xcd * 32;
-}
-
 extern "C" int64_t anemoi_gt_cluster_chain_workspace_bytes(void) {
   // 64 clusters x (2 parities x 4 members x [48 x 512] fp32 + a counter line)
   return (int64_t)64 * (2 * kClusterSize * (int64_t)kClSlotFloats * 4) + 64 * 128;
@@ -288,22 +282,18 @@ extern "C" int64_t anemoi_gt_cluster_chain_workspace_bytes(void) {
 
 extern "C" int anemoi_gt_cluster_chain_fwd(const anemoi_gt_cluster_chain_args_t* p, anemoi_dtype_t dtype, void* stream) {
   ANEMOI_REQUIRE(p != nullptr, "gt_cluster_chain_fwd: null argument block");
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "gt_cluster_chain_fwd: 16-bit model dtypes only");
-  ANEMOI_REQUIRE(p->n_rows >= 0 && p->channels == kCh, "gt_cluster_chain_fwd: channels=%d (this kernel is built for %d)", p->channels, kCh);
-  if (p->n_rows == 0) return ANEMOI_OK;
-  if (p->hidden != 4 * kCh) {
-    set_error("gt_cluster_chain_fwd: hidden=%d (the cluster of four splits a hidden width of %d)", p->hidden, 4 * kCh);
-    return ANEMOI_E_UNSUPPORTED;
-  }
-  ANEMOI_REQUIRE(p->q_out_features >= 0 && p->q_out_features % kCh == 0 && p->q_out_features <= 4 * kCh,
-                 "gt_cluster_chain_fwd: q_out_features=%d must be a multiple of %d up to %d", p->q_out_features, kCh, 4 * kCh);
+  ANEMOI_REQUIRE(p->channels == kCh, "gt_cluster_chain_fwd: channels=%d (this kernel is built for %d)", p->channels, kCh);
+  ChainProblem q;
+  q.kind = ChainKind::ClusterTail;
+  q.n_rows = p->n_rows, q.hidden = p->hidden, q.q_out_features = p->q_out_features, q.dtype = dtype;
+  const ChainPlan plan = plan_chain(q, chain_switches());
+  if (plan.status != ANEMOI_OK || plan.grid == 0) return chain_refused("gt_cluster_chain_fwd", q, plan);
   ANEMOI_REQUIRE(p->attn && p->x_res && p->wp && p->w1 && p->w2 && p->vec && p->x_out && p->workspace, "gt_cluster_chain_fwd: null operand");
   // columns of the trailing projection that go to q_out (all of them without a second destination)
   const int q1_cols = p->q_out2 != nullptr ? (p->q_split < 0 ? 0 : (p->q_split * kCh < p->q_out_features ? p->q_split * kCh : p->q_out_features)) : p->q_out_features;
   ANEMOI_REQUIRE(p->q_out_features == 0 || (p->wq && (q1_cols == 0 || p->q_out)), "gt_cluster_chain_fwd: the trailing projection needs wq and q_out");
   ANEMOI_REQUIRE((p->q_out_features == 0 && p->ln_out == nullptr) || p->extra == nullptr,
                  "gt_cluster_chain_fwd: the trailing projection / LayerNorm output read x2 before a second residual is added: not both");
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   ANEMOI_REQUIRE(al16(p->attn) && al16(p->x_res) && al16(p->wp) && al16(p->w1) && al16(p->w2) && al16(p->x_out) && al16(p->wq) && al16(p->q_out) &&
                      al16(p->extra) && al16(p->vec) && al16(p->ln_out) && (reinterpret_cast<uintptr_t>(p->workspace) & 127) == 0,
                  "gt_cluster_chain_fwd: operands must be 16-byte aligned (workspace: 128)");
@@ -332,18 +322,10 @@ extern "C" int anemoi_gt_cluster_chain_fwd(const anemoi_gt_cluster_chain_args_t*
   a.counters = reinterpret_cast<unsigned*>(p->workspace);
   a.scratch = reinterpret_cast<float*>(reinterpret_cast<char*>(p->workspace) + 64 * 128);
   a.n_rows = p->n_rows;
-  a.rows_per_tile = kPanel;
-  a.n_tiles = (a.n_rows + kPanel - 1) / kPanel;
-  const int grid = cluster_grid(a.n_tiles);
+  a.rows_per_tile = plan.rows_per_panel;
+  a.n_tiles = plan.panels;
   hipStream_t st = as_stream(stream);
-  if (dtype == ANEMOI_BF16) {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_cluster_chain_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kClusterSmem); });
-    hipLaunchKernelGGL((gt_cluster_chain_kernel<bf16_t>), dim3(grid), dim3(512), kClusterSmem, st, a);
-  } else {
-    static PerDeviceOnce once;
-    once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_cluster_chain_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kClusterSmem); });
-    hipLaunchKernelGGL((gt_cluster_chain_kernel<f16_t>), dim3(grid), dim3(512), kClusterSmem, st, a);
-  }
+  if (dtype == ANEMOI_BF16) ANEMOI_CHAIN_LAUNCH((gt_cluster_chain_kernel<bf16_t>), kClusterSmem, plan, st, a);
+  else ANEMOI_CHAIN_LAUNCH((gt_cluster_chain_kernel<f16_t>), kClusterSmem, plan, st, a);
   return check_launch("gt_cluster_chain_kernel");
 }

@@ -26,17 +26,18 @@
 
 namespace anemoi {
 
-constexpr int kEfRows = 80, kEfBands = 5, kEfWaves = 4, kEfThreads = 64 * kEfWaves;
+constexpr int kEfBands = 5, kEfWaves = 4;  // (kEfRows, kEfThreads, kEfMaxQ: chain_plan.h)
+static_assert(kEfRows == 16 * kEfBands && kEfThreads == 64 * kEfWaves, "chain_plan.h plans this tile");
 constexpr int kEfRowBytes = 512;                        // 256 16-bit columns: the widest K
 constexpr int kEfRedOff = kEfRows * kEfRowBytes;         // [80 rows][4 waves][2] fp32 partials
 constexpr int kEfStripOff = kEfRedOff + kEfRows * 4 * 2 * 4;
 constexpr int kEfStripBytes = 16 * 256;                  // one row band of a wave's 128 columns
 constexpr int kEfVecOff = kEfStripOff + kEfWaves * kEfStripBytes;
-constexpr int kEfMaxQ = 2048;
 constexpr int kEfVecMax = kCh + 3 * kEfMaxQ;             // fp32 [b_e | u | s | d]
 constexpr int ef_smem(int qc) { return kEfVecOff + (kCh + 3 * kCh * qc) * 4; }
 constexpr int kEfXIt = kEfRows * 32 / kEfThreads, kEfVecIt = (kEfVecMax / 4 + kEfThreads - 1) / kEfThreads;  // 16-byte pieces per thread, at most
 static_assert(ef_smem(kEfMaxQ / kCh) <= 160 * 1024, "LDS budget");
+static_assert(ef_smem(1) == ef_lds(1) && ef_smem(kEfMaxQ / kCh) == ef_lds(kEfMaxQ / kCh) && kEfRowBytes == 2 * kEfMaxIn, "chain_plan.h prices this layout");
 
 struct EmbedFoldArgs {
   const void* x;   int64_t ld_x;  int k_in;  // [n_rows, k_in] rows (k_in % 8 == 0, <= 256)
@@ -202,17 +203,6 @@ __global__ __launch_bounds__(kEfThreads, 2) void gt_embed_fold_kernel(EmbedFoldA
   }
 }
 
-template <typename T>
-static int launch_embed_fold(const EmbedFoldArgs& a, hipStream_t st) {
-  static PerDeviceOnce once;
-  once.run([&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_embed_fold_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, ef_smem(kEfMaxQ / kCh));
-  });
-  const int grid = (a.n_rows + kEfRows - 1) / kEfRows;
-  hipLaunchKernelGGL((gt_embed_fold_kernel<T>), dim3(grid), dim3(kEfThreads), ef_smem(a.qc), st, a);
-  return check_launch("gt_embed_fold_kernel");
-}
-
 }  // namespace anemoi
 
 using namespace anemoi;
@@ -220,16 +210,13 @@ using namespace anemoi;
 extern "C" int anemoi_gt_embed_fold_fwd(const anemoi_gt_embed_fold_args_t* p, anemoi_dtype_t dtype, void* stream) {
   const char* who = "gt_embed_fold_fwd";
   ANEMOI_REQUIRE(p != nullptr, "%s: null argument block", who);
-  ANEMOI_REQUIRE(p->n_rows >= 0 && p->in_features > 0 && p->q_out_features > 0, "%s: n_rows=%d in_features=%d q_out_features=%d", who, p->n_rows,
-                 p->in_features, p->q_out_features);
-  if ((dtype != ANEMOI_BF16 && dtype != ANEMOI_F16) || p->channels != kCh || p->in_features > 256 || p->in_features % 8 != 0 ||
-      p->q_out_features % kCh != 0 || p->q_out_features > kEfMaxQ) {
-    set_error("%s: not eligible (16-bit dtypes, 512 channels, in_features a multiple of 8 up to 256, q_out_features a multiple of 512 up to %d)", who, kEfMaxQ);
-    return ANEMOI_E_UNSUPPORTED;
-  }
-  if (p->n_rows == 0) return ANEMOI_OK;
+  ChainProblem q;
+  q.kind = ChainKind::EmbedFold;
+  q.n_rows = p->n_rows, q.in_features = p->in_features, q.q_out_features = p->q_out_features, q.dtype = dtype;
+  ChainPlan plan = plan_chain(q, chain_switches());
+  if (plan.status == ANEMOI_OK && p->channels != kCh) plan = refuse(ANEMOI_E_UNSUPPORTED, "built for 512 channels");
+  if (plan.status != ANEMOI_OK || plan.grid == 0) return chain_refused(who, q, plan);
   ANEMOI_REQUIRE(p->x && p->we && p->wc && p->vec && p->q_out, "%s: null operand", who);
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   ANEMOI_REQUIRE(al16(p->x) && al16(p->we) && al16(p->wc) && al16(p->vec) && al16(p->q_out), "%s: operands must be 16-byte aligned", who);
   ANEMOI_REQUIRE(p->ld_x >= p->in_features && p->ld_x % 8 == 0 && p->ld_q >= p->q_out_features && p->ld_q % 8 == 0,
                  "%s: leading dimensions too small or not multiples of 8 elements", who);
@@ -241,5 +228,7 @@ extern "C" int anemoi_gt_embed_fold_fwd(const anemoi_gt_embed_fold_args_t* p, an
   a.qout = p->q_out; a.ld_q = p->ld_q;
   a.n_rows = p->n_rows;
   hipStream_t st = as_stream(stream);
-  return dtype == ANEMOI_BF16 ? launch_embed_fold<bf16_t>(a, st) : launch_embed_fold<f16_t>(a, st);
+  if (dtype == ANEMOI_BF16) ANEMOI_CHAIN_LAUNCH((gt_embed_fold_kernel<bf16_t>), ef_smem(kEfMaxQ / kCh), plan, st, a);
+  else ANEMOI_CHAIN_LAUNCH((gt_embed_fold_kernel<f16_t>), ef_smem(kEfMaxQ / kCh), plan, st, a);
+  return check_launch("gt_embed_fold_kernel");
 }

@@ -56,20 +56,15 @@ __global__ __launch_bounds__(512, 1) void gt_rowchain_pipe_kernel(RowChainArgs a
   else pipe_role_b<T>(a, c, smem);
 }
 
-// pipelined < 0: the schedule the job's own size asks for
+// the plan's kernel: the single-panel schedule, or - several rounds of panels - the two wave groups on different panels
 template <typename T>
-static int launch_rowchain(const RowChainArgs& a, hipStream_t st, int pipelined = -1) {
-  static PerDeviceOnce once;
-  once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_rowchain_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, kRowChainSmem); });
-  const int grid = rowchain_grid(a.n_tiles);
-  if (pipelined < 0 ? rowchain_pipelined(a.n_tiles, a.k_in) : pipelined != 0) {  // several rounds of panels: the two wave groups on different panels
-    static PerDeviceOnce once2;
-    once2.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gt_rowchain_pipe_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, kRowChain2Smem); });
-    hipLaunchKernelGGL((gt_rowchain_pipe_kernel<T>), dim3(grid), dim3(512), kRowChain2Smem, st, a);
-    return check_launch("gt_rowchain_pipe_kernel");
+static int launch_rowchain(const RowChainArgs& a, const ChainPlan& plan, hipStream_t st) {
+  if (plan.kernel == ChainKernel::RowChainSingle) {
+    ANEMOI_CHAIN_LAUNCH((gt_rowchain_kernel<T>), kRowChainSmem, plan, st, a);
+    return check_launch("gt_rowchain_kernel");
   }
-  hipLaunchKernelGGL((gt_rowchain_kernel<T>), dim3(grid), dim3(512), kRowChainSmem, st, a);
-  return check_launch("gt_rowchain_kernel");
+  ANEMOI_CHAIN_LAUNCH((gt_rowchain_pipe_kernel<T>), kRowChain2Smem, plan, st, a);
+  return check_launch("gt_rowchain_pipe_kernel");
 }
 
 }  // namespace anemoi
@@ -77,29 +72,28 @@ static int launch_rowchain(const RowChainArgs& a, hipStream_t st, int pipelined 
 using namespace anemoi;
 
 extern "C" int anemoi_gt_rowchain_fwd(const anemoi_gt_rowchain_args_t* p, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(p != nullptr, "gt_rowchain_fwd: null argument block");
   RowChainArgs a;
-  const int rc = rowchain_args(p, dtype, "gt_rowchain_fwd", a);
-  if (rc != ANEMOI_OK || a.n_tiles == 0) return rc;
+  ChainPlan plan;
+  const int rc = rowchain_args(p, rowchain_problem(p, dtype), "gt_rowchain_fwd", a, plan);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
   hipStream_t st = as_stream(stream);
-  return dtype == ANEMOI_BF16 ? launch_rowchain<bf16_t>(a, st) : launch_rowchain<f16_t>(a, st);
+  return dtype == ANEMOI_BF16 ? launch_rowchain<bf16_t>(a, plan, st) : launch_rowchain<f16_t>(a, plan, st);
 }
 
 extern "C" int anemoi_gt_rowchain_panels_fwd(const anemoi_gt_rowchain_args_t* p, int32_t first_panel, int32_t panels, anemoi_dtype_t dtype, void* stream) {
+  ANEMOI_REQUIRE(p != nullptr, "gt_rowchain_panels_fwd: null argument block");
   RowChainArgs a;
-  const int rc = rowchain_args(p, dtype, "gt_rowchain_panels_fwd", a);
-  if (rc != ANEMOI_OK) return rc;
-  ANEMOI_REQUIRE(first_panel >= 0 && panels >= 0 && (int64_t)first_panel + panels <= a.n_tiles, "gt_rowchain_panels_fwd: panels [%d, %d + %d) of a job of %d panels",
-                 first_panel, first_panel, panels, a.n_tiles);
-  if (panels == 0) return ANEMOI_OK;
-  // the schedule of the WHOLE job (a panel's bits do not depend on which launch computes it), on the range's rows: the job shifted to its first row
-  const int pipelined = rowchain_pipelined(a.n_tiles, a.k_in) ? 1 : 0;
-  const int64_t r0 = (int64_t)first_panel * a.rows_per_tile, es = 2;
-  const int64_t r1 = r0 + (int64_t)panels * a.rows_per_tile;
-  a.x = static_cast<const char*>(a.x) + r0 * a.ld_x * es;
-  if (a.xout != nullptr) a.xout = static_cast<char*>(a.xout) + r0 * a.ld_out * es;
-  a.qout = static_cast<char*>(a.qout) + r0 * a.ld_q * es;
-  a.n_rows = (int)((r1 < a.n_rows ? r1 : (int64_t)a.n_rows) - r0);
-  a.n_tiles = panels;
+  ChainPlan plan;
+  const int rc = rowchain_args(p, rowchain_problem(p, dtype, ChainKind::RowChainPanels, first_panel, panels), "gt_rowchain_panels_fwd", a, plan);
+  if (rc != ANEMOI_OK || plan.grid == 0) return rc;
+  // the plan's schedule is the WHOLE job's (a panel's bits do not depend on which launch computes it), on the range's rows: the job shifted to its first row
+  const int64_t es = 2;
+  a.x = static_cast<const char*>(a.x) + plan.row_begin * a.ld_x * es;
+  if (a.xout != nullptr) a.xout = static_cast<char*>(a.xout) + plan.row_begin * a.ld_out * es;
+  a.qout = static_cast<char*>(a.qout) + plan.row_begin * a.ld_q * es;
+  a.n_rows = plan.n_rows;
+  a.n_tiles = plan.panels;
   hipStream_t st = as_stream(stream);
-  return dtype == ANEMOI_BF16 ? launch_rowchain<bf16_t>(a, st, pipelined) : launch_rowchain<f16_t>(a, st, pipelined);
+  return dtype == ANEMOI_BF16 ? launch_rowchain<bf16_t>(a, plan, st) : launch_rowchain<f16_t>(a, plan, st);
 }

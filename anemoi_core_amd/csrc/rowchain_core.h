@@ -26,6 +26,7 @@ constexpr int kRcVecOff = vec_off(8);  // the per-column vectors (16-bit), behin
 constexpr int kRcVecMax = 2560;
 constexpr int kRowChainSmem = kRcVecOff + kRcVecMax * 2;
 static_assert(kRowChainSmem <= 160 * 1024, "LDS budget");
+static_assert(kRowChainSmem == kRowChainLds && kRcVecMax == kCh + kRowChainMaxQ, "chain_plan.h prices this layout");
 
 // A panel of input rows: 48 rows x spr = 16 ng sixteen-byte slots (slots beyond the row's k_in / 8 are zero), shared out among the 512
 // threads (<= 6 slots each), requested into registers and stored to the swizzled panel later - the request of the NEXT panel rides under
@@ -149,6 +150,7 @@ __device__ __forceinline__ void rowchain_panels(const RowChainArgs& a, const Wal
 constexpr int kRc2Vec = vec_off(4);  // (four waves' partials)
 constexpr int kRowChain2Smem = kRc2Vec + kRcVecMax * 2;
 static_assert(kRowChain2Smem <= 160 * 1024, "LDS budget");
+static_assert(kRowChain2Smem == kRowChainPipeLds, "chain_plan.h prices this layout");
 
 struct XRowsA {  // a panel of input rows shared out among group A's 256 threads: <= 6 sixteen-byte slots each (in_features <= 256)
   u32x4 v[6];
@@ -303,41 +305,28 @@ __device__ __forceinline__ void rowchain_pipe_panels(const RowChainArgs& a, int 
   else pipe_role_b<T>(a, c, smem);
 }
 
-// Workgroups of a row-chain launch: one per panel up to the chip; several rounds: as many as make the rounds even (the CUs of an XCD share that
-// L2's bandwidth; gt_chain2.hip's rule).  Which schedule a job of n_tiles panels runs: several rounds and in_features <= 256 -> pipelined.  The two
-// schedules round differently (statistics merged from four or eight partials, the embedding's bias first or last): whoever computes a PART of a
-// job - the riders of a block tail, the launch of the panels no tail hosted - takes the schedule of the whole job, so that a panel's bits do not
-// depend on where it ran.
-inline int rowchain_grid(int n_tiles) {
-  int grid = n_tiles < 256 ? n_tiles : 256;
-  if (n_tiles > 256) {
-    const int rounds = (n_tiles + 255) / 256;
-    grid = (n_tiles + rounds - 1) / rounds;
-  }
-  return grid;
+// The argument block of the C ABI -> the kernel's: the shape is the plan's to judge (chain_plan.h: grid, schedule - rowchain_pipelined on why a
+// part of a job takes the schedule of the whole job), the operands are judged here (`who`: the entry point's name in the messages).
+// ANEMOI_OK with an empty plan: nothing to do.
+inline ChainProblem rowchain_problem(const anemoi_gt_rowchain_args_t* p, anemoi_dtype_t dtype, ChainKind kind = ChainKind::RowChain, int first_panel = 0,
+                                     int panels = 0) {
+  ChainProblem q;
+  q.kind = kind;
+  q.n_rows = p->n_rows, q.in_features = p->in_features, q.q_out_features = p->q_out_features, q.rows_per_tile = p->rows_per_tile, q.dtype = dtype;
+  q.first_panel = first_panel, q.panels = panels;
+  return q;
 }
-inline bool rowchain_pipelined(int n_tiles, int k_in) { return n_tiles > rowchain_grid(n_tiles) && k_in <= 256; }
-
-// The argument block of the C ABI -> the kernel's; the entry points' shared preconditions (`who`: the entry point's name in the messages).
-// ANEMOI_OK with n_tiles = 0: nothing to do.
-inline int rowchain_args(const anemoi_gt_rowchain_args_t* p, anemoi_dtype_t dtype, const char* who, RowChainArgs& a) {
+inline int rowchain_args(const anemoi_gt_rowchain_args_t* p, const ChainProblem& q, const char* who, RowChainArgs& a, ChainPlan& plan) {
   a = RowChainArgs{};
-  ANEMOI_REQUIRE(p != nullptr, "%s: null argument block", who);
-  ANEMOI_REQUIRE(dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "%s: 16-bit model dtypes only", who);
-  ANEMOI_REQUIRE(p->n_rows >= 0 && p->channels == kCh, "%s: channels=%d (this kernel is built for %d)", who, p->channels, kCh);
+  ANEMOI_REQUIRE(p->channels == kCh, "%s: channels=%d (this kernel is built for %d)", who, p->channels, kCh);
+  plan = plan_chain(q, chain_switches());
+  if (plan.status != ANEMOI_OK) return chain_refused(who, q, plan);
   if (p->n_rows == 0) return ANEMOI_OK;
-  ANEMOI_REQUIRE(p->in_features > 0 && p->in_features <= kCh && p->in_features % 8 == 0,
-                 "%s: in_features=%d must be a multiple of 8 up to %d (rows move as 16-byte pieces)", who, p->in_features, kCh);
-  ANEMOI_REQUIRE(p->q_out_features > 0 && p->q_out_features % kCh == 0 && p->q_out_features <= 4 * kCh,
-                 "%s: q_out_features=%d must be a multiple of %d up to %d", who, p->q_out_features, kCh, 4 * kCh);
   ANEMOI_REQUIRE(p->x && p->we && p->wq && p->vec && p->q_out, "%s: null operand", who);
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   ANEMOI_REQUIRE(al16(p->x) && al16(p->we) && al16(p->wq) && al16(p->vec) && al16(p->x_out) && al16(p->q_out), "%s: operands must be 16-byte aligned", who);
   ANEMOI_REQUIRE(p->ld_x >= p->in_features && p->ld_x % 8 == 0 && p->ld_q >= p->q_out_features && p->ld_q % 8 == 0 &&
                      (p->x_out == nullptr || (p->ld_out >= kCh && p->ld_out % 8 == 0)),
                  "%s: leading dimensions too small or not multiples of 8 elements", who);
-  const int rpt = p->rows_per_tile > 0 ? p->rows_per_tile : kPanel;
-  ANEMOI_REQUIRE(rpt <= kPanel, "%s: rows_per_tile=%d exceeds the %d-row panel", who, rpt, kPanel);
   a.x = p->x; a.ld_x = p->ld_x; a.k_in = p->in_features;
   a.we = (const char*)p->we; a.ng = (p->in_features + 127) / 128;
   a.wq = (const char*)p->wq; a.qc = p->q_out_features / kCh;
@@ -346,8 +335,8 @@ inline int rowchain_args(const anemoi_gt_rowchain_args_t* p, anemoi_dtype_t dtyp
   a.xout = p->x_out; a.ld_out = p->ld_out;
   a.qout = p->q_out; a.ld_q = p->ld_q;
   a.n_rows = p->n_rows;
-  a.rows_per_tile = rpt;
-  a.n_tiles = (a.n_rows + rpt - 1) / rpt;
+  a.rows_per_tile = p->rows_per_tile > 0 ? p->rows_per_tile : kPanel;
+  a.n_tiles = (a.n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
   return ANEMOI_OK;
 }
 

@@ -22,13 +22,12 @@ def side_schedule(host_rows: int, side_panels_left: int, panels_per_rider: int) 
     """How many of a side job's remaining 48-row panels ride on a block-tail launch over ``host_rows`` rows: ``panels_per_rider`` for every
     compute unit the launch leaves idle, per round of its panels (a tail of several rounds lasts that many times longer); 0 for a launch
     that keeps every compute unit busy.  Pure: the hosting decision is this function and nothing else."""
-    from ..ops import CHAIN_PANEL_ROWS, CHIP_CUS, chain_idle_cus
+    from ..ops import CHAIN_CHANNELS, chain_plan
 
-    idle = chain_idle_cus(host_rows)
-    if idle <= 0 or side_panels_left <= 0 or panels_per_rider <= 0:
+    if host_rows <= 0 or side_panels_left <= 0 or panels_per_rider <= 0:
         return 0
-    rounds = -(-(-(-host_rows // CHAIN_PANEL_ROWS)) // (CHIP_CUS - idle))
-    return min(side_panels_left, idle * panels_per_rider * rounds)
+    tail = chain_plan("block_tail", host_rows, hidden=CHAIN_CHANNELS)  # (the grid of a tail does not depend on its widths)
+    return min(side_panels_left, tail.idle_cus * panels_per_rider * tail.rounds)
 
 
 @dataclass
@@ -49,9 +48,9 @@ class SideJob:
 
     @property
     def n_panels(self) -> int:
-        from ..ops import CHAIN_PANEL_ROWS
+        from ..ops import row_chain_panels
 
-        return -(-self.x.shape[0] // CHAIN_PANEL_ROWS)
+        return row_chain_panels(self.x.shape[0], self.x.shape[1], self.q_out_features)
 
     def slice_for(self, host_rows: int):
         """The next panels for a block-tail launch over ``host_rows`` rows as an ``ops.ChainSide`` (None: none), taken off the job."""

@@ -12,6 +12,7 @@ The op-level mirror of the reference boundary is at the bottom:
 from __future__ import annotations
 
 from dataclasses import dataclass
+import functools
 from typing import NamedTuple, Optional
 
 import os
@@ -1093,6 +1094,91 @@ def linear_plan(role: str, n_rows: int, K: int, O: int, *, K2: int = 0, residual
 # ------------------------------------------------------------------------------------------ row-resident layer chain
 CHAIN_CHANNELS = 512  # the chain kernels (csrc/gt_chain2.hip, gnn_chain.hip) are built for this width: 4 waves x 128 / 8 waves x 64 columns
 
+# which entry point: ChainKind of csrc/chain_plan.h
+CHAIN_KINDS = ("block_tail", "block_tail_side", "cluster_tail", "row_chain", "row_chain_panels", "embed_fold", "gnn_edge", "gnn_mlp", "gnn_node")
+# ChainKernel: the instantiation as the host code names it, its dtype argument dropped
+CHAIN_KERNELS = ("none", "gt_chain2_kernel", "gt_chain2_kernel<false,true>", "gt_chain2_kernel<true>", "gt_chain2_kernel<true,true>",
+                 "gt_chain2_kernel<false,true,true>", "gt_cluster_chain_kernel", "gt_rowchain_kernel", "gt_rowchain_pipe_kernel", "gt_embed_fold_kernel",
+                 "gnn_edge_chain_kernel", "gnn_edge_chain_kernel<true>", "gnn_node_chain_kernel")
+
+
+class ChainSideShape(NamedTuple):
+    """The side job of a ``block_tail_side`` plan: a row-chain job of ``rows`` x ``in_features`` -> ``q_out``, of which ``panels`` panels from
+    ``first_panel`` ride, on at most ``cap`` workgroups (0: every idle compute unit)."""
+    rows: int
+    in_features: int
+    q_out: int
+    first_panel: int = 0
+    panels: int = 0
+    cap: int = 0
+    rows_per_tile: int = 0
+
+
+class ChainPlan(NamedTuple):
+    """What a chain entry point launches for a shape: ``kernel`` (one of CHAIN_KERNELS; "none": nothing to do) over ``panels`` panels of
+    ``rows_per_panel`` rows on ``grid`` workgroups; the other fields as in anemoi_chain_plan_t (include/anemoi_hip.h)."""
+    kernel: str
+    rows_per_panel: int
+    panels: int
+    grid: int
+    threads: int
+    lds_bytes: int
+    rounds: int
+    idle_cus: int
+    host_grid: int
+    riders: int
+    first: int
+    end: int
+    side_pipelined: bool
+    job_panels: int
+    pipelined: bool
+    n_rows: int
+    row_begin: int
+
+
+@functools.lru_cache(maxsize=4096)
+def chain_plan(kind: str, n_rows: int, *, in_features: int = 0, hidden: int = 0, q_out: int = 0, rows_per_tile: int = 0,
+               dtype: torch.dtype = torch.bfloat16, timeline: bool = False, first_panel: int = 0, panels: int = 0,
+               side: Optional[ChainSideShape] = None) -> Optional[ChainPlan]:
+    """The launch of the chain entry point ``kind`` (one of CHAIN_KINDS) for operands of this shape, under the environment switches of this
+    process (``ANEMOI_CHAIN_ROWS``).  Host-only: nothing is launched and no GPU is needed.  None where the entry point returns
+    unsupported; ValueError where it returns invalid.  A pure function of its arguments and of process constants: memoised, so that the
+    per-forward callers pay a dictionary lookup."""
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}[dtype]
+    sd = side or ChainSideShape(0, 0, 0)
+    if side is not None:
+        first_panel, panels = sd.first_panel, sd.panels
+    q = _lib.ChainProblem(CHAIN_KINDS.index(kind), n_rows, in_features, hidden, q_out, rows_per_tile, code, int(timeline), first_panel, panels,
+                          sd.rows, sd.in_features, sd.q_out, sd.rows_per_tile, sd.cap)
+    out = _lib.ChainPlan()
+    rc = _lib.load().anemoi_chain_plan(q, out)
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "chain_plan")
+    f = {name: getattr(out, name) for name, _ in out._fields_}
+    return ChainPlan(**{**f, "kernel": CHAIN_KERNELS[out.kernel], "side_pipelined": bool(out.side_pipelined), "pipelined": bool(out.pipelined)})
+
+
+def _plans(kind: str, x: Tensor, **shape) -> bool:
+    """The entry point ``kind`` takes rows like ``x`` (16-bit, on the GPU) in this shape: its plan exists."""
+    if not (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16)):
+        return False
+    try:
+        return chain_plan(kind, x.shape[0], dtype=x.dtype, **shape) is not None
+    except ValueError:
+        return False
+
+
+def _check_chain_images(who: str, dt: torch.dtype, images, vec: Tensor, vec_numel: int, vec_what: str) -> None:
+    """The fragment-major weight images (name, tensor or None, elements) and the per-column vector of a chain launch."""
+    for name, w, numel in images:
+        if w is None and numel == 0:
+            continue
+        if w is None or w.dim() != 1 or w.numel() != numel or w.dtype != dt or not w.is_contiguous():
+            raise ValueError(f"{who}: {name} must be the contiguous fragment-major image ({numel} x {dt}) made by pack_weight_frag")
+    if vec.dim() != 1 or vec.numel() != vec_numel or vec.dtype != dt or not vec.is_contiguous():
+        raise ValueError(f"{who}: vec must be contiguous [{vec_numel}] {dt} = {vec_what}")
+
 
 def pack_weight_frag(weight: Tensor) -> Tensor:
     """Fragment-major image of a Linear weight [O, K] (O % 64 == 0, K % 32 == 0) for the chain kernels: one contiguous KiB per
@@ -1106,6 +1192,8 @@ def pack_weight_frag(weight: Tensor) -> Tensor:
 
 
 def gt_layer_chain_supported(x: Tensor, hidden: int, q_out: int = 0) -> bool:
+    """The experiments build's first chain kernel (tools/experiments_ops.gt_layer_chain): it keeps no vectors in LDS, so neither width has
+    a limit, and its entry point has no kind in csrc/chain_plan.h."""
     return (x.is_cuda and x.dim() == 2 and x.shape[1] == CHAIN_CHANNELS and x.dtype in (torch.bfloat16, torch.float16)
             and hidden > 0 and hidden % CHAIN_CHANNELS == 0 and q_out % CHAIN_CHANNELS == 0)
 
@@ -1116,9 +1204,6 @@ class _Chain2Args(_lib.C.Structure):
                 ("wq", _p), ("q_out_features", _i32), ("vec", _p), ("ln1_eps", _f), ("lnq_eps", _f), ("extra", _p), ("ld_extra", _i64),
                 ("x_out", _p), ("ld_out", _i64), ("q_out", _p), ("ld_q", _i64), ("n_rows", _i32), ("channels", _i32),
                 ("rows_per_tile", _i32), ("timeline", _p)]
-
-
-CHAIN2_VEC_MAX = 6144  # elements of [b_p | d1 | b_2 | dq] the kernel keeps in LDS (csrc/gt_chain2.hip)
 
 
 def fold_layer_norm(weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Optional[Tensor]) -> tuple[Tensor, Tensor]:
@@ -1133,8 +1218,7 @@ def fold_layer_norm(weight: Tensor, bias: Optional[Tensor], gamma: Tensor, beta:
 
 def gt_layer_chain2_supported(x: Tensor, hidden: int, q_out: int = 0) -> bool:
     """``q_out``: a multiple of 512, or a NARROW trailing projection of 128, 256 or 384 columns (the decoder's node_data_extractor)."""
-    narrow = 0 < q_out < CHAIN_CHANNELS and q_out % 128 == 0
-    return gt_layer_chain_supported(x, hidden, 0 if narrow else q_out) and 2 * CHAIN_CHANNELS + hidden + q_out <= CHAIN2_VEC_MAX
+    return x.dim() == 2 and x.shape[1] == CHAIN_CHANNELS and _plans("block_tail", x, hidden=hidden, q_out=q_out)
 
 
 def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Tensor, vec: Tensor, hidden: int, ln1_eps: float, *,
@@ -1157,19 +1241,14 @@ def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Te
     dt = attn.dtype
     if D != CHAIN_CHANNELS or dt not in (torch.bfloat16, torch.float16):
         raise NotImplementedError(f"gt_layer_chain2: {D} channels / {dt} (built for {CHAIN_CHANNELS} channels, 16-bit dtypes)")
-    if 2 * D + hidden + q_out_features > CHAIN2_VEC_MAX:
+    if chain_plan("block_tail", N, hidden=hidden, q_out=q_out_features, rows_per_tile=int(rows_per_tile), dtype=dt, timeline=timeline is not None) is None:
         raise NotImplementedError(f"gt_layer_chain2: hidden={hidden} + q_out={q_out_features} exceed the kernel's LDS vector region")
     if tuple(x_res.shape) != (N, D) or (extra is not None and tuple(extra.shape) != (N, D)):
         raise ValueError("gt_layer_chain2: attn, x_res and extra must have the same [N, channels] shape")
     if extra is not None and not want_x_out:
         raise ValueError("gt_layer_chain2: a second residual needs x_out")
-    for name, w, numel in (("wp", wp, D * D), ("w1g", w1g, hidden * D), ("w2", w2, D * hidden), ("wqg", wqg, q_out_features * D)):
-        if w is None and numel == 0:
-            continue
-        if w is None or w.dim() != 1 or w.numel() != numel or w.dtype != dt or not w.is_contiguous():
-            raise ValueError(f"gt_layer_chain2: {name} must be the contiguous fragment-major image ({numel} x {dt}) made by pack_weight_frag")
-    if vec.dim() != 1 or vec.numel() != 2 * D + hidden + q_out_features or vec.dtype != dt or not vec.is_contiguous():
-        raise ValueError(f"gt_layer_chain2: vec must be contiguous [{2 * D + hidden + q_out_features}] {dt} = cat[bp, d1, b2, dq]")
+    _check_chain_images("gt_layer_chain2", dt, (("wp", wp, D * D), ("w1g", w1g, hidden * D), ("w2", w2, D * hidden), ("wqg", wqg, q_out_features * D)),
+                        vec, 2 * D + hidden + q_out_features, "cat[bp, d1, b2, dq]")
     if not want_x_out and not q_out_features:
         raise ValueError("gt_layer_chain2: want_x_out=False needs a trailing projection")
     x_out = torch.empty((N, D), dtype=dt, device=attn.device) if want_x_out else None
@@ -1193,21 +1272,15 @@ def gt_layer_chain2(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Te
     return x_out if q_out is None else (x_out, q_out)
 
 
-CHAIN_PANEL_ROWS = 48  # rows of an LDS panel of the chain kernels
-CHIP_CUS = 256         # MI355X: one chain workgroup per compute unit
-
-
 def chain_idle_cus(n_rows: int) -> int:
-    """Compute units a ``gt_layer_chain2`` launch over ``n_rows`` rows leaves idle in every round of panels (csrc/chain2_side_plan.h: one
-    workgroup per 48-row panel up to 256; beyond, as many as make the rounds even)."""
-    tiles = -(-n_rows // CHAIN_PANEL_ROWS)
-    if tiles <= 0:
-        return 0
-    grid = tiles
-    if tiles > CHIP_CUS:
-        rounds = -(-tiles // CHIP_CUS)
-        grid = -(-tiles // rounds)
-    return CHIP_CUS - min(grid, CHIP_CUS)
+    """Compute units a ``gt_layer_chain2`` launch over ``n_rows`` rows leaves idle in every round of panels (the plan's: one workgroup per
+    panel up to the chip; beyond, as many as make the rounds even)."""
+    return chain_plan("block_tail", n_rows, hidden=CHAIN_CHANNELS).idle_cus if n_rows > 0 else 0
+
+
+def row_chain_panels(n_rows: int, in_features: int, q_out: int) -> int:
+    """Panels of the row-chain job ``gt_row_chain(x [n_rows, in_features], ..., q_out)`` (the plan's)."""
+    return chain_plan("row_chain", n_rows, in_features=in_features, q_out=q_out).panels
 
 
 @dataclass
@@ -1229,7 +1302,7 @@ class ChainSide:
 
     @property
     def n_panels(self) -> int:
-        return -(-self.x.shape[0] // CHAIN_PANEL_ROWS)
+        return row_chain_panels(self.x.shape[0], self.x.shape[1], self.q_out_features)
 
 
 class _ClusterChainArgs(_lib.C.Structure):
@@ -1261,7 +1334,7 @@ def _cluster_workspace(device) -> Tensor:
 
 
 def gt_cluster_chain_supported(x: Tensor, hidden: int, q_out: int = 0) -> bool:
-    return gt_layer_chain_supported(x, hidden, q_out) and hidden == 4 * CHAIN_CHANNELS and q_out <= 4 * CHAIN_CHANNELS
+    return x.dim() == 2 and x.shape[1] == CHAIN_CHANNELS and _plans("cluster_tail", x, hidden=hidden, q_out=q_out)
 
 
 def gt_cluster_chain(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: Tensor, vec: Tensor, hidden: int, ln1_eps: float, *,
@@ -1281,13 +1354,8 @@ def gt_cluster_chain(attn: Tensor, x_res: Tensor, wp: Tensor, w1g: Tensor, w2: T
         raise ValueError("gt_cluster_chain: attn, x_res, extra and ln_out must have the same [N, channels] shape")
     if extra is not None and (q_out_features or ln_out is not None):
         raise ValueError("gt_cluster_chain: a trailing projection / LayerNorm output and a second residual exclude each other")
-    for name, w, numel in (("wp", wp, D * D), ("w1g", w1g, hidden * D), ("w2", w2, D * hidden), ("wqg", wqg, q_out_features * D)):
-        if w is None and numel == 0:
-            continue
-        if w is None or w.dim() != 1 or w.numel() != numel or w.dtype != dt or not w.is_contiguous():
-            raise ValueError(f"gt_cluster_chain: {name} must be the contiguous fragment-major image ({numel} x {dt}) made by pack_weight_frag")
-    if vec.dim() != 1 or vec.numel() != 2 * D + hidden + q_out_features or vec.dtype != dt or not vec.is_contiguous():
-        raise ValueError(f"gt_cluster_chain: vec must be contiguous [{2 * D + hidden + q_out_features}] {dt} = cat[bp, d1, b2, dq]")
+    _check_chain_images("gt_cluster_chain", dt, (("wp", wp, D * D), ("w1g", w1g, hidden * D), ("w2", w2, D * hidden), ("wqg", wqg, q_out_features * D)),
+                        vec, 2 * D + hidden + q_out_features, "cat[bp, d1, b2, dq]")
     ws = _cluster_workspace(attn.device)
     x_out = torch.empty((N, D), dtype=dt, device=attn.device)
     q_cols = q_out_features if q_out2 is None else D * q_split
@@ -1318,8 +1386,7 @@ def pack_embedding_frag(weight: Tensor) -> Tensor:
 
 
 def gt_row_chain_supported(x: Tensor, q_out: int) -> bool:
-    return (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and 0 < x.shape[1] <= CHAIN_CHANNELS and x.shape[1] % 8 == 0
-            and x.stride(1) == 1 and x.stride(0) % 8 == 0 and q_out > 0 and q_out % CHAIN_CHANNELS == 0 and q_out <= 4 * CHAIN_CHANNELS)
+    return x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and _plans("row_chain", x, in_features=x.shape[1], q_out=q_out)
 
 
 def gt_row_chain(x: Tensor, we: Tensor, wqg: Tensor, vec: Tensor, q_out_features: int, ln_eps: float, *, want_x_out: bool = True,
@@ -1375,9 +1442,6 @@ class _EmbedFoldArgs(_lib.C.Structure):
                 ("q_out", _p), ("ld_q", _i64), ("n_rows", _i32), ("channels", _i32)]
 
 
-EMBED_FOLD_MAX_IN = 256  # widest input row of ``gt_embed_fold`` (csrc/gt_embed_fold.hip)
-
-
 def compose_embedding_projection(w_emb: Tensor, b_emb: Optional[Tensor], w_proj: Tensor, b_proj: Optional[Tensor], gamma: Tensor,
                                  beta: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor]:
     """The operands of ``gt_embed_fold`` for ``Linear(w_emb, b_emb) -> LayerNorm(gamma, beta) -> Linear(w_proj, b_proj)``.  With
@@ -1400,9 +1464,7 @@ def compose_embedding_projection(w_emb: Tensor, b_emb: Optional[Tensor], w_proj:
 
 
 def gt_embed_fold_supported(x: Tensor, q_out: int) -> bool:
-    return (x.is_cuda and x.dim() == 2 and x.dtype in (torch.bfloat16, torch.float16) and 0 < x.shape[1] <= EMBED_FOLD_MAX_IN
-            and x.shape[1] % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and q_out > 0 and q_out % CHAIN_CHANNELS == 0
-            and q_out <= 4 * CHAIN_CHANNELS)
+    return x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and _plans("embed_fold", x, in_features=x.shape[1], q_out=q_out)
 
 
 def gt_embed_fold(x: Tensor, we: Tensor, wc: Tensor, vec: Tensor, q_out_features: int, ln_eps: float) -> Optional[Tensor]:

@@ -580,6 +580,31 @@ int anemoi_gt_embed_fold_fwd(const anemoi_gt_embed_fold_args_t* args, anemoi_dty
 int anemoi_gt_chain2_side_fwd(const anemoi_gt_chain2_args_t* args, const anemoi_gt_rowchain_args_t* side, int32_t side_first_panel,
                               int32_t side_panels, int32_t side_blocks, anemoi_dtype_t dtype, void* stream);
 
+/* Which kernel a chain entry point launches for a shape, on how many rows per panel, workgroups and bytes of LDS: the decision of
+ * csrc/chain_plan.h, asked without launching anything.  HOST-ONLY: no HIP call, no device needed.  kind: 0 anemoi_gt_chain2_fwd,
+ * 1 anemoi_gt_chain2_side_fwd, 2 anemoi_gt_cluster_chain_fwd, 3 anemoi_gt_rowchain_fwd, 4 anemoi_gt_rowchain_panels_fwd,
+ * 5 anemoi_gt_embed_fold_fwd, 6 anemoi_gnn_edge_chain_fwd, 7 anemoi_gnn_mlp_chain_fwd, 8 anemoi_gnn_node_chain_fwd (and its segsum
+ * form).  The problem holds the shape fields of that entry point's arguments (the others are not read): first_panel / panels are the
+ * range of kind 4 and the side job's riding panels of kind 1, whose side job is side_* with side_cap = side_blocks.  Returns what the
+ * entry point returns for the shape with well-formed operands (null, alignment and leading-dimension checks look at pointers and stay
+ * in the entry points): ANEMOI_OK, ANEMOI_E_UNSUPPORTED or ANEMOI_E_INVALID; `out` is written for ANEMOI_OK only.  kernel: 0 nothing
+ * to launch, 1 gt_chain2 on every CU, 2 below the chip, 3 / 4 their instrumented forms, 5 with riders, 6 cluster, 7 row chain
+ * single-panel, 8 pipelined, 9 embed fold, 10 / 11 / 12 GraphConv edge / MLP / node.  rounds: panels of the busiest workgroup;
+ * idle_cus: CUs without a workgroup in every round.  Kind 1: host_grid tail workgroups, riders behind them on panels [first, end) of the
+ * side job, side_pipelined its schedule.  Kinds 3, 4: job_panels and pipelined describe the WHOLE job, n_rows rows from row_begin are
+ * the launch's.  Under the environment switches of this process (ANEMOI_CHAIN_ROWS; the experiments build's grid switches). */
+typedef struct anemoi_chain_problem {
+  int32_t kind, n_rows, in_features, hidden, q_out_features, rows_per_tile, dtype, timeline, first_panel, panels;
+  int32_t side_rows, side_in_features, side_q_out_features, side_rows_per_tile, side_cap;
+} anemoi_chain_problem_t;
+typedef struct anemoi_chain_plan {
+  int32_t kernel, rows_per_panel, panels, grid, threads, lds_bytes, rounds, idle_cus;
+  int32_t host_grid, riders, first, end, side_pipelined;
+  int32_t job_panels, pipelined, n_rows;
+  int64_t row_begin;
+} anemoi_chain_plan_t;
+int anemoi_chain_plan(const anemoi_chain_problem_t* problem, anemoi_chain_plan_t* out);
+
 /* ---- cluster chain: the block tail for FEW rows (round 6; csrc/gt_cluster_chain.hip) ----------------------------------------------
  * What anemoi_gt_chain2_fwd computes (same operands, same folded LayerNorms, same vec layout with hidden = 2048:
  * [b_p 512 | d1 2048 | b_2 512 | dq q_out_features]), organised for block tails of a few thousand rows - a rank's share of a sharded

@@ -70,8 +70,8 @@ def present_rule(want, tol=2.5e-2):
 
 
 def panel_split(n, cap):
-    """MIRROR of chain_rows_per_tile + the grid rule of the three launches in csrc/gnn_chain.hip (cap = 64: edge and MLP chain,
-    48: node chain; no ANEMOI_CHAIN_ROWS / ANEMOI_GNN_NODE_ROWS).  -> (rows_per_tile, tiles, last, grid, panels_per_workgroup):
+    """The tests' own restatement of gnn_rows_per_tile + the grid rule of the three GraphConv launches in csrc/chain_plan.h (cap = 64: edge
+    and MLP chain, 48: node chain; no ANEMOI_CHAIN_ROWS / ANEMOI_GNN_NODE_ROWS) - tests/test_chain_plan_cpu.py holds the plan to it.  -> (rows_per_tile, tiles, last, grid, panels_per_workgroup):
     ``last`` = rows of the last tile, ``panels_per_workgroup`` = what the busiest workgroup walks; tiles - (that - 1) * grid
     workgroups walk that many, the others one fewer."""
     rounds = (n + 256 * cap - 1) // (256 * cap)

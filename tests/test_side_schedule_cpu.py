@@ -7,7 +7,7 @@ import torch
 
 
 def _panels_per_round(host_rows):
-    """csrc/chain2_side_plan.h chain2_grid, restated: workgroups of a tail over host_rows rows"""
+    """csrc/chain_plan.h even_rounds_grid, restated: workgroups of a tail over host_rows rows"""
     tiles = -(-host_rows // 48)
     if tiles <= 256:
         return tiles

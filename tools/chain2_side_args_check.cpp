@@ -1,120 +1,80 @@
 // Host-only check of anemoi_gt_chain2_side_fwd's argument validation and launch plan: the entry point of csrc/gt_chain2.hip compiled for the
 // HOST (csrc/gt_chain2_side.hip) with its kernel launches replaced by a recorder, driven over valid and invalid argument blocks.  Nothing is launched; no GPU needed.
+// (The other chain entry points: tools/chain_args_check.cpp; --record as there.)
 //
 //   hipcc --cuda-host-only -x hip -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 //         -I include -I anemoi_core_amd/csrc tools/chain2_side_args_check.cpp -o /tmp/chain2_side_args_check && /tmp/chain2_side_args_check
-#include <hip/hip_runtime.h>
-
-#include <stdarg.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
-#include "common.h"
-
-namespace anemoi {
-static char g_err[512];
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-}
-int check_launch(const char*) { return ANEMOI_OK; }
-}  // namespace anemoi
-
-struct Record {
-  int grid = 0, block = 0, smem = 0;
-  bool side = false;
-  int pipe = -1, host_grid = 0, first = 0, end = 0, riders = 0, host_tiles = 0, side_tiles = 0;
-};
-static std::vector<Record> g_launches;
-
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(kernel, grid, block, smem, stream, arg) record_launch((grid), (block), (smem), (arg))
-#define hipFuncSetAttribute(...) hipSuccess
+#include "chain_check_common.h"
 
 #include "chain2_core.h"
 #include "rowchain_core.h"
 namespace anemoi {
 struct Chain2Args;
 struct Chain2SideArgs;
-static void record_launch(dim3 grid, dim3 block, int smem, const Chain2SideArgs& a);
+static void record_launch(const char* kernel, dim3 grid, dim3 block, int smem, const Chain2SideArgs& a);
 }  // namespace anemoi
 
 #include "gt_chain2_side.hip"
 
 // (the tail alone is the other translation unit's entry point: recorded as a delegation)
 static int g_delegated = 0;
-extern "C" int anemoi_gt_chain_rows_per_tile(int32_t) { return 48; }
 extern "C" int anemoi_gt_chain2_fwd(const anemoi_gt_chain2_args_t*, anemoi_dtype_t, void*) {
   ++g_delegated;
   return ANEMOI_OK;
 }
 
 namespace anemoi {
-static void record_launch(dim3 grid, dim3 block, int smem, const Chain2SideArgs& a) {
+static void record_launch(const char* kernel, dim3 grid, dim3 block, int smem, const Chain2SideArgs& a) {
   Record r;
-  r.grid = (int)grid.x; r.block = (int)block.x; r.smem = smem; r.side = true; r.host_tiles = a.n_tiles;
+  r.kernel = kernel_name(kernel);
+  r.grid = (int)grid.x; r.block = (int)block.x; r.smem = smem; r.n_rows = a.n_rows; r.rows_per_tile = a.rows_per_tile; r.n_tiles = a.n_tiles;
   r.host_grid = a.host_grid; r.first = a.side_first; r.end = a.side_end; r.riders = a.side_blocks; r.pipe = a.side_pipe; r.side_tiles = a.side.n_tiles;
   g_launches.push_back(r);
 }
 }  // namespace anemoi
 
-static int g_fail = 0, g_cases = 0;
-#define EXPECT(cond, ...)                                   \
-  do {                                                      \
-    ++g_cases;                                              \
-    if (!(cond)) {                                          \
-      ++g_fail;                                             \
-      printf("FAIL line %d: %s  ", __LINE__, #cond);        \
-      printf(__VA_ARGS__);                                  \
-      printf("  [%s]\n", anemoi::g_err);                    \
-    }                                                       \
-  } while (0)
-
-static void* P(uintptr_t v) { return reinterpret_cast<void*>(v); }  // aligned dummy addresses: never dereferenced on the host
-
-static anemoi_gt_chain2_args_t host_block(int n_rows, int q_out) {
-  anemoi_gt_chain2_args_t a;
-  memset(&a, 0, sizeof a);
-  a.attn = P(0x10000); a.ld_attn = 512; a.x_res = P(0x20000); a.ld_x = 512;
-  a.wp = P(0x30000); a.w1 = P(0x40000); a.hidden = 2048; a.w2 = P(0x50000);
-  a.wq = q_out ? P(0x60000) : nullptr; a.q_out_features = q_out; a.vec = P(0x70000);
-  a.ln1_eps = a.lnq_eps = 1e-5f;
-  a.x_out = P(0x80000); a.ld_out = 512; a.q_out = q_out ? P(0x90000) : nullptr; a.ld_q = q_out;
-  a.n_rows = n_rows; a.channels = 512;
-  return a;
-}
-static anemoi_gt_rowchain_args_t side_block(int n_rows, int k_in, int q_out) {
-  anemoi_gt_rowchain_args_t s;
-  memset(&s, 0, sizeof s);
-  s.x = P(0xa0000); s.ld_x = k_in; s.in_features = k_in; s.we = P(0xb0000); s.wq = P(0xc0000); s.q_out_features = q_out;
-  s.vec = P(0xd0000); s.ln_eps = 1e-5f; s.x_out = P(0xe0000); s.ld_out = 512; s.q_out = P(0xf0000); s.ld_q = q_out;
-  s.n_rows = n_rows; s.channels = 512;
-  return s;
+static bool g_record = false;
+static int side_call(anemoi_gt_chain2_args_t* h, anemoi_gt_rowchain_args_t* s, int first, int count, int cap, anemoi_dtype_t dt) {
+  g_launches.clear();
+  g_delegated = 0;
+  anemoi::g_err[0] = 0;
+  const int rc = anemoi_gt_chain2_side_fwd(h, s, first, count, cap, dt, nullptr);
+  // (the table describes shapes: calls with a faulty pointer, leading dimension or channel count are checked below and not printed)
+  const bool shapes_only = h != nullptr && s != nullptr && h->attn == P(0x10000) && h->ld_q == h->q_out_features && h->channels == 512 && s->x == P(kRowChainX) &&
+                           s->q_out != nullptr && s->ld_q == s->q_out_features && s->channels == 512;
+  if (g_record && shapes_only)
+    print_row("block_tail_side", {h->n_rows, h->hidden, h->q_out_features, h->rows_per_tile, s->n_rows, s->in_features, s->q_out_features, s->rows_per_tile,
+                                  first, count, cap, dt},
+              rc, g_launches.empty() ? nullptr : &g_launches[0], g_delegated == 1);
+  return rc;
 }
 
-int main() {
+// the workgroups of a tail of `tiles` panels, restated: one per panel up to the chip, beyond as many as make the rounds even
+static int tail_grid(int tiles) {
+  if (tiles <= 256) return tiles;
+  const int rounds = (tiles + 255) / 256;
+  return (tiles + rounds - 1) / rounds;
+}
+
+int main(int argc, char** argv) {
   using namespace anemoi;
+  g_record = argc > 1 && strcmp(argv[1], "--record") == 0;
   const int smem_side = kChain2SideSmem;
   // ---- valid blocks: the recorded launch is the plan
   for (int host_rows : {1, 47, 48, 149, 10242, 12240 - 48, 12240, 12288 - 1, 12288, 12289, 12336, 24576, 24577, 40962, 542080}) {
     for (int side_rows : {1, 48, 347, 40320}) {
       const int tiles = (host_rows + 47) / 48, side_tiles = (side_rows + 47) / 48;
-      const int grid = chain2_grid(tiles);
+      const int grid = tail_grid(tiles);
       for (int first : {0, 3, side_tiles - 1, side_tiles}) {
         if (first < 0 || first > side_tiles) continue;
         for (int count : {0, 1, 4, side_tiles - first}) {
           if (count < 0 || first + count > side_tiles) continue;
           for (int cap : {0, 1, 2, 300}) {
             for (anemoi_dtype_t dt : {ANEMOI_BF16, ANEMOI_F16}) {
+              if (dt == ANEMOI_F16 && (cap != 0 || first != 0)) continue;  // (the dtype picks the instantiation and nothing else)
               auto h = host_block(host_rows, 2048);
               auto s = side_block(side_rows, 192, 1024);
-              g_launches.clear();
-              g_delegated = 0;
-              const int rc = anemoi_gt_chain2_side_fwd(&h, &s, first, count, cap, dt, nullptr);
+              const int rc = side_call(&h, &s, first, count, cap, dt);
               if (grid >= 256) {
                 EXPECT(rc == ANEMOI_E_UNSUPPORTED && g_launches.empty(), "host %d side %d rc %d launches %zu", host_rows, side_rows, rc, g_launches.size());
                 continue;
@@ -129,9 +89,9 @@ int main() {
               int riders = 256 - grid;
               if (cap > 0 && cap < riders) riders = cap;
               if (count < riders) riders = count;
-              EXPECT(r.side && r.host_grid == grid && r.riders == riders && r.grid == grid + riders && r.grid <= 256 && r.block == 512 && r.smem == smem_side,
+              EXPECT(r.kernel == "gt_chain2_kernel<false,true,true>" && r.host_grid == grid && r.riders == riders && r.grid == grid + riders && r.grid <= 256 && r.block == 512 && r.smem == smem_side,
                      "grid %d host_grid %d riders %d (want %d + %d)", r.grid, r.host_grid, r.riders, grid, riders);
-              EXPECT(r.first == first && r.end == first + count && r.end <= r.side_tiles && r.side_tiles == side_tiles && r.host_tiles == tiles && r.pipe == (side_tiles > 256 ? 1 : 0),
+              EXPECT(r.first == first && r.end == first + count && r.end <= r.side_tiles && r.side_tiles == side_tiles && r.n_tiles == tiles && r.pipe == (side_tiles > 256 ? 1 : 0),
                      "panels [%d, %d) of %d", r.first, r.end, r.side_tiles);
             }
           }
@@ -139,12 +99,17 @@ int main() {
       }
     }
   }
+  for (int k_in : {256, 264})  // (264: the first width whose riders are not pipelined)
+    for (int host_rows : {149, 10242}) {
+      auto h = host_block(host_rows, 2048);
+      auto s = side_block(40320, k_in, 1024);
+      const int rc = side_call(&h, &s, 0, 4, 0, ANEMOI_BF16);
+      EXPECT(rc == ANEMOI_OK && g_launches.size() == 1 && g_launches[0].pipe == (k_in <= 256), "side in_features %d: rc %d", k_in, rc);
+    }
   // ---- invalid blocks: the code, and nothing launched
   auto expect_refused = [&](const char* what, int want, anemoi_gt_chain2_args_t* h, anemoi_gt_rowchain_args_t* s, int first, int count, int cap,
                             anemoi_dtype_t dt = ANEMOI_BF16, bool with_text = true) {
-    g_launches.clear();
-    g_err[0] = 0;
-    const int rc = anemoi_gt_chain2_side_fwd(h, s, first, count, cap, dt, nullptr);
+    const int rc = side_call(h, s, first, count, cap, dt);
     EXPECT(rc == want && g_launches.empty() && (g_err[0] != 0 || !with_text), "%s: rc %d (want %d), launches %zu", what, rc, want, g_launches.size());
   };
   {
@@ -181,7 +146,7 @@ int main() {
     expect_refused("side in_features > 512", ANEMOI_E_UNSUPPORTED, &h, &t, 0, 8, 0);
     t = s; t.q_out_features = 2560; t.ld_q = 2560;
     expect_refused("side q_out", ANEMOI_E_UNSUPPORTED, &h, &t, 0, 8, 0);
-    t = s; t.x = P(0xa0004);
+    t = s; t.x = P(kRowChainX + 4);
     expect_refused("side alignment", ANEMOI_E_UNSUPPORTED, &h, &t, 0, 8, 0);
     t = s; t.q_out = nullptr;
     expect_refused("side null output", ANEMOI_E_UNSUPPORTED, &h, &t, 0, 8, 0);
@@ -192,6 +157,6 @@ int main() {
     t = s; t.rows_per_tile = 64;
     expect_refused("side rows_per_tile", ANEMOI_E_UNSUPPORTED, &h, &t, 0, 8, 0);
   }
-  printf("chain2 side entry point: %d checks, %d failures\n", g_cases, g_fail);
+  if (!g_record) printf("chain2 side entry point: %d checks, %d failures\n", g_cases, g_fail);
   return g_fail ? 1 : 0;
 }
