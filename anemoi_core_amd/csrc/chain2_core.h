@@ -41,7 +41,7 @@ __device__ __forceinline__ void gemm128(const unsigned char* abuf, int lane, fra
 #pragma unroll
       for (int ni = 0; ni < 8; ++ni) {
 #pragma unroll
-        for (int mi = 0; mi < 3; ++mi) acc[mi][ni] = cmfma<T>(ring[j][ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
+        for (int mi = 0; mi < 3; ++mi) acc[mi][ni] = mfma16<T>(ring[j][ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
         ring[j][ni] = *reinterpret_cast<gfrag_t>((ni < 4 ? g0 : g1) + loff + (ni & 3) * 1024);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -83,7 +83,7 @@ __device__ __forceinline__ void gemm64(const unsigned char* abuf, int lane, frag
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
 #pragma unroll
-        for (int mi = 0; mi < 3; ++mi) acc[mi][ni] = cmfma<T>(ring[j & 1][(j >> 1) * 4 + ni], fa[mi], acc[mi][ni]);
+        for (int mi = 0; mi < 3; ++mi) acc[mi][ni] = mfma16<T>(ring[j & 1][(j >> 1) * 4 + ni], fa[mi], acc[mi][ni]);
         ring[j & 1][(j >> 1) * 4 + ni] = *reinterpret_cast<gfrag_t>(g0 + loff + ni * 1024);
         __builtin_amdgcn_sched_barrier(0);
       }

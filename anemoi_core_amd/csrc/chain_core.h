@@ -6,24 +6,9 @@
 // coordinates in it, the LayerNorm statistics and the epilogue forms of both wave layouts.
 #pragma once
 #include "chain_host.h"
+#include "mma.h"
 
 namespace anemoi {
-
-using frag8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <typename T>
-__device__ __forceinline__ f32x4 cmfma(frag8 a, frag8 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 cmfma<bf16_t>(frag8 a, frag8 b, f32x4 c) {
-  using bf8 = __attribute__((ext_vector_type(8))) __bf16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 cmfma<f16_t>(frag8 a, frag8 b, f32x4 c) {
-  using h8 = __attribute__((ext_vector_type(8))) _Float16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
 
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
@@ -128,7 +113,7 @@ __device__ __forceinline__ void gemm_seg(const unsigned char* abuf, int lane, fr
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = cmfma<T>(bq[j][ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<T>(bq[j][ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
       {
         const gptr_t pj = uniform_ptr(pfg + j * 4096);
 #pragma unroll

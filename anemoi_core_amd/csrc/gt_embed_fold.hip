@@ -67,7 +67,7 @@ __device__ __forceinline__ void embed_fold_gemm(const unsigned char* arow, int x
     for (int ni = 0; ni < 8; ++ni) {
 #pragma unroll
       for (int mi = 0; mi < kEfBands; ++mi) {
-        acc[mi][ni] = cmfma<T>(ring[ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
+        acc[mi][ni] = mfma16<T>(ring[ni], fa[mi], acc[mi][ni]);  // D^T: lane = row x, 4 consecutive columns
         if (ni == 7) fa[mi] = *reinterpret_cast<const frag8*>(arow + mi * 16 * kEfRowBytes + aoff);
       }
       ring[ni] = *reinterpret_cast<gfrag_t>((ni < 4 ? g0 : g1) + loff + (ni & 3) * 1024);

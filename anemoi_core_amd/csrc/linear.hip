@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "linear_plan.h"
+#include "mma.h"
 
 namespace anemoi {
 
@@ -150,26 +151,17 @@ __global__ __launch_bounds__(256) void linear_generic_kernel(LinArgs a) {
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int kTileBytes = BM * BK * 2;  // one operand tile (16 KiB)
 
-using frag8 = __attribute__((ext_vector_type(8))) short;  // 8 x 16-bit operand elements (4 VGPRs)
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(frag8 a, frag8 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<bf16_t>(frag8 a, frag8 b, f32x4 c) {
-  using bf8 = __attribute__((ext_vector_type(8))) __bf16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<f16_t>(frag8 a, frag8 b, f32x4 c) {
-  using h8 = __attribute__((ext_vector_type(8))) _Float16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
 
 // byte offset of (row, 16-byte slot) inside a [128][64] 16-bit tile with XOR-swizzled slots
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * (BK * 2) + ((slot ^ ((row >> 1) & 7)) << 4); }
+
+// XCD-aware bijective remap of a workgroup's tile id: workgroups dispatched to the same XCD (id % 8) get consecutive tile ids, so
+// the column tiles of a row panel run on one XCD and the A panel is fetched into one L2.
+__device__ __forceinline__ int xcd_tile(int id, int num_tiles) {
+  const int q = num_tiles >> 3, r = num_tiles & 7, xcd = id & 7, pos = id >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+}
 
 // Epilogue shared by the MFMA kernels.
 // acc[mi][ni][r] = out[m = m0 + wr*64 + mi*16 + (lane & 15)][n = n0 + wc*64 + ni*16 + (lane>>4)*4 + r].
@@ -239,12 +231,7 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(LinArgs a, int tile
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
 
-  // XCD-aware bijective remap: workgroups dispatched to the same XCD (id % 8) get consecutive tile ids.
-  int id = blockIdx.x;
-  {
-    const int q = num_tiles >> 3, r = num_tiles & 7, xcd = id & 7, pos = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int id = xcd_tile(blockIdx.x, num_tiles);
   const int m0 = (id / tiles_n) * BM, n0 = (id % tiles_n) * BN;
 
   const T* __restrict__ x = (const T*)a.x;
@@ -345,8 +332,47 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(LinArgs a, int tile
 //  * the epilogue is specialised at compile time (EPI flags): residual / gather rows are fetched up front, the
 //    accumulators go through a wave-private LDS band (swizzled, conflict-free) so that every global access of the
 //    epilogue is a whole 128-byte line.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
+
+// DMA ring addressing of the persistent and the big-tile kernel: where the 1-KiB pieces (8 rows x 64 elements) of the K-tile being
+// issued come from.  An address is a wave-uniform 64-bit base (operand + tile byte offset + K offset) plus a per-lane 32-bit byte
+// offset that is fixed for the tile; wave w owns pieces w kAPW .. + kAPW - 1 of A and w kWPW .. + kWPW - 1 of W.  The DMA writes
+// lane-linear, so the XOR slot swizzle of lds_off() is applied to the lane's SOURCE slot.  What is issued when, and every counted
+// wait, belongs to each kernel's schedule and stays there.
+// Outputs: the per-lane offsets a_voff / a2_voff / w_voff (relative to the tile's first row: they fit 32 bits, ring_eligible) and the
+// tile byte offsets x_toff / x2_toff / w_toff (wave-uniform, 64-bit).  k_off: byte offset of a split-K share inside the operand rows
+// (x and w; x2 takes no split).  CLAMP_W: the W pieces do not divide evenly over the waves and a wave's surplus ones re-fetch the last
+// piece (they land in the kernel's dummy KiB).  The kernels keep these in plain local arrays: inside a struct they went to scratch.
+template <int kAPieces, int kWPieces, bool CLAMP_W, int kAPW, int kWPW>
+__device__ __forceinline__ void ring_tile_offsets(const LinArgs& a, int m0, int n0, int64_t k_off, int wave, int lane,
+                                                  uint32_t (&a_voff)[kAPW], uint32_t (&a2_voff)[kAPW], uint32_t (&w_voff)[kWPW],
+                                                  int64_t& x_toff, int64_t& x2_toff, int64_t& w_toff) {
+  x_toff = (int64_t)m0 * a.ldx * 2 + k_off;
+  x2_toff = (int64_t)m0 * a.ldx2 * 2;
+  w_toff = (int64_t)n0 * a.ldw * 2 + k_off;
+#pragma unroll
+  for (int i = 0; i < kAPW; ++i) {
+    const int row = min(wave * kAPW + i, kAPieces - 1) * 8 + (lane >> 3);
+    const int slot = (lane & 7) ^ ((row >> 1) & 7);
+    const int m = min(m0 + row, a.n_rows - 1);  // rows past the end are computed but never stored
+    a_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx + slot * 8) * 2);
+    a2_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx2 + slot * 8) * 2);
+  }
+#pragma unroll
+  for (int i = 0; i < kWPW; ++i) {
+    const int row = (CLAMP_W ? min(wave * kWPW + i, kWPieces - 1) : wave * kWPW + i) * 8 + (lane >> 3);
+    const int slot = (lane & 7) ^ ((row >> 1) & 7);
+    const int n = min(n0 + row, a.O - 1);
+    w_voff[i] = (uint32_t)(((int64_t)(n - n0) * a.ldw + slot * 8) * 2);
+  }
+}
+// the K-tile after the one just issued: global index, index within its tile, tile
+__device__ __forceinline__ void ring_advance(int& ig, int& ikt, int& ij, int nk) {
+  ++ig;
+  if (++ikt == nk) {
+    ikt = 0;
+    ++ij;
+  }
+}
 
 // acc[mi][ni][r] = out[m0 + wr*64 + mi*16 + (lane & 15)][n0 + wc*64 + ni*16 + (lane>>4)*4 + r]
 // epi: this wave's 4 KiB LDS slice (16 rows x 256 B); one 16-row band (mi) at a time.  The band is written in the MFMA
@@ -356,9 +382,40 @@ typedef __attribute__((address_space(1))) const void gbl_void_t;
 // (guide T21).  Interior tiles issue exactly kEpiStores = 8 stores per wave.
 constexpr int kEpiStores = 8;
 
-// LayerNorm fold, small-tile kernels: mean / rstd of one row straight from the producer's strip sums (the big-tile kernel
+// LayerNorm fold: sum and sum of squares of one row from the strip sums its producer left, st = [strips][2].  THE summation order
+// of the fold - every consumer goes through here (or, a strip per lane, through group_sum<8>), so the statistics are bit-identical
+// whichever kernel applies them.  D = 512: four 16-byte loads, same order as the generic loop.
+__device__ __forceinline__ void ln_strip_sums(const float* st, int strips, float& s1, float& s2) {
+  s1 = 0.f;
+  s2 = 0.f;
+  if (strips == 8) {
+    f32x4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = reinterpret_cast<const f32x4*>(st)[q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      s1 += v[q][0];
+      s2 += v[q][1];
+      s1 += v[q][2];
+      s2 += v[q][3];
+    }
+  } else {
+    for (int q = 0; q < strips; ++q) {
+      s1 += st[2 * q];
+      s2 += st[2 * q + 1];
+    }
+  }
+}
+
+// {mean, rstd} of a row of ln_D elements from its sum and sum of squares
+__device__ __forceinline__ f32x2 mean_rstd(float s1, float s2, int ln_D, float eps) {
+  const float inv = 1.0f / (float)ln_D, mu = s1 * inv;
+  return f32x2{mu, rsqrtf(fmaxf(s2 * inv - mu * mu, 0.f) + eps)};
+}
+
+// LayerNorm fold, small-tile kernels: {mean, rstd} of one row straight from the producer's strip sums (the big-tile kernel
 // stages them in LDS once per tile; with 64-row tiles on a few thousand rows the 8 lanes that share a row re-read its 64
-// bytes from L1 instead).  Same summation order as the LDS variant: bit-identical statistics.
+// bytes from L1 instead).
 template <typename T>
 __device__ __forceinline__ void ln_row_stats(const LinArgs& a, int m, int cp, float& mu, float& rs) {
   if (m >= a.n_rows + a.tail_rows) {  // a row of a ragged last tile that does not exist: never stored, nothing to fetch for it
@@ -366,7 +423,6 @@ __device__ __forceinline__ void ln_row_stats(const LinArgs& a, int m, int cp, fl
     rs = 1.f;
     return;
   }
-  const float* st = a.stats_in + (int64_t)m * a.ln_strips * 2;
   float s1 = 0.f, s2 = 0.f;
   if (m >= a.ln_tail_begin) {
     // a producer's peeled tail row: sums of the stored row itself, shared out over the 8 lanes that hold the row in the epilogue
@@ -395,26 +451,12 @@ __device__ __forceinline__ void ln_row_stats(const LinArgs& a, int m, int cp, fl
     }
     s1 = group_sum<8>(s1);
     s2 = group_sum<8>(s2);
-  } else if (a.ln_strips == 8) {
-    f32x4 v[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = reinterpret_cast<const f32x4*>(st)[q];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      s1 += v[q][0];
-      s2 += v[q][1];
-      s1 += v[q][2];
-      s2 += v[q][3];
-    }
   } else {
-    for (int q = 0; q < a.ln_strips; ++q) {
-      s1 += st[2 * q];
-      s2 += st[2 * q + 1];
-    }
+    ln_strip_sums(a.stats_in + (int64_t)m * a.ln_strips * 2, a.ln_strips, s1, s2);
   }
-  const float inv = 1.0f / (float)a.ln_D;
-  mu = s1 * inv;
-  rs = rsqrtf(fmaxf(s2 * inv - mu * mu, 0.f) + a.ln_eps);
+  const f32x2 mr = mean_rstd(s1, s2, a.ln_D, a.ln_eps);
+  mu = mr[0];
+  rs = mr[1];
 }
 
 // The gather-add epilogue's row indices for one lane (rows mi * 16 + it * 8 of its wave's slab), loaded by the big-tile kernel during
@@ -543,16 +585,13 @@ __device__ __forceinline__ void mfma_epilogue_fast(const LinArgs& a, f32x4 (&acc
           mr = *reinterpret_cast<const f32x2*>(ln_rows + 2 * (wr * (16 * MI) + (lane >> 3) + mi * 16 + it * 8));
         } else {
           const int m = m0 + wr * (16 * MI) + (lane >> 3) + mi * 16 + it * 8;
-          float mu_, rs_;
           if (ln_strip_per_lane && m < a.ln_tail_begin) {  // (the 8 lanes of a row agree on both conditions)
-            const float s1 = group_sum<8>(ln_part[mi][it][0]), s2 = group_sum<8>(ln_part[mi][it][1]);
-            const float inv = 1.0f / (float)a.ln_D;
-            mu_ = s1 * inv;
-            rs_ = rsqrtf(fmaxf(s2 * inv - mu_ * mu_, 0.f) + a.ln_eps);
+            mr = mean_rstd(group_sum<8>(ln_part[mi][it][0]), group_sum<8>(ln_part[mi][it][1]), a.ln_D, a.ln_eps);
           } else {
+            float mu_, rs_;
             ln_row_stats<T>(a, m, cp, mu_, rs_);
+            mr = f32x2{mu_, rs_};
           }
-          mr = f32x2{mu_, rs_};
         }
 #pragma unroll
         for (int r = 0; r < 8; ++r) vv[r] = fmaf(mr[1], fmaf(-mr[0], lc[r], c[it][r >> 2][r & 3]), bv[r]);
@@ -807,9 +846,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void linear_mfma_persistent_kernel
   const int total_g = my_tiles * nk;
 
   auto tile_origin = [&](int j, int& m0, int& n0) -> int {
-    int id = blockIdx.x + j * G;
-    const int q = num_tiles >> 3, r = num_tiles & 7, xcd = id & 7, pos = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+    int id = xcd_tile(blockIdx.x + j * G, num_tiles);
     const int split = id % a.splits;
     id /= a.splits;
     m0 = (id / tiles_n) * TBM;
@@ -818,30 +855,13 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void linear_mfma_persistent_kernel
   };
 
   // ---- DMA issue side (runs STAGES-1 K-tiles ahead of the MFMA side, across tile boundaries).  Addresses are a
-  // wave-uniform 64-bit base (operand + K offset) plus a per-lane 32-bit byte offset fixed for the tile.
+  // wave-uniform 64-bit base (operand + K offset) plus a per-lane 32-bit byte offset fixed for the tile (ring_tile_offsets).
   uint32_t a_voff[kAPW], a2_voff[kAPW], w_voff[kWPW];
   int64_t x_toff = 0, x2_toff = 0, w_toff = 0;  // byte offset of the tile being issued (wave-uniform, 64-bit)
   auto setup_issue_tile = [&](int j) {
     int m0, n0;
     const int64_t k_off = (int64_t)tile_origin(j, m0, n0) * nk * BK * 2;
-    x_toff = (int64_t)m0 * a.ldx * 2 + k_off;
-    x2_toff = (int64_t)m0 * a.ldx2 * 2;
-    w_toff = (int64_t)n0 * a.ldw * 2 + k_off;
-#pragma unroll
-    for (int i = 0; i < kAPW; ++i) {
-      const int row = min(wave * kAPW + i, kAPieces - 1) * 8 + (lane >> 3);
-      const int slot = (lane & 7) ^ ((row >> 1) & 7);
-      const int m = min(m0 + row, a.n_rows - 1);  // rows past the end are computed but never stored
-      a_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx + slot * 8) * 2);  // relative to the tile's first row: fits 32 bits
-      a2_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx2 + slot * 8) * 2);
-    }
-#pragma unroll
-    for (int i = 0; i < kWPW; ++i) {
-      const int row = min(wave * kWPW + i, kWPieces - 1) * 8 + (lane >> 3);
-      const int slot = (lane & 7) ^ ((row >> 1) & 7);
-      const int n = min(n0 + row, a.O - 1);
-      w_voff[i] = (uint32_t)(((int64_t)(n - n0) * a.ldw + slot * 8) * 2);
-    }
+    ring_tile_offsets<kAPieces, kWPieces, true>(a, m0, n0, k_off, wave, lane, a_voff, a2_voff, w_voff, x_toff, x2_toff, w_toff);
   };
   int ig = 0, ikt = 0, ij = 0;  // next K-tile to issue: global index, index within its tile, tile
   auto issue_next = [&]() {
@@ -864,11 +884,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void linear_mfma_persistent_kernel
       __builtin_amdgcn_global_load_lds((gbl_void_t*)(wbase + w_voff[i]),
                                        (lds_void_t*)(pc < kWPieces ? stage + TBM * BK * 2 + pc * 1024 : dummy), 16, 0, 0);
     }
-    ++ig;
-    if (++ikt == nk) {
-      ikt = 0;
-      ++ij;
-    }
+    ring_advance(ig, ikt, ij, nk);
   };
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s) issue_next();
@@ -1085,11 +1101,7 @@ __global__ __launch_bounds__(512, 1) void linear_mfma_splitwave_kernel(LinArgs a
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave & 1, wr = (wave >> 1) % WR, kg = (wave >> 1) / WR;
-  int id = blockIdx.x;
-  {  // XCD-aware bijective remap: the column tiles of a row panel run on one XCD (the A panel is fetched into one L2)
-    const int q = num_tiles >> 3, r = num_tiles & 7, xcd = id & 7, pos = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-  }
+  const int id = xcd_tile(blockIdx.x, num_tiles);
   const int m0 = (id / tiles_n) * TM, n0 = (id % tiles_n) * SN;
   const int nk = a.K1 / SKW;
   const uint32_t smem_l = (uint32_t)(size_t)(lds_void_t*)smem;
@@ -1242,37 +1254,18 @@ __global__ __launch_bounds__(512, 1) void linear_mfma_bigtile_kernel(LinArgs a, 
   const int total_g = my_tiles * nk;
 
   auto tile_origin = [&](int j, int& m0, int& n0) {
-    int id = blockIdx.x + j * G;
-    const int q = num_tiles >> 3, r = num_tiles & 7, xcd = id & 7, pos = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
+    const int id = xcd_tile(blockIdx.x + j * G, num_tiles);
     m0 = (id / tiles_n) * TBM;
     n0 = (id % tiles_n) * TBN;
   };
 
-  // ---- DMA issue side: K-tile ig (one ahead of the MFMA side), one 1-KiB piece per call
+  // ---- DMA issue side: K-tile ig (one ahead of the MFMA side), one 1-KiB piece per call; the W pieces divide evenly over the waves
   uint32_t a_voff[kAPW], a2_voff[kAPW], w_voff[kWPW];
   int64_t x_toff = 0, x2_toff = 0, w_toff = 0;  // byte offset of the tile being issued (wave-uniform, 64-bit)
   auto setup_issue_tile = [&](int j) {
     int m0, n0;
     tile_origin(j, m0, n0);
-    x_toff = (int64_t)m0 * a.ldx * 2;
-    x2_toff = (int64_t)m0 * a.ldx2 * 2;
-    w_toff = (int64_t)n0 * a.ldw * 2;
-#pragma unroll
-    for (int i = 0; i < kAPW; ++i) {
-      const int row = min(wave * kAPW + i, kAPieces - 1) * 8 + (lane >> 3);
-      const int slot = (lane & 7) ^ ((row >> 1) & 7);
-      const int m = min(m0 + row, a.n_rows - 1);  // rows past the end are computed but never stored
-      a_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx + slot * 8) * 2);  // relative to the tile's first row: fits 32 bits
-      a2_voff[i] = (uint32_t)(((int64_t)(m - m0) * a.ldx2 + slot * 8) * 2);
-    }
-#pragma unroll
-    for (int i = 0; i < kWPW; ++i) {
-      const int row = (wave * kWPW + i) * 8 + (lane >> 3);
-      const int slot = (lane & 7) ^ ((row >> 1) & 7);
-      const int n = min(n0 + row, a.O - 1);
-      w_voff[i] = (uint32_t)(((int64_t)(n - n0) * a.ldw + slot * 8) * 2);
-    }
+    ring_tile_offsets<kAPieces, kWPieces, false>(a, m0, n0, 0, wave, lane, a_voff, a2_voff, w_voff, x_toff, x2_toff, w_toff);
   };
   // The pieces of a K-tile are issued one by one between MFMAs, so the issue itself must be branch-free: everything
   // uniform (source bases, destination stage, "is there still a K-tile to fetch") is fixed by begin_issue() before the
@@ -1306,13 +1299,7 @@ __global__ __launch_bounds__(512, 1) void linear_mfma_bigtile_kernel(LinArgs a, 
     }
   };
   auto end_issue = [&]() {
-    if (s_valid) {
-      ++ig;
-      if (++ikt == nk) {
-        ikt = 0;
-        ++ij;
-      }
-    }
+    if (s_valid) ring_advance(ig, ikt, ij, nk);
   };
   begin_issue();
 #pragma unroll
@@ -1347,28 +1334,11 @@ __global__ __launch_bounds__(512, 1) void linear_mfma_bigtile_kernel(LinArgs a, 
       // mean / rstd of the tile's rows from the producer's strip sums (fixed order), one thread per row, while the first
       // K-tile is in flight; double-buffered over tiles, published by the K-loop's barriers
       for (int r = tid; r < TBM; r += 64 * NW) {
-        const float* st = a.stats_in + (int64_t)min(m0 + r, a.n_rows - 1) * a.ln_strips * 2;
-        float s1 = 0.f, s2 = 0.f;
-        if (a.ln_strips == 8) {  // D = 512: four 16-byte loads, same summation order as the generic loop
-          f32x4 v[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = reinterpret_cast<const f32x4*>(st)[q];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            s1 += v[q][0];
-            s2 += v[q][1];
-            s1 += v[q][2];
-            s2 += v[q][3];
-          }
-        } else {
-          for (int q = 0; q < a.ln_strips; ++q) {
-            s1 += st[2 * q];
-            s2 += st[2 * q + 1];
-          }
-        }
-        const float inv = 1.0f / (float)a.ln_D, mu = s1 * inv;
-        ln_rows[2 * r] = mu;
-        ln_rows[2 * r + 1] = rsqrtf(fmaxf(s2 * inv - mu * mu, 0.f) + a.ln_eps);
+        float s1, s2;
+        ln_strip_sums(a.stats_in + (int64_t)min(m0 + r, a.n_rows - 1) * a.ln_strips * 2, a.ln_strips, s1, s2);
+        const f32x2 mr = mean_rstd(s1, s2, a.ln_D, a.ln_eps);
+        ln_rows[2 * r] = mr[0];
+        ln_rows[2 * r + 1] = mr[1];
       }
     }
 

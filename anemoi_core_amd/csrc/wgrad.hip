@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mma.h"
 
 namespace anemoi {
 namespace {
@@ -28,27 +29,10 @@ namespace {
 constexpr int TM = 128, TN = 128, TK = 64;
 constexpr int kPiece = 1024;                 // bytes per DMA piece: [8 rows][64 cols] of 16-bit
 
-using frag8 = __attribute__((ext_vector_type(8))) short;
 using s16x4 = __attribute__((ext_vector_type(4))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_line[256];  // zero-initialised: source of out-of-range lanes
-
-template <typename T>
-__device__ __forceinline__ f32x4 mfma16(frag8 a, frag8 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma16<bf16_t>(frag8 a, frag8 b, f32x4 c) {
-  using bf8 = __attribute__((ext_vector_type(8))) __bf16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma16<f16_t>(frag8 a, frag8 b, f32x4 c) {
-  using h8 = __attribute__((ext_vector_type(8))) _Float16;
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), c, 0, 0, 0);
-}
 
 struct WgradArgs {
   const void* dz;  // [n_rows, O]

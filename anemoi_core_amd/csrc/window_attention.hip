@@ -145,7 +145,7 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
 #pragma unroll
       for (int s = 0; s < D / 32; ++s) {
         const frag8 kf = *reinterpret_cast<const frag8*>(k_lds + (16 * sb + c) * KS + 8 * g + 32 * s);
-        z = mfma16(kf, qf[s], z, T{});
+        z = mfma16<T>(kf, qf[s], z);
       }
       st[sb] = z;
     }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
 #pragma unroll
     for (int db = 0; db < D / 16; ++db) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) acc[db] = mfma16(transposed_frag(vt_lds, VS, 16 * db + c, s, g), pf[s], acc[db], T{});
+      for (int s = 0; s < 2; ++s) acc[db] = mfma16<T>(transposed_frag(vt_lds, VS, 16 * db + c, s, g), pf[s], acc[db]);
     }
   }
 

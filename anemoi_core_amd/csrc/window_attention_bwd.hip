@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64 * kWaves) void win_attn_bwd_query_kernel(WinBwdA
       gf[s] = *reinterpret_cast<const frag8*>((const T*)a.d_out + (row0 + qi) * a.ldg + col);
       of = *reinterpret_cast<const frag8*>((const T*)a.out + (row0 + qi) * a.ldo + col);
     }
-    od = mfma16(of, gf[s], od, T{});  // [query 4 g + r][query c]
+    od = mfma16<T>(of, gf[s], od);  // [query 4 g + r][query c]
   }
   const float diag = (c & 3) == 0 ? od[0] : (c & 3) == 1 ? od[1] : (c & 3) == 2 ? od[2] : od[3];
   const float delta = __shfl(diag, 16 * (c >> 2) + c, 64);  // the lane of this query with g = c / 4 holds its diagonal element
@@ -181,8 +181,8 @@ __global__ __launch_bounds__(64 * kWaves) void win_attn_bwd_query_kernel(WinBwdA
       for (int s = 0; s < D / 32; ++s) {
         const frag8 kf = *reinterpret_cast<const frag8*>(k_lds + (16 * sb + c) * RS + 8 * g + 32 * s);
         const frag8 vf = *reinterpret_cast<const frag8*>(v_lds + (16 * sb + c) * RS + 8 * g + 32 * s);
-        st = mfma16(kf, qf[s], st, T{});
-        dp = mfma16(vf, gf[s], dp, T{});
+        st = mfma16<T>(kf, qf[s], st);
+        dp = mfma16<T>(vf, gf[s], dp);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64 * kWaves) void win_attn_bwd_query_kernel(WinBwdA
 #pragma unroll
     for (int db = 0; db < D / 16; ++db) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) acc[db] = mfma16(transposed_frag(kt_lds, TS, 16 * db + c, s, g), tf[s], acc[db], T{});
+      for (int s = 0; s < 2; ++s) acc[db] = mfma16<T>(transposed_frag(kt_lds, TS, 16 * db + c, s, g), tf[s], acc[db]);
     }
   }
 
@@ -324,8 +324,8 @@ __global__ __launch_bounds__(64 * kWaves) void win_attn_bwd_key_kernel(WinBwdArg
       for (int s = 0; s < D / 32; ++s) {
         const frag8 qa = *reinterpret_cast<const frag8*>(q_lds + (16 * sb + c) * RS + 8 * g + 32 * s);
         const frag8 ga = *reinterpret_cast<const frag8*>(g_lds + (16 * sb + c) * RS + 8 * g + 32 * s);
-        st = mfma16(qa, kf[s], st, T{});
-        dp = mfma16(ga, vf[s], dp, T{});
+        st = mfma16<T>(qa, kf[s], st);
+        dp = mfma16<T>(ga, vf[s], dp);
       }
       const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_lds + 16 * sb + 4 * g);
       const f32x4 d4 = *reinterpret_cast<const f32x4*>(delta_lds + 16 * sb + 4 * g);
@@ -344,8 +344,8 @@ __global__ __launch_bounds__(64 * kWaves) void win_attn_bwd_key_kernel(WinBwdArg
     for (int db = 0; db < D / 16; ++db) {
 #pragma unroll
       for (int s = 0; s < QT / 32; ++s) {
-        accv[db] = mfma16(transposed_frag(gt_lds, TS, 16 * db + c, s, g), pf[s], accv[db], T{});
-        acck[db] = mfma16(transposed_frag(qt_lds, TS, 16 * db + c, s, g), tf[s], acck[db], T{});
+        accv[db] = mfma16<T>(transposed_frag(gt_lds, TS, 16 * db + c, s, g), pf[s], accv[db]);
+        acck[db] = mfma16<T>(transposed_frag(qt_lds, TS, 16 * db + c, s, g), tf[s], acck[db]);
       }
     }
   }

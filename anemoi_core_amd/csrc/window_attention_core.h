@@ -2,6 +2,7 @@
 // types of mfma_f32_16x16x32 and the conversions around it.
 #pragma once
 #include "common.h"
+#include "mma.h"
 
 namespace anemoi {
 
@@ -10,19 +11,8 @@ namespace {
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
-using frag8 = __attribute__((ext_vector_type(8))) short;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-
-__device__ __forceinline__ f32x4 mfma16(const frag8& a, const frag8& b, const f32x4& c, bf16_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, a),
-                                                 __builtin_bit_cast(__attribute__((ext_vector_type(8))) __bf16, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(const frag8& a, const frag8& b, const f32x4& c, f16_t) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(__attribute__((ext_vector_type(8))) _Float16, a),
-                                                __builtin_bit_cast(__attribute__((ext_vector_type(8))) _Float16, b), c, 0, 0, 0);
-}
 
 template <typename T>
 __device__ __forceinline__ short to_bits(float x) {

@@ -304,6 +304,26 @@ def test_linear_transpose_detecting(ops):
     assert torch.equal(y.float().cpu(), w.float().t())
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_linear_strided_output_four_column_tail(ops, dtype):
+    """O % 8 == 4 with a row stride that is a multiple of 8 (a column slab of a wider buffer): the only way onto the DMA-ring kernels
+    with half an 8-column group at the end of a row - the band epilogue narrows its last loads and stores to 4 columns.  Three row
+    tiles of 64, the last with 2 rows; the 4 columns of the buffer beyond the output keep their fill."""
+    N, K, O, ld = 130, 64, 100, 104
+    gen = torch.Generator().manual_seed(N + K + O)
+    x = torch.randn(N, K, generator=gen).to(dtype)
+    w = (torch.randn(O, K, generator=gen) / math.sqrt(K)).to(dtype)
+    b = (0.1 * torch.randn(O, generator=gen)).to(dtype)
+    res = torch.randn(N, ld, generator=gen).to(dtype)
+    d = lambda t: t.to(DEV)  # noqa: E731
+    for act in (None, "gelu"):
+        wide = torch.full((N, ld), 7.0, dtype=dtype, device=DEV)
+        y = ops.linear(d(x), d(w), d(b), act=act, residual=d(res)[:, :O], out=wide[:, :O])
+        assert y.data_ptr() == wide.data_ptr()
+        assert_close(wide[:, :O], _lin_ref(x, w, b, act, res[:, :O]), dtype, f"4-column tail act={act}")
+        assert bool((wide[:, O:] == 7.0).all()), "columns beyond the output were written"
+
+
 # ------------------------------------------------------------------------------------------ GraphConv pieces
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("D", [512, 32, 100])
