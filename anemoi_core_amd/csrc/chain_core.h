@@ -301,6 +301,106 @@ __device__ __forceinline__ void store_block_via_strip(const u32x2 (&pk)[NB][4], 
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the strip may be rewritten
 }
 
+// ---- the phases of a panel in the 64-column layout (acc[mi][0..3], eight waves x 64 columns), named once: a kernel's panel loop is
+// load, gemm_seg, one of these, barrier.  pb / pg / pt: this lane's packed columns of a bias / gamma / beta (load_cols, requested
+// before the GEMM).  None of them holds a barrier, and only ring_head a scheduling fence: the order of a panel's phases stays in the
+// kernels, next to the measurements behind it.  Each takes the lane's coordinates from lane_cols itself: the opaque lane id stays per phase.
+
+// the weight ring's first fill: the 4 fragments of each of the first 4 K-steps of the stream at `w` (wave-uniform), pinned in issue order
+__device__ __forceinline__ void ring_head(frag8 (&bq)[4][4], const char* w, uint32_t loff) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      bq[j][ni] = *reinterpret_cast<gfrag_t>(uniform_ptr(w + j * 4096) + loff + ni * 1024);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// load_cols of the vector at p + col0, or zeros for a vector that is not there (a LayerNorm without bias, a projection without one)
+template <typename T>
+__device__ __forceinline__ void load_cols_or_zero(const void* p, int wave, int g, u32x2 (&o)[4], int col0 = 0) {
+  if (p != nullptr) {
+    load_cols<T>((const T*)p + col0, wave, g, o);
+  } else {
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) o[ni] = u32x2{0u, 0u};
+  }
+}
+
+// One column block of a row band: acc + bias, GELU unless gelu is false, rounded to the model dtype
+template <typename T>
+__device__ __forceinline__ u32x2 bias_act4(const f32x4& v, u32x2 pb, bool gelu) {
+  float bias[4], t[4];
+  unpack4<T>(pb, bias);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) t[r] = v[r] + bias[r];
+  if (gelu) {
+    gelu_fast2(t[0], t[1]);
+    gelu_fast2(t[2], t[3]);
+  }
+  return pack4<T>(t);
+}
+// The wave's block through bias_act4 into the panel buffer `dst` (its own columns) ...
+template <typename T, int NB>
+__device__ __forceinline__ void bias_act_rows(const f32x4 (&acc)[NB][4], const u32x2 (&pb)[4], unsigned char* dst, int lane, int wave, bool gelu = true) {
+  const LaneCols<4> lc = lane_cols<4>(lane, wave);
+#pragma unroll
+  for (int mi = 0; mi < NB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) *reinterpret_cast<u32x2*>(dst + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = bias_act4<T>(acc[mi][ni], pb[ni], gelu);
+}
+// ... or into registers first (bias_act_pack) and from there into the buffer (put_rows): the form for a block that goes over the operand
+// it was computed from, with the caller's barrier between the two - and, on its own, for a block on its way to store_block_via_strip
+template <typename T, int NB>
+__device__ __forceinline__ void bias_act_pack(const f32x4 (&acc)[NB][4], const u32x2 (&pb)[4], u32x2 (&pk)[NB][4], bool gelu) {
+#pragma unroll
+  for (int mi = 0; mi < NB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) pk[mi][ni] = bias_act4<T>(acc[mi][ni], pb[ni], gelu);
+}
+template <typename T, int NB>
+__device__ __forceinline__ void put_rows(const u32x2 (&pk)[NB][4], unsigned char* dst, int lane, int wave) {
+  const LaneCols<4> lc = lane_cols<4>(lane, wave);
+#pragma unroll
+  for (int mi = 0; mi < NB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) *reinterpret_cast<u32x2*>(dst + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = pk[mi][ni];
+}
+// acc <- the fp32 image of (acc + bias) rounded to the model dtype, as a Linear's output is: the input of panel_row_stats
+template <typename T, int NB>
+__device__ __forceinline__ void bias_round_rows(f32x4 (&acc)[NB][4], const u32x2 (&pb)[4]) {
+#pragma unroll
+  for (int mi = 0; mi < NB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      float t[4];
+      unpack4<T>(bias_act4<T>(acc[mi][ni], pb[ni], false), t);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[mi][ni][r] = t[r];
+    }
+}
+
+// pk = LayerNorm(acc) + residual, rounded once: fma((acc - mean) rstd, gamma, beta) + res - the arithmetic of layernorm_fwd followed by
+// the residual add, which is edge_ln_res_segsum's.  res(mi, ni): this lane's 4 packed residual values of row band mi, column block ni
+// (from registers or from a panel in LDS).
+template <typename T, int NB, typename Res>
+__device__ __forceinline__ void layernorm_residual_pack(const f32x4 (&acc)[NB][4], const float (&mean)[NB], const float (&rstd)[NB], const u32x2 (&pg)[4],
+                                                        const u32x2 (&pt)[4], Res res, u32x2 (&pk)[NB][4]) {
+#pragma unroll
+  for (int mi = 0; mi < NB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      float gv[4], bv[4], rv[4], o[4];
+      unpack4<T>(pg[ni], gv);
+      unpack4<T>(pt[ni], bv);
+      unpack4<T>(res(mi, ni), rv);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = fmaf((acc[mi][ni][r] - mean[mi]) * rstd[mi], gv[r], bv[r]) + rv[r];
+      pk[mi][ni] = pack4<T>(o);
+    }
+}
+
 // ---- epilogues of a wave's 48 x 16 NI block held as acc[mi][0..NI-1] (wave w of kWaves<NI>), on the swizzled panel buffers
 
 // acc[mi][ni] = vec[col0 + column] (+ the panel values at the lane's positions of `rows`): the accumulators of a GEMM start at its bias (+ residual)

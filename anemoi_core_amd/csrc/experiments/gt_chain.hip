@@ -115,13 +115,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
   request_panel(tile);
   __builtin_amdgcn_sched_barrier(0);
   frag8 bq[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      bq[j][ni] = *reinterpret_cast<gfrag_t>(uniform_ptr(wp0 + j * 4096) + loff + ni * 1024);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  ring_head(bq, wp0, loff);
 
   for (;;) {
     const int r0 = tile * a.rows_per_tile;
@@ -146,12 +140,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     u32x2 pb[4], pg[4], pt[4];  // packed parameter columns of the coming epilogue (see load_cols)
     load_cols<T>((const T*)a.bp, wave, g, pb);
     load_cols<T>((const T*)a.ln1_g, wave, g, pg);
-    if (a.ln1_b != nullptr) {
-      load_cols<T>((const T*)a.ln1_b, wave, g, pt);
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) pt[ni] = u32x2{0u, 0u};
-    }
+    load_cols_or_zero<T>(a.ln1_b, wave, g, pt);
     __builtin_amdgcn_sched_barrier(0);
 
     f32x4 acc[3][4], acc2[3][4];
@@ -214,30 +203,13 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
         for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni) hp[mi][ni] = u32x2{__float_as_uint(acc[mi][ni][0]), __float_as_uint(acc[mi][ni][1])};
-      } else
-#pragma unroll
-      for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float bias[4], t[4];
-          unpack4<T>(pb[ni], bias);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-          gelu_fast2(t[0], t[1]);
-          gelu_fast2(t[2], t[3]);
-          hp[mi][ni] = pack4<T>(t);
-        }
+      } else {
+        bias_act_pack<T, 3>(acc, pb, hp, true);
+      }
       stamp();  // GELU in registers
       if (c > 0) lds_barrier();  // all waves: M2(c-2) read and h_(c-1) written (c = 0: bufA was last read by the projection, two barriers ago)
       stamp();  // barrier passed
-      {
-        const LaneCols<4> lc = lane_cols<4>(lane, wave);
-        unsigned char* const hb = (c & 1) ? bufC : bufA;
-#pragma unroll
-        for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) *reinterpret_cast<u32x2*>(hb + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = hp[mi][ni];
-      }
+      put_rows<T, 3>(hp, (c & 1) ? bufC : bufA, lane, wave);
       if (c > 0) {
         // M2(c-1); behind it M1(c+1), or the last MLP-2 segment
         const char* nx2 = c + 1 < a.hc ? w10 + (int64_t)(c + 1) * 8 * kSlab : w20 + (int64_t)c * kSlab;
@@ -249,12 +221,7 @@ __global__ __launch_bounds__(512, 1) void gt_chain_kernel(ChainArgs a) {
     load_cols<T>((const T*)a.b2, wave, g, pb);
     if (a.qc > 0) {
       load_cols<T>((const T*)a.lnq_g, wave, g, pg);
-      if (a.lnq_b != nullptr) {
-        load_cols<T>((const T*)a.lnq_b, wave, g, pt);
-      } else {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) pt[ni] = u32x2{0u, 0u};
-      }
+      load_cols_or_zero<T>(a.lnq_b, wave, g, pt);
     }
     {
       const LaneCols<4> lc = lane_cols<4>(lane, wave);

@@ -107,13 +107,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
   }
   __builtin_amdgcn_sched_barrier(0);
   frag8 bq[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      bq[j][ni] = *reinterpret_cast<gfrag_t>(uniform_ptr(w0 + j * 4096) + loff + ni * 1024);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  ring_head(bq, w0, loff);
   lds_barrier();
 
   for (;;) {
@@ -176,7 +170,12 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
       gemm_seg<T, NB>(bufE + 48 * 16, lane, bq, w0 + 3 * 16384, w1, loff, acc, NoHook(), 1, flip < 0 ? -1 : flip ^ 1);
     }
     stamp();  // + 1: first GEMM done
-    {
+    if constexpr (MLP) {
+      bias_act_rows<T, NB>(acc, pb, bufH, lane, wave, !(dbg & 1));
+    } else {
+      // bias_act_rows with the two gathered rows added in front of the GELU.  Inline: with the gathered rows live this phase sits at 251
+      // VGPRs, and every helper form tried (an addend callable of bias_act_rows) came out at 256, the bf16 one with scratch
+      // (profiles/r23_gnn_chain_helpers_check.txt)
       const LaneCols<4> lc = lane_cols<4>(lane, wave);
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi)
@@ -184,15 +183,10 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
         for (int ni = 0; ni < 4; ++ni) {
           float bias[4], t1[4], t2[4], t[4];
           unpack4<T>(pb[ni], bias);
-          if constexpr (MLP) {
+          unpack4<T>(ga[mi][ni], t1);
+          unpack4<T>(gb[mi][ni], t2);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-          } else {
-            unpack4<T>(ga[mi][ni], t1);
-            unpack4<T>(gb[mi][ni], t2);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) t[r] = (acc[mi][ni][r] + bias[r]) + (t1[r] + t2[r]);  // the association of linear.hip's gather-add epilogue
-          }
+          for (int r = 0; r < 4; ++r) t[r] = (acc[mi][ni][r] + bias[r]) + (t1[r] + t2[r]);  // the association of linear.hip's gather-add epilogue
           if (!(dbg & 1)) {
             gelu_fast2(t[0], t[1]);
             gelu_fast2(t[2], t[3]);
@@ -218,37 +212,13 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
     }
     stamp();  // + 3: second GEMM done (and the next panel moved into LDS)
     u32x2 hp[NB][4];
-#pragma unroll
-    for (int mi = 0; mi < NB; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        float bias[4], t[4];
-        unpack4<T>(pb[ni], bias);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-        if (!(dbg & 1)) {
-          gelu_fast2(t[0], t[1]);
-          gelu_fast2(t[2], t[3]);
-        }
-        hp[mi][ni] = pack4<T>(t);
-      }
+    bias_act_pack<T, NB>(acc, pb, hp, !(dbg & 1));
     lds_barrier();
-    {
-      const LaneCols<4> lc = lane_cols<4>(lane, wave);
-#pragma unroll
-      for (int mi = 0; mi < NB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) *reinterpret_cast<u32x2*>(bufH + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = hp[mi][ni];
-    }
+    put_rows<T, NB>(hp, bufH, lane, wave);
     u32x2 pg[4], pt[4];
     load_cols<T>((const T*)a.b2, wave, g, pb);
     load_cols<T>((const T*)a.ln_g, wave, g, pg);
-    if (a.ln_b != nullptr) {
-      load_cols<T>((const T*)a.ln_b, wave, g, pt);
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) pt[ni] = u32x2{0u, 0u};
-    }
+    load_cols_or_zero<T>(a.ln_b, wave, g, pt);
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
     stamp();  // + 4: GELU epilogue written in place (two barriers)
@@ -275,6 +245,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
           for (int ni = 0; ni < 4; ++ni) er[mi][ni] = u32x2{0u, 0u};
       }
       __builtin_amdgcn_sched_barrier(0);
+      // bias_round_rows, inline: as the helper the instrumented instantiation (256 VGPRs, spilling) spilled one register more
 #pragma unroll
       for (int mi = 0; mi < NB; ++mi)
 #pragma unroll
@@ -291,18 +262,7 @@ __global__ __launch_bounds__(512, 1) void gnn_edge_chain_kernel(EdgeChainArgs a)
       panel_row_stats<T, NB>(acc, a.ln_eps, red, wave, lc.x, lc.g, mean, rstd);  // (one barrier: behind it no wave reads bufH)
       stamp();  // + 6: row statistics merged (barrier passed)
       u32x2 pk[NB][4];
-#pragma unroll
-      for (int mi = 0; mi < NB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float gv[4], bv[4], ev[4], o[4];
-          unpack4<T>(pg[ni], gv);
-          unpack4<T>(pt[ni], bv);
-          unpack4<T>(er[mi][ni], ev);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = fmaf((acc[mi][ni][r] - mean[mi]) * rstd[mi], gv[r], bv[r]) + ev[r];  // edge_ln_res_segsum's arithmetic
-          pk[mi][ni] = pack4<T>(o);
-        }
+      layernorm_residual_pack<T, NB>(acc, mean, rstd, pg, pt, [&](int mi, int ni) { return er[mi][ni]; }, pk);
       store_block_via_strip<T, NB>(pk, bufH + wave * (kERows * 128), (T*)a.e_new + (int64_t)r0 * a.ld_o + wave * 64, a.ld_o, (dbg & 8) ? 0 : nr, lane, wave);
     }
     stamp();  // + 7: LayerNorm + residual applied, rows stored through the strips
@@ -429,13 +389,7 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
   request_panel(tile);
   __builtin_amdgcn_sched_barrier(0);
   frag8 bq[4][4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      bq[j][ni] = *reinterpret_cast<gfrag_t>(uniform_ptr(wa0 + j * 4096) + loff + ni * 1024);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+  ring_head(bq, wa0, loff);
 
   for (;;) {
     const int r0 = tile * a.rows_per_tile;
@@ -459,51 +413,18 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     zero_acc<T>(acc);
     gemm_seg<T>(bufA, lane, bq, wa0, wa0 + kSlab, loff, acc);
     gemm_seg<T>(bufC, lane, bq, wa0 + kSlab, wb0, loff, acc);
-    {
-      const LaneCols<4> lc = lane_cols<4>(lane, wave);
-#pragma unroll
-      for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float bias[4], t[4];
-          unpack4<T>(pb[ni], bias);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-          gelu_fast2(t[0], t[1]);
-          gelu_fast2(t[2], t[3]);
-          *reinterpret_cast<u32x2*>(bufB + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = pack4<T>(t);
-        }
-    }
+    bias_act_rows<T, 3>(acc, pb, bufB, lane, wave);
     load_cols<T>((const T*)a.bb, wave, g, pb);
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();  // h1 complete; every wave is done with the agg panel
     // ---- h2 = gelu(h1 W_b^T + b_b) -> bufC
     zero_acc<T>(acc);
     gemm_seg<T>(bufB, lane, bq, wb0, wc0, loff, acc);
-    {
-      const LaneCols<4> lc = lane_cols<4>(lane, wave);
-#pragma unroll
-      for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float bias[4], t[4];
-          unpack4<T>(pb[ni], bias);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-          gelu_fast2(t[0], t[1]);
-          gelu_fast2(t[2], t[3]);
-          *reinterpret_cast<u32x2*>(bufC + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = pack4<T>(t);
-        }
-    }
+    bias_act_rows<T, 3>(acc, pb, bufC, lane, wave);
     u32x2 pg[4], pt[4];
     load_cols<T>((const T*)a.bc, wave, g, pb);
     load_cols<T>((const T*)a.ln_g, wave, g, pg);
-    if (a.ln_b != nullptr) {
-      load_cols<T>((const T*)a.ln_b, wave, g, pt);
-    } else {
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) pt[ni] = u32x2{0u, 0u};
-    }
+    load_cols_or_zero<T>(a.ln_b, wave, g, pt);
     __builtin_amdgcn_sched_barrier(0);
     lds_barrier();
     // ---- y = h2 W_c^T + b_c (rounded); x' = LayerNorm(y) + x -> global (and bufB for the trailing projection)
@@ -514,59 +435,29 @@ __global__ __launch_bounds__(512, 1) void gnn_node_chain_kernel(NodeChainArgs a)
     unsigned char* const strip = bufC + wave * (kPanel * 128);  // behind the statistics' barrier no wave reads bufC any more
     {
       const LaneCols<4> lc = lane_cols<4>(lane, wave);
-#pragma unroll
-      for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float bias[4], t[4];
-          unpack4<T>(pb[ni], bias);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) t[r] = acc[mi][ni][r] + bias[r];
-          unpack4<T>(pack4<T>(t), t);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[mi][ni][r] = t[r];
-        }
+      bias_round_rows<T, 3>(acc, pb);
       float mean[3], rstd[3];
       panel_row_stats<T>(acc, a.ln_eps, red, wave, lc.x, lc.g, mean, rstd);
       u32x2 pk[3][4];
+      auto x_rows = [&](int mi, int ni) { return *reinterpret_cast<const u32x2*>(bufA + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]); };
+      layernorm_residual_pack<T, 3>(acc, mean, rstd, pg, pt, x_rows, pk);
+      if (a.tc > 0) {
 #pragma unroll
-      for (int mi = 0; mi < 3; ++mi)
+        for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          float gv[4], bv[4], xv[4], o[4];
-          unpack4<T>(pg[ni], gv);
-          unpack4<T>(pt[ni], bv);
-          unpack4<T>(*reinterpret_cast<const u32x2*>(bufA + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]), xv);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = fmaf((acc[mi][ni][r] - mean[mi]) * rstd[mi], gv[r], bv[r]) + xv[r];  // layernorm_fwd's arithmetic (+ residual)
-          pk[mi][ni] = pack4<T>(o);
-          if (a.tc > 0) *reinterpret_cast<u32x2*>(bufB + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = pk[mi][ni];
-        }
+          for (int ni = 0; ni < 4; ++ni) *reinterpret_cast<u32x2*>(bufB + (mi * 16 + lc.x) * kRowBytes + lc.coff[ni]) = pk[mi][ni];
+      }
       store_block_via_strip<T>(pk, strip, (T*)a.x_out + (int64_t)r0 * a.ld_o + wave * 64, a.ld_o, nr, lane, wave);
     }
     if (a.tc > 0) {
       lds_barrier();  // x' panel complete
       for (int c = 0; c < a.tc; ++c) {
-        if (a.bt != nullptr) {
-          load_cols<T>((const T*)a.bt + c * kCh, wave, g, pb);
-        } else {
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) pb[ni] = u32x2{0u, 0u};
-        }
+        load_cols_or_zero<T>(a.bt, wave, g, pb, c * kCh);
         __builtin_amdgcn_sched_barrier(0);
         zero_acc<T>(acc);
         gemm_seg<T>(bufB, lane, bq, wt0 + (int64_t)c * 8 * kSlab, c + 1 < a.tc ? wt0 + (int64_t)(c + 1) * 8 * kSlab : wa0, loff, acc);
         u32x2 pk[3][4];
-#pragma unroll
-        for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            float bias[4], o[4];
-            unpack4<T>(pb[ni], bias);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = acc[mi][ni][r] + bias[r];
-            pk[mi][ni] = pack4<T>(o);
-          }
+        bias_act_pack<T, 3>(acc, pb, pk, false);
         store_block_via_strip<T>(pk, strip, (T*)a.t_out + (int64_t)r0 * a.ld_t + c * kCh + wave * 64, a.ld_t, nr, lane, wave);
       }
     }
@@ -594,6 +485,18 @@ using namespace anemoi;
 
 static bool al(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// The operand, alignment and leading-dimension checks of the edge chain's entry points, on their argument block (`who`: the entry point's
+// name in the error text).  mlp: no gathered rows, an optional residual, and e only as wide as the first GEMM's K
+static int edge_chain_operands(const char* who, const EdgeChainArgs& a, bool mlp) {
+  ANEMOI_REQUIRE(a.e && a.w0 && a.b0 && a.w1 && a.b1 && a.w2 && a.b2 && a.ln_g && a.e_new && (mlp || (a.g1 && a.idx1 && a.g2 && a.idx2)), "%s: null operand", who);
+  ANEMOI_REQUIRE(al(a.e, 16) && al(a.e_new, 16) && al(a.w0, 16) && al(a.w1, 16) && al(a.w2, 16) && al(a.g1, 8) && al(a.g2, 8) && al(a.res, 8) && al(a.b0, 8) &&
+                     al(a.b1, 8) && al(a.b2, 8) && al(a.ln_g, 8) && al(a.ln_b, 8) && a.ld_e % 8 == 0 && a.ld_o % 8 == 0 && a.ld_e >= 128 * a.k0_groups &&
+                     a.ld_o >= kCh && (mlp || (a.ld_g1 % 4 == 0 && a.ld_g2 % 4 == 0 && a.ld_g1 >= kCh && a.ld_g2 >= kCh)) &&
+                     (!a.res || (a.ld_res % 4 == 0 && a.ld_res >= kCh)),
+                 "%s: operand alignment / leading dimensions", who);
+  return ANEMOI_OK;
+}
+
 extern "C" int anemoi_gnn_edge_chain_fwd(const void* e, int64_t ld_e, const void* g1, int64_t ld_g1, const int32_t* idx1, const void* g2,
                                          int64_t ld_g2, const int32_t* idx2, const void* w0, const void* b0, const void* w1, const void* b1,
                                          const void* w2, const void* b2, const void* ln_w, const void* ln_b, float eps, void* e_new,
@@ -601,13 +504,9 @@ extern "C" int anemoi_gnn_edge_chain_fwd(const void* e, int64_t ld_e, const void
   ChainPlan plan;
   const int rc = gnn_plan("gnn_edge_chain_fwd", ChainKind::GnnEdge, n_rows, 0, channels, dtype, plan);
   if (rc != ANEMOI_OK || plan.grid == 0) return rc;
-  ANEMOI_REQUIRE(e && g1 && idx1 && g2 && idx2 && w0 && b0 && w1 && b1 && w2 && b2 && ln_w && e_new, "gnn_edge_chain_fwd: null operand");
-  ANEMOI_REQUIRE(al(e, 16) && al(e_new, 16) && al(w0, 16) && al(w1, 16) && al(w2, 16) && al(g1, 8) && al(g2, 8) && al(b0, 8) && al(b1, 8) && al(b2, 8) &&
-                     al(ln_w, 8) && al(ln_b, 8) && ld_e % 8 == 0 && ld_o % 8 == 0 && ld_g1 % 4 == 0 && ld_g2 % 4 == 0 && ld_e >= kCh && ld_o >= kCh &&
-                     ld_g1 >= kCh && ld_g2 >= kCh,
-                 "gnn_edge_chain_fwd: operand alignment / leading dimensions");
   EdgeChainArgs a{e, ld_e, g1, ld_g1, idx1, g2, ld_g2, idx2, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, e_new, ld_o,
                   n_rows, plan.rows_per_panel, plan.panels, 0};
+  if (const int bad = edge_chain_operands("gnn_edge_chain_fwd", a, false)) return bad;
   // round 5: ANEMOI_GNN_CHAIN_V2=1 selects the two-group launch (gnn_chain2.hip): built, parity-green, and slower than the symmetric
   // kernel below (212 against 195 us at 81 840 rows: its 40 / 48-row panels need 7-8 passes over the weights instead of 5,
   // profiles/r05_gnn_edge_chain_role_split.txt) - kept for the A/B
@@ -630,18 +529,15 @@ extern "C" int anemoi_gnn_edge_chain_timeline(const void* e, int64_t ld_e, const
                                               int64_t ld_g2, const int32_t* idx2, const void* w0, const void* b0, const void* w1, const void* b1,
                                               const void* w2, const void* b2, const void* ln_w, const void* ln_b, float eps, void* e_new,
                                               int64_t ld_o, int32_t n_rows, unsigned long long* timeline, void* stream) {
-  ANEMOI_REQUIRE(n_rows > 0 && e && g1 && idx1 && g2 && idx2 && w0 && b0 && w1 && b1 && w2 && b2 && ln_w && e_new && timeline, "gnn_edge_chain_timeline: null operand");
-  // (the argument checks of anemoi_gnn_edge_chain_fwd; this entry point is bf16 only)
-  ANEMOI_REQUIRE(al(e, 16) && al(e_new, 16) && al(w0, 16) && al(w1, 16) && al(w2, 16) && al(g1, 8) && al(g2, 8) && al(b0, 8) && al(b1, 8) && al(b2, 8) &&
-                     al(ln_w, 8) && al(ln_b, 8) && ld_e % 8 == 0 && ld_o % 8 == 0 && ld_g1 % 4 == 0 && ld_g2 % 4 == 0 && ld_e >= kCh && ld_o >= kCh &&
-                     ld_g1 >= kCh && ld_g2 >= kCh,
-                 "gnn_edge_chain_timeline: operand alignment / leading dimensions");
-  ChainPlan plan;
-  const int rc = gnn_plan("gnn_edge_chain_timeline", ChainKind::GnnEdge, n_rows, 0, kCh, ANEMOI_BF16, plan);
-  if (rc != ANEMOI_OK) return rc;
   EdgeChainArgs a{e, ld_e, g1, ld_g1, idx1, g2, ld_g2, idx2, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, e_new, ld_o,
-                  n_rows, plan.rows_per_panel, plan.panels, 0};
+                  n_rows, 0, 0, 0};
   a.timeline = timeline;
+  ANEMOI_REQUIRE(n_rows > 0 && timeline, "gnn_edge_chain_timeline: null operand");
+  if (const int bad = edge_chain_operands("gnn_edge_chain_timeline", a, false)) return bad;
+  ChainPlan plan;
+  const int rc = gnn_plan("gnn_edge_chain_timeline", ChainKind::GnnEdge, n_rows, 0, kCh, ANEMOI_BF16, plan);  // (this entry point is bf16 only)
+  if (rc != ANEMOI_OK) return rc;
+  a.rows_per_tile = plan.rows_per_panel, a.n_tiles = plan.panels;
   static const int dbg = ANEMOI_EXPERIMENT_ENV("ANEMOI_EDGE_CHAIN_DBG", 0, 0, 31);
   a.dbg = dbg;
   plan.lds_bytes = kEdgeSmem + 8 * kETlSlots * 8;  // (the instrumented instantiation's stamps behind the product's LDS)
@@ -656,15 +552,12 @@ extern "C" int anemoi_gnn_mlp_chain_fwd(const void* x, int64_t ld_x, int32_t in_
   ChainPlan plan;
   const int rc = gnn_plan("gnn_mlp_chain_fwd", ChainKind::GnnMlp, n_rows, in_features, channels, dtype, plan);
   if (rc != ANEMOI_OK || plan.grid == 0) return rc;
-  ANEMOI_REQUIRE(x && w0 && b0 && w1 && b1 && w2 && b2 && ln_w && out, "gnn_mlp_chain_fwd: null operand");
-  ANEMOI_REQUIRE(al(x, 16) && al(out, 16) && al(w0, 16) && al(w1, 16) && al(w2, 16) && al(res, 8) && al(b0, 8) && al(b1, 8) && al(b2, 8) && al(ln_w, 8) &&
-                     al(ln_b, 8) && ld_x % 8 == 0 && ld_o % 8 == 0 && ld_x >= in_features && ld_o >= kCh && (!res || (ld_res % 4 == 0 && ld_res >= kCh)),
-                 "gnn_mlp_chain_fwd: operand alignment / leading dimensions");
   EdgeChainArgs a{x, ld_x, nullptr, 0, nullptr, nullptr, 0, nullptr, (const char*)w0, b0, (const char*)w1, b1, (const char*)w2, b2, ln_w, ln_b, eps, out, ld_o,
                   n_rows, plan.rows_per_panel, plan.panels, 0};
   a.res = res;
   a.ld_res = ld_res;
-  a.k0_groups = in_features / 128;
+  a.k0_groups = in_features / 128;  // (a multiple of 128: the plan refuses every other width)
+  if (const int bad = edge_chain_operands("gnn_mlp_chain_fwd", a, true)) return bad;
 #ifdef ANEMOI_EXPERIMENTS
   static const int v2 = env_int(getenv("ANEMOI_GNN_CHAIN_V2"), 0, 0, 1);
   if (v2) return launch_edge_chain2(a, dtype, stream, true);

@@ -264,6 +264,29 @@ int main(int argc, char** argv) {
     EXPECT(anemoi_gt_rowchain_fwd(nullptr, ANEMOI_BF16, nullptr) == ANEMOI_E_INVALID, "row chain null block");
     EXPECT(anemoi_gt_cluster_chain_fwd(nullptr, ANEMOI_BF16, nullptr) == ANEMOI_E_INVALID, "cluster null block");
     EXPECT(anemoi_gt_embed_fold_fwd(nullptr, ANEMOI_BF16, nullptr) == ANEMOI_E_INVALID, "embed fold null block");
+    // the GraphConv edge and MLP chains check their operands in one place: the code, and the text under the entry point's own name
+    void* const v = P(0x10000);
+    void* const odd = P(0x10004);
+    const int32_t* const idx = reinterpret_cast<const int32_t*>(P(0x20000));
+    const auto refused = [](int rc, const char* text) { return rc == ANEMOI_E_INVALID && strcmp(anemoi::g_err, text) == 0; };
+    const char* const kNull = "gnn_edge_chain_fwd: null operand";
+    const char* const kAlign = "gnn_edge_chain_fwd: operand alignment / leading dimensions";
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 512, nullptr, 512, idx, v, 512, idx, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kNull), "edge null g1");
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 512, v, 512, idx, v, 512, nullptr, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kNull), "edge null idx2");
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 512, v, 512, idx, v, 512, idx, v, v, v, v, v, v, nullptr, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kNull), "edge null ln_w");
+    EXPECT(anemoi_gnn_edge_chain_fwd(v, 512, v, 512, idx, v, 512, idx, v, v, v, v, v, v, v, nullptr, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr) == ANEMOI_OK, "edge without ln_b");
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 512, odd, 512, idx, v, 512, idx, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kAlign), "edge g1 alignment");
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 512, v, 510, idx, v, 512, idx, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kAlign), "edge ld_g1");
+    EXPECT(refused(anemoi_gnn_edge_chain_fwd(v, 504, v, 512, idx, v, 512, idx, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 65, 512, ANEMOI_BF16, nullptr), kAlign), "edge ld_e");
+    EXPECT(anemoi_gnn_edge_chain_fwd(v, 512, nullptr, 512, idx, v, 512, idx, v, v, v, v, v, v, v, v, 1e-5f, v, 512, 0, 512, ANEMOI_BF16, nullptr) == ANEMOI_OK, "edge no rows: operands not looked at");
+    const char* const kMlpNull = "gnn_mlp_chain_fwd: null operand";
+    const char* const kMlpAlign = "gnn_mlp_chain_fwd: operand alignment / leading dimensions";
+    EXPECT(refused(anemoi_gnn_mlp_chain_fwd(nullptr, 256, 256, v, v, v, v, v, v, v, v, 1e-5f, nullptr, 0, v, 512, 65, 512, ANEMOI_F16, nullptr), kMlpNull), "mlp null x");
+    EXPECT(anemoi_gnn_mlp_chain_fwd(v, 256, 256, v, v, v, v, v, v, v, v, 1e-5f, nullptr, 0, v, 512, 65, 512, ANEMOI_F16, nullptr) == ANEMOI_OK, "mlp 256 columns wide, no residual");
+    EXPECT(refused(anemoi_gnn_mlp_chain_fwd(v, 248, 256, v, v, v, v, v, v, v, v, 1e-5f, nullptr, 0, v, 512, 65, 512, ANEMOI_F16, nullptr), kMlpAlign), "mlp ld_x below in_features");
+    EXPECT(refused(anemoi_gnn_mlp_chain_fwd(v, 256, 256, v, v, v, v, v, v, v, v, 1e-5f, v, 510, v, 512, 65, 512, ANEMOI_F16, nullptr), kMlpAlign), "mlp ld_res");
+    EXPECT(refused(anemoi_gnn_mlp_chain_fwd(v, 256, 256, v, v, v, v, v, v, v, v, 1e-5f, odd, 512, v, 512, 65, 512, ANEMOI_F16, nullptr), kMlpAlign), "mlp residual alignment");
+    EXPECT(anemoi_gnn_mlp_chain_fwd(v, 256, 256, v, v, v, v, v, v, v, v, 1e-5f, v, 512, v, 512, 65, 512, ANEMOI_F16, nullptr) == ANEMOI_OK, "mlp with residual");
   }
   if (!g_record) printf("chain entry points: %d checks, %d failures\n", g_cases, g_fail);
   return g_fail ? 1 : 0;
