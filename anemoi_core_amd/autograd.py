@@ -32,7 +32,8 @@ _SAVE_PRE = os.environ.get("ANEMOI_SAVE_PREACT", "1") == "1"  # 0: recompute GEL
 def _granule_rows(t: Tensor) -> Tensor:
     """Rows that start on 16-byte boundaries (what the LDS-DMA granules of the wgrad kernel need), copying only if necessary."""
     ok = t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) % 8 == 0) and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
+    # clone, not contiguous(): a dense view that starts off a 16-byte boundary is "contiguous" already and would come back as it is
+    return t if ok else t.clone(memory_format=torch.contiguous_format)
 
 
 def _tn_ok(dz: Tensor, x: Tensor) -> bool:

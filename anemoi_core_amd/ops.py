@@ -769,7 +769,15 @@ def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, act: Opt
     """y = act([x | x2] @ weight^T + bias + g1[idx1] + g2[idx2]) + residual.  x [N, K1], x2 [N, K2], weight [O, K1+K2].
     Differentiable: with autograd recording it runs as ``autograd.LinearFunction``; the gather-add terms then need
     ``seg1`` / ``seg2`` = (ptr int32 [rows(g)+1], ids int32 [N] or None): the rows of the output grouped by idx value
-    (for a dst-sorted graph: (colptr, None) for idx = dst and (rowptr, edge_ids) for idx = src)."""
+    (for a dst-sorted graph: (colptr, None) for idx = dst and (rowptr, edge_ids) for idx = src).
+    Leading dimensions of x (and of a residual) count as rows, as in torch.nn.Linear: y gets them back."""
+    if x.dim() > 2:
+        if out is not None:
+            raise ValueError("out= needs a 2-D x")
+        res2d = None if residual is None else residual.reshape(-1, residual.shape[-1])
+        y = linear(x.reshape(-1, x.shape[-1]), weight, bias, act=act, residual=res2d, x2=x2, g1=g1, idx1=idx1, g2=g2, idx2=idx2,
+                   seg1=seg1, seg2=seg2)
+        return y.view(*x.shape[:-1], y.shape[-1])
     if _needs_grad(x, weight, bias, residual, x2, g1, g2):
         if out is not None:
             raise ValueError("out= is not supported while autograd is recording")
