@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import threading
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanemoi_hip.so")
 
 F32, BF16, F16 = 0, 1, 2
@@ -30,6 +30,11 @@ class AttentionPlan(C.Structure):
     """anemoi_gt_attention_plan_t: the plan of one edge-attention call (csrc/gt_attention_plan.h), field for field."""
     _fields_ = [(name, _i32) for name in ("route", "vec", "lph", "fe_pad", "kv_adjacent", "lds_bytes")] + \
                [(name, C.c_uint32) for name in ("grid_dst", "grid_src", "grid_wgrad")]
+
+
+class WindowAttentionPlan(C.Structure):
+    """anemoi_window_attention_plan_t: what a window-attention kernel does with a sequence (csrc/window_attention_core.h), field for field."""
+    _fields_ = [(name, _i32) for name in ("window", "rows_per_block", "grid_x", "tile_rows", "lo", "hi", "ntiles")]
 
 
 class ShtPlan(C.Structure):
@@ -129,6 +134,7 @@ SIGNATURES = {
     "anemoi_window_attention_fwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f, _f, _p, C.c_int, _p], C.c_int),
     "anemoi_window_attention_bwd": ([_p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i32, _i32, _i32, _i32,
                                      _i32, _f, _f, _p, _i32, C.c_int, _p], C.c_int),
+    "anemoi_window_attention_plan": ([_i32, _i32, _i32, _i32, C.c_int, _i32, _i32, C.POINTER(WindowAttentionPlan), C.POINTER(_i32), _i32], C.c_int),
     "anemoi_sparse_project_fwd": ([_p, _i64, _i64, _i32, _i64, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _i32, C.c_int, C.c_int, _p], C.c_int),
     "anemoi_sht_plan": ([_i32, _i32, C.POINTER(_i32), _i32, _i32, C.POINTER(ShtPlan)], C.c_int),
     "anemoi_sht_fwd": ([_p, _i64, _i64, _p, _i32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _p], C.c_int),

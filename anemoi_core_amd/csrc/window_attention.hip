@@ -5,25 +5,21 @@
 //   s = <q_i, k_j> * scale;  s = softcap * tanh(s / softcap) if softcap > 0;  s -= slope_h * |i - j| if ALiBi;
 //   out_i = sum_j softmax_j(s) v_j,  lse_i = ln sum_j exp(s_j - max) + max.
 //
-// 16-bit path (flash-style, mfma_f32_16x16x32): a workgroup of four waves owns 64 query rows of one (sequence, head); each wave 16 of
-// them.  Only the 64-key tiles that meet [q0 - w, q1 + w] ∩ [0, N) are visited, so the work is N (2w + 1), not N^2.  A tile's K rows
-// ([key][d]) and V^T ([d][key]) sit in LDS, shared by the four waves; the next tile's rows are loaded into registers while the current
-// one is worked on.  The scores are computed transposed, S^T = K Q^T, so that a lane holds 16 scores of ONE query (4 key groups x 4
-// registers): the softmax statistics need two cross-lane steps per tile, and the probabilities feed P V (as O^T = V^T P^T) in the
-// registers they were computed in - the k order of that MFMA is permuted to match (key of k slot 8g + j = 16(2s + j/4) + 4g + j%4).
-// log2(e) * scale is folded into one multiply and exp2.  A score outside the band or the sequence is -inf before the exponential, i.e.
-// an exact 0; the masks are evaluated only on the tiles that cross a band or sequence edge.
+// 16-bit path (flash-style, mfma_f32_16x16x32), on the phases of window_attention_core.h: a workgroup of four waves owns 64 query rows
+// of one (sequence, head); only the 64-key tiles that meet [q0 - w, q1 + w] ∩ [0, N) are visited, so the work is N (2w + 1), not N^2.
+// It keeps K row-major and V transposed in LDS; the next tile's rows are loaded into registers while the current one is worked on.  The
+// scores are computed transposed, S^T = K Q^T, so that a lane holds 16 scores of ONE query (4 key groups x 4 registers): the softmax
+// statistics - this kernel's own part - need two cross-lane steps per tile, and the probabilities feed P V (as O^T = V^T P^T) in the
+// registers they were computed in.  log2(e) * scale is folded into one multiply and exp2.  A score outside the band or the sequence is
+// -inf before the exponential, i.e. an exact 0; the masks are evaluated only on the tiles that cross a band or sequence edge.
 //
 // fp32 path: one wave per (query, head), plain and exact (expf, sequential dots) - a correctness path, not a fast one.
+// anemoi_window_attention_plan (at the end) answers for all three MFMA kernels, forward and backward, from the same band functions.
 #include "window_attention_core.h"
 
 namespace anemoi {
 
 namespace {
-
-constexpr int kWinWaves = 4;
-constexpr int kWinQ = 16 * kWinWaves;  // query rows per workgroup
-constexpr int kWinK = 64;              // keys per tile
 
 struct WinArgs {
   const void* q;
@@ -41,57 +37,34 @@ struct WinArgs {
   hipStream_t stream;
 };
 
-// the score of query i, key j from the raw dot product, in the log2 domain (FANCY: softcap and / or ALiBi)
-template <bool FANCY>
-__device__ __forceinline__ float win_score(float dot, int i, int j, float sl2e, float scale, float softcap, float slope) {
-  if constexpr (!FANCY) {
-    return dot * sl2e;
-  } else {
-    float s = dot * scale;
-    if (softcap > 0.f) s = softcap * tanhf(s / softcap);
-    s -= slope * (float)abs(i - j);
-    return s * kLog2e;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- 16-bit, MFMA
 template <typename T, int D, bool FANCY>
 __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a) {
-  constexpr int KS = D + 8;       // K tile row stride in elements (16 B of padding against bank conflicts)
-  constexpr int VS = kWinK + 8;   // V^T tile row stride
-  constexpr int CH = D / 8;       // 16-byte chunks per row
-  constexpr int LOADS = kWinK * CH / (64 * kWinWaves);  // 16-byte chunks per thread and tile (K and V each)
-  static_assert(LOADS >= 1 && kWinK * CH % (64 * kWinWaves) == 0, "tile loads");
-  __shared__ __attribute__((aligned(16))) uint16_t k_lds[kWinK * KS];
+  constexpr int KT = win_tile_rows(kWinFwd, D);  // keys per tile
+  constexpr int VS = KT + 8;                     // V^T tile row stride
+  __shared__ __attribute__((aligned(16))) uint16_t k_lds[KT * (D + 8)];
   __shared__ __attribute__((aligned(16))) uint16_t vt_lds[D * VS];
 
   const int N = a.N, H = a.H, w = a.window;
-  const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-  const int q0 = blockIdx.x * kWinQ;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, c = lane & 15;
-  const int qw = q0 + wave * 16;  // this wave's first query
-  const int64_t row0 = (int64_t)b * N;
-  const T* __restrict__ qp = (const T*)a.q;
+  const WinLane p = win_lane(N, H);
+  const int h = p.h, q0 = p.first, tid = p.tid, g = p.g, c = p.c, qw = p.strip;
+  const int64_t row0 = p.row0;
   const T* __restrict__ kp = (const T*)a.k;
   const T* __restrict__ vp = (const T*)a.v;
-
-  // key range of the workgroup: the band of its query rows
-  const int lo = w < 0 ? 0 : max(0, q0 - w);
-  const int hi = w < 0 ? N : min(N, q0 + kWinQ + w);
-  const int ntiles = (hi - lo + kWinK - 1) / kWinK;
-
-  // Q of this lane's query as the B operand of S^T = K Q^T: Q[qw + c][8g + j + 32 s]
+  const WinBand band = win_band(q0, kWinOwn, w, N);  // the keys of the workgroup's queries
+  const int lo = band.lo, hi = band.hi, ntiles = win_tiles(band, KT);
+  // Three phases of this kernel stay spelt out - the owned-row load (load_row_frags), the element mask (in_band) and the accumulate
+  // GEMM (accumulate_transposed): through the helpers an instantiation took 4 VGPRs more, or the d = 64 kernel ran 1 % longer.  And
+  // the loader is called through a lambda, here and in the query pass: called directly, twice, the d = 64 kernels ran 3.7 % (with a
+  // window) and 6 % longer.  profiles/r24_window_attention_helpers_check.txt has the figures.
   const int qi = qw + c;
-  frag8 qf[D / 32];
-  {
+  frag8 qf[D / 32];  // Q of this lane's query as the B operand of S^T = K Q^T: Q[qw + c][8g + j + 32 s]
 #pragma unroll
-    for (int s = 0; s < D / 32; ++s) {
-      if (qi < N)
-        qf[s] = *reinterpret_cast<const frag8*>(qp + (row0 + qi) * a.ldq + (int64_t)h * D + 8 * g + 32 * s);
-      else
-        qf[s] = frag8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
+  for (int s = 0; s < D / 32; ++s) {
+    if (qi < N)
+      qf[s] = *reinterpret_cast<const frag8*>((const T*)a.q + (row0 + qi) * a.ldq + (int64_t)h * D + 8 * g + 32 * s);
+    else
+      qf[s] = frag8{0, 0, 0, 0, 0, 0, 0, 0};
   }
   const float sl2e = a.scale * kLog2e;
   const float slope = (FANCY && a.slopes) ? a.slopes[h] : 0.f;
@@ -101,54 +74,23 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
   for (int db = 0; db < D / 16; ++db) acc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
 
-  // the tile loader: chunk e of this thread = (key e / CH, 8 columns at 8 (e % CH)); keys beyond the range are zeros
-  frag8 kreg[LOADS], vreg[LOADS];
-  auto load_tile = [&](int kt) {
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) {
-      const int e = tid + u * 64 * kWinWaves, key = e / CH, col = 8 * (e % CH);
-      const int j = kt + key;
-      if (j < hi) {
-        kreg[u] = *reinterpret_cast<const frag8*>(kp + (row0 + j) * a.ldk + (int64_t)h * D + col);
-        vreg[u] = *reinterpret_cast<const frag8*>(vp + (row0 + j) * a.ldv + (int64_t)h * D + col);
-      } else {
-        kreg[u] = frag8{0, 0, 0, 0, 0, 0, 0, 0};
-        vreg[u] = frag8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
-  };
+  frag8 kreg[tile_loads<KT, D>()], vreg[tile_loads<KT, D>()];
+  auto load_tile = [&](int kt) { load_tile_pair<T, KT, D>(kreg, vreg, kp, a.ldk, vp, a.ldv, row0, (int64_t)h * D, kt, hi, tid); };
   if (ntiles > 0) load_tile(lo);
 
   for (int t = 0; t < ntiles; ++t) {
-    const int kt = lo + t * kWinK;
+    const int kt = lo + t * KT;
     __syncthreads();  // every wave is done with the previous tile
-#pragma unroll
-    for (int u = 0; u < LOADS; ++u) {
-      const int e = tid + u * 64 * kWinWaves, key = e / CH, col = 8 * (e % CH);
-      *reinterpret_cast<frag8*>(k_lds + key * KS + col) = kreg[u];
-#pragma unroll
-      for (int x = 0; x < 8; ++x) vt_lds[(col + x) * VS + key] = (uint16_t)vreg[u][x];
-    }
+    store_tile_rows<KT, D>(k_lds, kreg, tid);
+    store_tile_transposed<KT, D>(vt_lds, vreg, tid);
     __syncthreads();
-    if (t + 1 < ntiles) load_tile(kt + kWinK);  // in flight while this tile is worked on
+    if (t + 1 < ntiles) load_tile(kt + KT);  // in flight while this tile is worked on
 
-    // does the tile meet this wave's band at all, and does it need the masks?
-    const int klast = kt + kWinK - 1;
-    if (w >= 0 && (kt > qw + 15 + w || klast < qw - w)) continue;
-    const bool full = klast < N && qw + 15 < N && (w < 0 || (klast - qw <= w && qw + 15 - kt <= w));
-
-    // S^T[key 16 sb + 4 g + r][query c]
-    f32x4 st[4];
+    if (!tile_meets_band(kt, KT, qw, w)) continue;
+    const bool full = tile_is_full(kt, KT, qw, N, w);
+    f32x4 st[4];  // S^T[key 16 sb + 4 g + r][query c]
 #pragma unroll
-    for (int sb = 0; sb < 4; ++sb) {
-      f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < D / 32; ++s) {
-        const frag8 kf = *reinterpret_cast<const frag8*>(k_lds + (16 * sb + c) * KS + 8 * g + 32 * s);
-        z = mfma16<T>(kf, qf[s], z);
-      }
-      st[sb] = z;
-    }
+    for (int sb = 0; sb < 4; ++sb) st[sb] = score_block<T, D>(k_lds, sb, qf, g, c);
     float mx = -INFINITY;
 #pragma unroll
     for (int sb = 0; sb < 4; ++sb)
@@ -156,7 +98,7 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
       for (int r = 0; r < 4; ++r) {
         const int j = kt + 16 * sb + 4 * g + r;
         float x = win_score<FANCY>(st[sb][r], qi, j, sl2e, a.scale, a.softcap, slope);
-        if (!full && !(j < N && (w < 0 || abs(qi - j) <= w))) x = -INFINITY;
+        if (!full && !(j < N && (w < 0 || abs(qi - j) <= w))) x = -INFINITY;  // = in_band(qi, j, N, w) where qi < N
         st[sb][r] = x;
         mx = fmaxf(mx, x);
       }
@@ -171,34 +113,27 @@ __global__ __launch_bounds__(64 * kWinWaves) void win_attn_mfma_kernel(WinArgs a
     for (int db = 0; db < D / 16; ++db) acc[db] *= corr;
     frag8 pf[2];
 #pragma unroll
-    for (int sb = 0; sb < 4; ++sb)
+    for (int sb = 0; sb < 4; ++sb) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(st[sb][r] - base);
-        l += p;
-        pf[sb >> 1][4 * (sb & 1) + r] = to_bits<T>(p);
+        st[sb][r] = __builtin_amdgcn_exp2f(st[sb][r] - base);
+        l += st[sb][r];
       }
-    // O^T[d 16 db + 4 g + r][query c] += V^T[d][keys] P^T[keys][query]; k slot 8g + j of step s is key 32 s + 16 (j / 4) + 4 g + j % 4
+      pack_kslot<T>(pf, sb, st[sb]);
+    }
+    // O^T[d 16 db + 4 g + r][query c] += V^T[d][keys] P^T[keys][query]
 #pragma unroll
     for (int db = 0; db < D / 16; ++db) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) acc[db] = mfma16<T>(transposed_frag(vt_lds, VS, 16 * db + c, s, g), pf[s], acc[db]);
     }
   }
-
   // the row sum over the four key groups of the query
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if (qi >= N) return;
   const float inv = l > 0.f ? 1.f / l : 0.f;
-  T* __restrict__ op = (T*)a.out + (row0 + qi) * a.ldo + (int64_t)h * D;
-#pragma unroll
-  for (int db = 0; db < D / 16; ++db) {
-    Vec<T, 4> o;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) o.v[r] = from_float<T>(acc[db][r] * inv);
-    *reinterpret_cast<Vec<T, 4>*>(op + 16 * db + 4 * g) = o;
-  }
+  store_row_frags<T, D>((T*)a.out + (row0 + qi) * a.ldo + (int64_t)h * D, acc, inv, g);
   if (a.lse && g == 0) a.lse[(row0 + qi) * H + h] = (m + log2f(l)) * kLn2;
 }
 
@@ -216,8 +151,7 @@ __global__ __launch_bounds__(64) void win_attn_plain_kernel(WinArgs a) {
   const T* __restrict__ vp = (const T*)a.v + row0 * a.ldv + (int64_t)h * D;
   for (int x = lane; x < D; x += 64) q_s[x] = to_float(qp[x]);
   __syncthreads();
-  const int lo = w < 0 ? 0 : max(0, i - w);
-  const int hi = w < 0 ? N : min(N, i + w + 1);
+  const int lo = win_band(i, 1, w, N).lo, hi = win_band(i, 1, w, N).hi;
   const float slope = a.slopes ? a.slopes[h] : 0.f;
   float m = -INFINITY, l = 0.f, o0 = 0.f, o1 = 0.f;
   for (int j0 = lo; j0 < hi; j0 += 64) {
@@ -227,9 +161,7 @@ __global__ __launch_bounds__(64) void win_attn_plain_kernel(WinArgs a) {
       const T* kr = kp + (int64_t)j * a.ldk;
       float dot = 0.f;
       for (int x = 0; x < D; ++x) dot = fmaf(q_s[x], to_float(kr[x]), dot);
-      s = dot * a.scale;
-      if (a.softcap > 0.f) s = a.softcap * tanhf(s / a.softcap);
-      s -= slope * (float)abs(i - j);
+      s = plain_score(dot, i, j, a.scale, a.softcap, slope);
     }
     float mx = s;
 #pragma unroll
@@ -258,29 +190,6 @@ __global__ __launch_bounds__(64) void win_attn_plain_kernel(WinArgs a) {
   if (a.lse && lane == 0) a.lse[(row0 + i) * H + h] = m + logf(l);
 }
 
-template <typename T, int D>
-int launch_mfma(const WinArgs& a) {
-  const dim3 grid((unsigned)((a.N + kWinQ - 1) / kWinQ), (unsigned)(a.batch * a.H)), block(64 * kWinWaves);
-  if (a.softcap > 0.f || a.slopes)
-    hipLaunchKernelGGL((win_attn_mfma_kernel<T, D, true>), grid, block, 0, a.stream, a);
-  else
-    hipLaunchKernelGGL((win_attn_mfma_kernel<T, D, false>), grid, block, 0, a.stream, a);
-  return check_launch("win_attn_mfma_kernel");
-}
-
-template <typename T>
-int dispatch_16(const WinArgs& a) {
-  switch (a.d) {
-    case 32: return launch_mfma<T, 32>(a);
-    case 64: return launch_mfma<T, 64>(a);
-    default: return launch_mfma<T, 128>(a);
-  }
-}
-
-bool aligned(const void* p, int64_t ld, int elems) {
-  return ((uintptr_t)p % 16 == 0) && (ld % elems == 0);
-}
-
 }  // namespace
 
 }  // namespace anemoi
@@ -290,28 +199,47 @@ using namespace anemoi;
 extern "C" int anemoi_window_attention_fwd(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out,
                                            int64_t ldo, float* lse, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window,
                                            float scale, float softcap, const float* alibi_slopes, anemoi_dtype_t dtype, void* stream) {
-  ANEMOI_REQUIRE(batch >= 0 && seq_len >= 0 && H > 0 && d > 0, "window_attention_fwd: bad sizes batch=%d seq_len=%d H=%d d=%d", batch, seq_len,
-                 H, d);
-  if (d != 32 && d != 64 && d != 128) {
-    set_error("window_attention_fwd: head dimension %d not supported; supported: 32, 64, 128", d);
-    return ANEMOI_E_UNSUPPORTED;
-  }
-  ANEMOI_REQUIRE(dtype == ANEMOI_F32 || dtype == ANEMOI_BF16 || dtype == ANEMOI_F16, "window_attention_fwd: bad dtype %d", (int)dtype);
-  ANEMOI_REQUIRE((int64_t)batch * H < 65536, "window_attention_fwd: batch * H = %lld too large", (long long)batch * H);
+  if (int rc = win_check_args("window_attention_fwd", batch, seq_len, H, d, dtype, {ldq, ldk, ldv, ldo}, scale)) return rc;
   if (batch == 0 || seq_len == 0) return ANEMOI_OK;
   ANEMOI_REQUIRE(q && k && v && out, "window_attention_fwd: null pointer");
-  const int64_t A = (int64_t)H * d;
-  ANEMOI_REQUIRE(ldq >= A && ldk >= A && ldv >= A && ldo >= A, "window_attention_fwd: leading dimension smaller than H*d=%lld", (long long)A);
-  ANEMOI_REQUIRE(scale > 0.f, "window_attention_fwd: scale must be positive");
-  // a window of seq_len - 1 or more covers every key: unbounded (and no band edge such as q0 + 64 + w can overflow int32)
-  const int w = (window < 0 || window >= seq_len - 1) ? -1 : window;
-  WinArgs a{q, ldq, k, ldk, v, ldv, out, ldo, lse, alibi_slopes, batch, seq_len, H, d, w, scale, softcap, as_stream(stream)};
+  const WinArgs a{q, ldq, k, ldk, v, ldv, out, ldo, lse, alibi_slopes, batch, seq_len, H, d, win_window(window, seq_len), scale, softcap,
+                  as_stream(stream)};
   if (dtype == ANEMOI_F32) {
     hipLaunchKernelGGL(win_attn_plain_kernel<float>, dim3((unsigned)seq_len, (unsigned)(batch * H)), dim3(64), 0, a.stream, a);
     return check_launch("win_attn_plain_kernel");
   }
   // 16-byte loads of q / k / v rows, 8-byte stores of out rows
-  ANEMOI_REQUIRE(aligned(q, ldq, 8) && aligned(k, ldk, 8) && aligned(v, ldv, 8) && (uintptr_t)out % 8 == 0 && ldo % 4 == 0,
+  ANEMOI_REQUIRE(win_rows_aligned({{q, ldq}, {k, ldk}, {v, ldv}}, 8) && win_rows_aligned({{out, ldo}}, 4),
                  "window_attention_fwd: 16-bit q / k / v need 16-byte aligned rows (pointer and leading dimension), out 8-byte aligned rows");
-  return dtype == ANEMOI_BF16 ? dispatch_16<bf16_t>(a) : dispatch_16<f16_t>(a);
+  return with_win_instance(dtype, d, softcap > 0.f || alibi_slopes, [&](auto t, auto d_c, auto fancy_c) {
+    const dim3 grid((unsigned)((a.N + kWinOwn - 1) / kWinOwn), (unsigned)(a.batch * a.H)), block(64 * kWinWaves);
+    hipLaunchKernelGGL((win_attn_mfma_kernel<decltype(t), decltype(d_c)::value, decltype(fancy_c)::value>), grid, block, 0, a.stream, a);
+    return check_launch("win_attn_mfma_kernel");
+  });
+}
+
+// Host-only: what the kernels of `pass` do with the rows of one wave, from the band functions the kernels call.  fp32 (the plain kernels):
+// a workgroup is one wave and owns one row, every tile of its band is visited, and a tile is full if no lane of it reaches `hi`.
+extern "C" int anemoi_window_attention_plan(int32_t pass, int32_t seq_len, int32_t d, int32_t window, anemoi_dtype_t dtype, int32_t block,
+                                            int32_t wave, anemoi_window_attention_plan_t* out, int32_t* tile_class, int32_t tile_capacity) {
+  ANEMOI_REQUIRE(out != nullptr && (tile_class != nullptr || tile_capacity <= 0), "window_attention_plan: null out");
+  ANEMOI_REQUIRE(pass >= kWinFwd && pass <= kWinBwdKey, "window_attention_plan: unknown pass %d", pass);
+  if (int rc = win_check_args("window_attention_plan", 1, seq_len, 1, d, dtype, {}, 1.f)) return rc;
+  const bool plain = dtype == ANEMOI_F32;
+  const int own = plain ? 1 : kWinOwn, grid_x = (seq_len + own - 1) / own;
+  ANEMOI_REQUIRE(block >= 0 && block < (grid_x > 0 ? grid_x : 1) && wave >= 0 && wave < (plain ? 1 : kWinWaves),
+                 "window_attention_plan: no block %d, wave %d", block, wave);
+  const int w = win_window(window, seq_len), rows = win_tile_rows(plain ? kWinFwd : pass, d), first = block * own, strip = first + 16 * wave;
+  const WinBand band = win_band(first, own, w, seq_len);
+  *out = anemoi_window_attention_plan_t{w, own, grid_x, rows, band.lo, band.hi, win_tiles(band, rows)};
+  for (int t = 0; t < out->ntiles && t < tile_capacity; ++t) {
+    const int t0 = band.lo + t * rows;
+    if (plain)
+      tile_class[t] = t0 + rows <= band.hi ? ANEMOI_WINDOW_TILE_FULL : ANEMOI_WINDOW_TILE_MASKED;
+    else
+      tile_class[t] = !tile_meets_band(t0, rows, strip, w)          ? ANEMOI_WINDOW_TILE_SKIPPED
+                      : tile_is_full(t0, rows, strip, seq_len, w) ? ANEMOI_WINDOW_TILE_FULL
+                                                                  : ANEMOI_WINDOW_TILE_MASKED;
+  }
+  return ANEMOI_OK;
 }

@@ -430,16 +430,8 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
     WINDOW_HEAD_DIMS; query i attends keys j of its own sequence with |i - j| <= window (None or -1: all).  scale defaults to d^-1/2;
     softcap > 0 caps the scores; alibi_slopes fp32 [num_heads].  Returns out [batch * N, A] (and the fp32 LSE [batch * N, num_heads]).
     Differentiable in q, k, v: with autograd recording it runs as ``autograd.WindowAttentionFunction`` (HIP backward kernel)."""
-    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape:
-        raise ValueError(f"q, k and v must be 2-D of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
-    rows, A = q.shape
-    if num_heads <= 0 or A % num_heads:
-        raise ValueError(f"channels {A} not divisible by heads {num_heads}")
-    d = A // num_heads
-    if d not in WINDOW_HEAD_DIMS:
-        raise ValueError(f"window_attention: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
-    if batch_size <= 0 or rows % batch_size:
-        raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    _window_shape("window_attention", (q, k, v), num_heads, batch_size,
+                  f"q, k and v must be 2-D of one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
     if _needs_grad(q, k, v):
         from .autograd import WindowAttentionFunction
 
@@ -447,6 +439,23 @@ def window_attention(q: Tensor, k: Tensor, v: Tensor, num_heads: int, window: Op
         return (out, lse) if return_lse else out
     return _window_attention_fwd(q, k, v, num_heads, window, scale=scale, softcap=softcap, alibi_slopes=alibi_slopes, batch_size=batch_size,
                                  return_lse=return_lse)
+
+
+def _window_shape(op: str, operands, num_heads: int, batch_size: int, one_shape: str) -> tuple[int, int, int]:
+    """The shape checks ``window_attention`` and ``window_attention_bwd`` share: 2-D operands of one shape [rows, A] (``one_shape`` is the
+    op's message for that), heads that divide A into a supported head dimension, a batch size that divides the rows.  -> (rows, A, d)."""
+    q = operands[0]
+    if q.dim() != 2 or any(t.shape != q.shape for t in operands[1:]):
+        raise ValueError(one_shape)
+    rows, A = q.shape
+    if num_heads <= 0 or A % num_heads:
+        raise ValueError(f"channels {A} not divisible by heads {num_heads}")
+    d = A // num_heads
+    if d not in WINDOW_HEAD_DIMS:
+        raise ValueError(f"{op}: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
+    if batch_size <= 0 or rows % batch_size:
+        raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    return rows, A, d
 
 
 def _window_scalars(d: int, window: Optional[int], scale: Optional[float], softcap: Optional[float]) -> tuple[int, float, float]:
@@ -487,16 +496,8 @@ def window_attention_bwd(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Te
     ``out`` / ``lse`` are the forward's results, the scalars the forward's.  ``grads_out`` = (dq, dk, dv): write the gradients into these
     row-strided views, e.g. the three column slices of one [rows, 3A] gradient buffer.  ``delta``: the fp32 [rows, H] workspace the query
     pass fills and the key pass reads (allocated here by default); ``passes`` runs one pass alone, for timing."""
-    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape or d_out.shape != q.shape:
-        raise ValueError("q, k, v, out and d_out must be 2-D of one shape")
-    rows, A = q.shape
-    if num_heads <= 0 or A % num_heads:
-        raise ValueError(f"channels {A} not divisible by heads {num_heads}")
-    d = A // num_heads
-    if d not in WINDOW_HEAD_DIMS:
-        raise ValueError(f"window_attention_bwd: head dimension {d} not supported; supported: {set(WINDOW_HEAD_DIMS)}")
-    if batch_size <= 0 or rows % batch_size:
-        raise ValueError(f"rows {rows} not divisible by batch_size {batch_size}")
+    rows, A, d = _window_shape("window_attention_bwd", (q, k, v, out, d_out), num_heads, batch_size,
+                               "q, k, v, out and d_out must be 2-D of one shape")
     if tuple(lse.shape) != (rows, num_heads) or lse.dtype != torch.float32 or not lse.is_contiguous():
         raise ValueError(f"lse must be contiguous fp32 [{rows}, {num_heads}]")
     w, scale, cap = _window_scalars(d, window, scale, softcap)
@@ -521,6 +522,38 @@ def window_attention_bwd(d_out: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Te
                                                  _vec(alibi_slopes, "alibi_slopes", num_heads, torch.float32), int(passes), _dt(q), _stream())
     _lib.check(rc, "window_attention_bwd")
     return dq, dk, dv
+
+
+WINDOW_PASSES = ("forward", "backward_query", "backward_key")  # WinPass of csrc/window_attention_core.h
+WINDOW_TILE_CLASSES = ("skipped", "masked", "full")              # include/anemoi_hip.h: ANEMOI_WINDOW_TILE_*
+
+
+class WindowAttentionPlan(NamedTuple):
+    """What one wave of a window-attention kernel does with its sequence; fields as in anemoi_window_attention_plan_t, plus one of
+    WINDOW_TILE_CLASSES per streamed tile (tile t = rows [lo + t tile_rows, + tile_rows), rows from ``hi`` on read as zeros)."""
+    window: int
+    rows_per_block: int
+    grid_x: int
+    tile_rows: int
+    lo: int
+    hi: int
+    ntiles: int
+    tiles: tuple
+
+
+def window_attention_plan(op: str, seq_len: int, d: int, window: Optional[int], *, dtype: torch.dtype = torch.bfloat16, block: int = 0,
+                          wave: int = 0) -> WindowAttentionPlan:
+    """The band arithmetic of ``window_attention`` / ``window_attention_bwd`` (``op``: one of WINDOW_PASSES) for workgroup ``block`` and
+    wave ``wave`` of a sequence of ``seq_len`` rows: the functions the kernels themselves call (csrc/window_attention_core.h).  Host-only:
+    nothing is launched and no GPU is needed."""
+    w = -1 if window is None or window < 0 else int(min(window, 2**31 - 1))
+    capacity = max(int(seq_len), 0) // 32 + 2
+    out, classes = _lib.WindowAttentionPlan(), (_lib.C.c_int32 * capacity)()
+    rc = _lib.load().anemoi_window_attention_plan(WINDOW_PASSES.index(op), int(seq_len), int(d), w, _DT[dtype], int(block), int(wave), out,
+                                                  classes, capacity)
+    _lib.check(rc, "window_attention_plan")
+    return WindowAttentionPlan(**{name: getattr(out, name) for name, _ in out._fields_},
+                               tiles=tuple(WINDOW_TILE_CLASSES[c] for c in classes[:out.ntiles]))
 
 
 # ------------------------------------------------------------------------------------------ sparse projection

@@ -31,7 +31,7 @@ extern "C" {
 
 /* (The EDM diffusion entries - anemoi_noise_cond_fwd, anemoi_transport_assemble_input, anemoi_edm_output, anemoi_edm_update - were added at
  * 25 without a bump: they only add entry points, every earlier signature keeps its meaning.) */
-#define ANEMOI_HIP_ABI_VERSION 25
+#define ANEMOI_HIP_ABI_VERSION 26
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
 typedef enum { ANEMOI_ACT_NONE = 0, ANEMOI_ACT_GELU = 1 } anemoi_act_t;
@@ -715,6 +715,25 @@ int anemoi_window_attention_bwd(const void* q, int64_t ldq, const void* k, int64
                                 const void* d_out, int64_t ldg, const float* lse, void* dq, int64_t lddq, void* dk, int64_t lddk, void* dv,
                                 int64_t lddv, float* delta, int32_t batch, int32_t seq_len, int32_t H, int32_t d, int32_t window, float scale,
                                 float softcap, const float* alibi_slopes, int32_t passes, anemoi_dtype_t dtype, void* stream);
+
+/* What the kernels of the two ops above do with a sequence of seq_len rows, asked without launching anything (ABI 26).  HOST-ONLY: no HIP
+ * call, no device needed; the answer comes from the band functions of csrc/window_attention_core.h that the kernels themselves call.
+ * pass: 0 the forward, 1 the backward's query pass, 2 its key pass.  A workgroup owns rows_per_block rows of one (sequence, head) - queries,
+ * or keys in the key pass - and streams tiles of tile_rows rows of the other side, tile t = rows [lo + t tile_rows, + tile_rows), ntiles of
+ * them, rows from `hi` on read as zeros; 16-bit dtypes: 64 owned rows, wave 0..3 a strip of 16 of them; fp32: one row and one wave.
+ *   window: as normalised (-1 = unbounded);  grid_x: workgroups per (sequence, head) = ceil(seq_len / rows_per_block);
+ *   tile_class[t] (the first min(ntiles, tile_capacity) tiles; NULL with tile_capacity 0 to ask for the sizes only) for workgroup `block`
+ *   and wave `wave`: 0 the wave skips the tile (it holds no row in the band of the wave's rows), 1 it masks element by element, 2 every
+ *   pair is in the band and the sequence and no mask is evaluated.
+ * d, seq_len and dtype are refused as the ops refuse them. */
+#define ANEMOI_WINDOW_TILE_SKIPPED 0
+#define ANEMOI_WINDOW_TILE_MASKED 1
+#define ANEMOI_WINDOW_TILE_FULL 2
+typedef struct {
+  int32_t window, rows_per_block, grid_x, tile_rows, lo, hi, ntiles;
+} anemoi_window_attention_plan_t;
+int anemoi_window_attention_plan(int32_t pass, int32_t seq_len, int32_t d, int32_t window, anemoi_dtype_t dtype, int32_t block, int32_t wave,
+                                 anemoi_window_attention_plan_t* out, int32_t* tile_class, int32_t tile_capacity);
 
 /* Sparse projection of node rows by a constant CSR matrix, forward (and, on the transposed matrix, backward).
  * Replaces: SparseProjector._project_flattened (layers/sparse_projector.py:78-104: permute copy, torch.sparse.mm, permute copy) as

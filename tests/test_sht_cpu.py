@@ -173,12 +173,12 @@ def test_plan_refuses_bad_shapes():
 
 # ---------------------------------------------------------------------------------------------- ABI 25
 def test_abi_25_entries_are_declared_bound_built_and_cited():
-    assert _lib.ABI_VERSION == 25
+    assert _lib.ABI_VERSION >= 25  # the entries came with ABI 25; later versions keep them
     decl = header_functions()
     lib = _lib.load()
-    assert lib.anemoi_hip_abi_version() == 25
+    assert lib.anemoi_hip_abi_version() == _lib.ABI_VERSION
     text = open(HEADER).read()
-    assert "#define ANEMOI_HIP_ABI_VERSION 25" in text
+    assert f"#define ANEMOI_HIP_ABI_VERSION {_lib.ABI_VERSION}" in text
     for name in NEW_ENTRIES:
         assert name in decl and name in _lib.SIGNATURES, name
         assert len(_lib.SIGNATURES[name][0]) == decl[name], name
