@@ -146,6 +146,12 @@ SIGNATURES = {
     "anemoi_edm_output": ([_p, _i64, C.c_int, _p, _i32, _i64, _i64, _i64, _i64, _p, _i32, C.c_double, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p],
                           C.c_int),
     "anemoi_edm_update": ([_i32, _p, _p, _p, _p, _p, _i64, _i32, _p], C.c_int),
+    "anemoi_noise_cond_bwd_workspace_bytes": ([_i64, _i64, _i32, _i32], _i64),
+    "anemoi_noise_cond_bwd": ([_p, _i64, _i64, _p, _i64, _i64, C.c_int, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, C.c_int, _p, _p, _p, _p, _p, _i64, _i32,
+                               _i32, _i32, _p], C.c_int),
+    "anemoi_transport_assemble_input_bwd": ([_p, _i64, _i32, _p, _i64, _i32, _i32, _i32, C.c_int, _p], C.c_int),
+    "anemoi_edm_output_bwd": ([_p, _i32, _i64, _i64, _i64, _i64, _i64, _p, _i32, C.c_double, _i32, _p, _i64, _i32, C.c_int, _i32, _i32, _i32, _i32,
+                               _i32, _p], C.c_int),
 }
 
 

@@ -1,5 +1,6 @@
 """Autograd glue for the training path (scope row f1): torch.autograd.Functions whose forward AND backward are the HIP
-kernels of this package.  ``ops.linear`` / ``ops.layer_norm`` / ``ops.window_attention`` route here whenever autograd is recording; the edge attention op
+kernels of this package.  ``ops.linear`` / ``ops.layer_norm`` / ``ops.window_attention`` and the three launches around the EDM denoiser network
+(``ops.noise_cond`` / ``ops.transport_assemble_input`` / ``ops.edm_output``) route here whenever autograd is recording; the edge attention op
 carries its own registration (``ops.graph_transformer_attention``).
 
 Linear backward (reference: autograd of torch.nn.Linear as instantiated by layer_kernels, layers/utils.py:107-121):
@@ -432,3 +433,61 @@ def window_attention_qkv(qkv: Tensor, num_heads: int, window: Optional[int], *, 
     if batch_size <= 0 or qkv.shape[0] % batch_size:
         raise ValueError(f"rows {qkv.shape[0]} not divisible by batch_size {batch_size}")
     return WindowAttentionQKVFunction.apply(qkv, num_heads, window, scale, softcap, alibi_slopes, batch_size)[0]
+
+
+class NoiseCondFunction(torch.autograd.Function):
+    """``ops.noise_cond`` with its HIP backward (csrc/transport_bwd.hip): the gradients of the noise MLP's four parameters, in their dtypes.
+    The noise level, the embedder's frequencies and pi carry no gradient; the conditioning vector is recomputed, not stored."""
+
+    @staticmethod
+    def forward(ctx, values, frequencies, pi, log_quarter, rows, out_dtype, w1, b1, w2, b2):
+        ctx.log_quarter, ctx.rows = log_quarter, rows
+        ctx.set_materialize_grads(False)  # a destination the loss does not reach hands over None, not a tensor of zeros to sum
+        ctx.save_for_backward(values, frequencies, pi, w1, b1, w2, b2)
+        outs = ops._noise_cond_fwd(values, frequencies, w1, b1, w2, b2, pi=pi, log_quarter=log_quarter, rows=rows, out_dtype=out_dtype)
+        ctx.present = tuple(o is not None for o in outs)
+        return outs
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        values, frequencies, pi, w1, b1, w2, b2 = ctx.saved_tensors
+        # (a row-major gradient with a leading dimension - a column slice of a wider buffer - is read in place)
+        d_outs = tuple(None if d is None or not have else (d if d.dim() == 2 and d.stride(1) == 1 and d.stride(0) >= d.shape[1] else d.contiguous())
+                       for d, have in zip(d_outs, ctx.present))
+        grads = ops.noise_cond_backward(d_outs, ctx.rows, values, frequencies, w1, b1, w2, b2, pi=pi, log_quarter=ctx.log_quarter)
+        grads = tuple(g.to(p.dtype).view(p.shape) if need else None for g, p, need in zip(grads, (w1, b1, w2, b2), ctx.needs_input_grad[6:]))
+        return (None, None, None, None, None, None, *grads)
+
+
+class TransportAssembleInputFunction(torch.autograd.Function):
+    """``ops.transport_assemble_input`` with its HIP backward: the gradient of the node-attribute block (whose trainable columns are a
+    Parameter), summed over the groups.  x, the noised target and sigma carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, y, attrs, width, sigma, sigma_data, out_dtype):
+        ctx.col0 = x.shape[1] * x.shape[4] + y.shape[1] * y.shape[4]
+        ctx.attrs_shape = tuple(attrs.shape)
+        return ops._transport_assemble_input_fwd(x, y, attrs, width, sigma=sigma, sigma_data=sigma_data, out_dtype=out_dtype)
+
+    @staticmethod
+    def backward(ctx, d_rows):
+        n, a = ctx.attrs_shape
+        if d_rows.stride(1) != 1:
+            d_rows = d_rows.contiguous()
+        return None, None, ops.transport_assemble_input_backward(d_rows, ctx.col0, n, a), None, None, None, None
+
+
+class EdmOutputFunction(torch.autograd.Function):
+    """``ops.edm_output`` with its HIP backward: d_pred = c_out d_out in the network's row layout and dtype, the whole row written.  The
+    noised target and sigma carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, y, sigma, shape, sigma_data, out_dtype):
+        ctx.pred_shape, ctx.pred_dtype, ctx.sigma_data = tuple(pred.shape), pred.dtype, sigma_data
+        ctx.save_for_backward(sigma)
+        return ops._edm_output_fwd(pred, y, sigma, shape, sigma_data=sigma_data, out_dtype=out_dtype)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (sigma,) = ctx.saved_tensors
+        return ops.edm_output_backward(d_out, sigma, ctx.pred_shape, ctx.pred_dtype, sigma_data=ctx.sigma_data), None, None, None, None, None

@@ -19,7 +19,7 @@ LIBPATH = os.path.join(LIBDIR, "libanemoi_hip.so")
 EXT_PATH = os.path.join(LIBDIR, "libanemoi_torch.so")
 INCLUDE = os.path.join(REPO, "include")
 
-SOURCES = ["lib.cpp", "gt_attention.hip", "gt_attention_bwd.hip", "rowwise.hip", "model_edge.hip", "rowwise_bwd.hip", "linear.hip", "wgrad.hip", "peer.hip", "gt_chain2.hip", "gt_chain2_side.hip", "gt_rowchain.hip", "gt_embed_fold.hip", "gt_cluster_chain.hip", "gnn_chain.hip", "window_attention.hip", "window_attention_bwd.hip", "sparse_project.hip", "sht.hip", "transport.hip"]
+SOURCES = ["lib.cpp", "gt_attention.hip", "gt_attention_bwd.hip", "rowwise.hip", "model_edge.hip", "rowwise_bwd.hip", "linear.hip", "wgrad.hip", "peer.hip", "gt_chain2.hip", "gt_chain2_side.hip", "gt_rowchain.hip", "gt_embed_fold.hip", "gt_cluster_chain.hip", "gnn_chain.hip", "window_attention.hip", "window_attention_bwd.hip", "sparse_project.hip", "sht.hip", "transport.hip", "transport_bwd.hip"]
 # `--experiments`: the same sources compiled with -DANEMOI_EXPERIMENTS (timing switches that change what a kernel computes, in-kernel
 # timeline instantiations) plus the measured-and-superseded kernels under csrc/experiments/ -> lib/libanemoi_hip_exp.so, selected with
 # ANEMOI_HIP_LIB=<that path> by the A/B scripts in tools/.  Never the default: the product library carries none of it.

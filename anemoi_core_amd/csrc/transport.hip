@@ -2,36 +2,12 @@
 // samplers/transport_samplers.py): the noise conditioning, the two model edges with the EDM preconditioning, and the solver update.
 // Four element-wise kernels; every per-call scalar (sigma, the solver's coefficients) is read from DEVICE memory, so that a captured launch
 // replays for every step of a sampler.  Plain stores, one owner per output element, no atomics: results do not depend on the launch order.
-#include "common.h"
+#include "transport_core.h"  // the EDM coefficients and the conditioning vector, shared with the backward kernels (transport_bwd.hip)
 
 #include <type_traits>
 
 namespace anemoi {
 namespace {
-
-constexpr int kNoiseChannelsMax = 64;  // C: width of the noise embedding and of the first Linear
-constexpr int kNoiseCondMax = 32;      // cond_dim: width of the conditioning rows
-constexpr int kCondTileRows = 512;     // rows of one destination a workgroup of anemoi_noise_cond_fwd writes
-
-dim3 grid_for(int64_t n_threads) { return dim3((unsigned)((n_threads + 255) / 256)); }
-bool grid_fits(int64_t n_threads) { return (n_threads + 255) / 256 <= 0x7fffffffll; }
-
-// precision flag of the C ABI (0 = fp32, 1 = fp64) -> f(type_tag<float | double>)
-template <typename F>
-int dispatch_real(int32_t is_f64, F&& f) {
-  return is_f64 ? f(type_tag<double>{}) : f(type_tag<float>{});
-}
-
-// The EDM coefficients of one group in fp32, every operation rounded on its own in the order the reference's tensor expressions are
-// evaluated (transport/objectives.py:209-211): t = sd^2 + sigma^2, c_in = 1 / sqrt(t), c_skip = sd^2 / t, c_out = (sigma sd) / sqrt(t).
-struct EdmCoefficients {
-  float c_in, c_skip, c_out;
-};
-__device__ __forceinline__ EdmCoefficients edm_coefficients(float sigma, float sd, float sd2) {
-  const float t = __fadd_rn(__fmul_rn(sigma, sigma), sd2);
-  const float r = __fsqrt_rn(t);
-  return {__fdiv_rn(1.0f, r), __fdiv_rn(sd2, t), __fdiv_rn(__fmul_rn(sigma, sd), r)};
-}
 
 // ---------------------------------------------------------------------------------------------- 1. noise conditioning
 // grid (G, tiles of destination 0 + tiles of destination 1); every workgroup recomputes the group's conditioning vector (C / 2 sin / cos
@@ -43,29 +19,8 @@ __global__ __launch_bounds__(256) void noise_cond_kernel(const TV* __restrict__ 
                                                          int64_t rows0, int64_t ld0, int tiles0, TO* __restrict__ out1, int64_t rows1,
                                                          int64_t ld1, int C, int cond_dim) {
   __shared__ float emb[kNoiseChannelsMax], hid[kNoiseChannelsMax], cnd[kNoiseCondMax];
-  const int g = blockIdx.x, t = threadIdx.x, half = C / 2;
-  float v = (float)values[g];
-  if (transform == 1) v = __fdiv_rn(logf(v), 4.0f);
-  if (t < half) {
-    float a = __fmul_rn(v, freq[t]);
-    if (pi != nullptr) a = __fmul_rn(__fmul_rn(a, 2.0f), pi[0]);
-    emb[t] = sinf(a);  // (the precise functions: the argument reaches hundreds of radians)
-    emb[half + t] = cosf(a);
-  }
-  __syncthreads();
-  if (t < C) {
-    float acc = 0.f;
-    for (int k = 0; k < C; ++k) acc = fmaf(to_float(w1[t * C + k]), emb[k], acc);
-    acc += to_float(b1[t]);
-    hid[t] = acc / (1.0f + expf(-acc));  // SiLU
-  }
-  __syncthreads();
-  if (t < cond_dim) {
-    float acc = 0.f;
-    for (int k = 0; k < C; ++k) acc = fmaf(to_float(w2[t * C + k]), hid[k], acc);
-    cnd[t] = acc + to_float(b2[t]);
-  }
-  __syncthreads();
+  const int g = blockIdx.x, t = threadIdx.x;
+  noise_cond_vector<TW>((float)values[g], transform, freq, pi, w1, b1, w2, b2, C, cond_dim, emb, nullptr, hid, cnd);
   const bool first = (int)blockIdx.y < tiles0;
   TO* out = first ? out0 : out1;
   const int64_t rows = first ? rows0 : rows1, ld = first ? ld0 : ld1;

@@ -95,12 +95,13 @@ def ens_model_config(kind, num_channels, num_layers, num_heads, trainable, *, no
 
 def transport_model_config(kind, num_channels, num_layers, num_heads, trainable, *, noise_embedder="SinusoidalEmbeddings", noise_channels=32,
                            noise_cond_dim=16, objective="edm_diffusion", sigma_data=1.0, sigma_max=100.0, sigma_min=0.02, rho=7.0, source=None,
-                           inference_defaults=None, prefix="anemoi.models.layers", **embedder_kw):
+                           inference_defaults=None, training_condition=None, prefix="anemoi.models.layers", **embedder_kw):
     """The nested config of the reference's AnemoiTransportModelEncProcDec (training/src/anemoi/training/config/model/
     graphtransformer_transport_edm.yaml): ``model_config(kind, ...)`` whose encoder, processor and decoder take a ConditionalLayerNorm of
     ``condition_shape = noise_cond_dim`` as ``layer_kernels.LayerNorm``, plus the ``model.model.transport`` section.  ``noise_embedder``:
     "SinusoidalEmbeddings" (``max_period``) or "RandomFourierEmbeddings" (``scale``) of layers/diffusion.py; ``inference_defaults``:
-    {"sampling_schedule": {"schedule_type": ..., ...}, "sampler": {"sampler": ..., ...}}."""
+    {"sampling_schedule": {"schedule_type": ..., ...}, "sampler": {"sampler": ..., ...}}; ``training_condition``: {"distribution": one of
+    transport.SIGMA_TRAINING_DISTRIBUTIONS, its keywords ...}, what ``prepare_edm_training`` draws sigma from (absent when None)."""
     cfg = model_config(kind, num_channels, num_layers, num_heads, trainable, prefix=prefix)
     m = cfg["model"]
     for part in ("encoder", "processor", "decoder"):
@@ -114,4 +115,6 @@ def transport_model_config(kind, num_channels, num_layers, num_heads, trainable,
                                "noise_embedder": dict({"_target_": f"{prefix}.diffusion.{noise_embedder}", "num_channels": noise_channels}, **embedder_kw),
                                "sigma_data": sigma_data, "sigma_max": sigma_max, "sigma_min": sigma_min, "rho": rho, "source": dict(source or {}),
                                "inference_defaults": inference_defaults}
+    if training_condition is not None:
+        m["model"]["transport"]["training_condition"] = dict(training_condition)
     return cfg

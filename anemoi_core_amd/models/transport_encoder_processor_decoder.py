@@ -11,9 +11,14 @@ Around the network run exactly three launches of this library per dataset (ops.n
 ops.edm_output); no torch operation touches the state.  Ensemble members are folded into the batch, as in the ensemble model (the
 reference builds the hidden attributes for ``batch_size`` rows, :291, and fails on more than one member).
 
+Training: under autograd the three launches run as ``autograd.NoiseCondFunction`` / ``TransportAssembleInputFunction`` /
+``EdmOutputFunction`` (backward kernels: csrc/transport_bwd.hip), the network takes the trainable routes of its blocks, and
+``prepare_edm_training`` draws sigma from ``training_condition``, noises the target and returns the EDM loss weights; the loss itself stays
+with the caller.  Gradients reach every parameter; the noise level, the noised target and x carry none (refused by name).
+
 Not implemented, each refused with a message that names it: the tendency model, the stochastic-interpolant objective, a sharded model or
-grid, training, GNN / Transformer processors or mappers inside the transport model.  ``predict_step`` calls the pre- and post-processor
-modules (no fused normaliser / imputer chain)."""
+grid, GNN / Transformer processors or mappers inside the transport model, differentiating through a sampler.  ``predict_step`` calls the
+pre- and post-processor modules (no fused normaliser / imputer chain)."""
 from __future__ import annotations
 
 from typing import Optional
@@ -24,7 +29,8 @@ from torch import Tensor, nn
 from .. import ops
 from ..distributed.primitives import scoped_forward
 from ..distributed.shapes import BipartiteGraphShardInfo, GraphShardInfo, comm_size, get_shard_sizes
-from ..transport import EdmSettings, NoiseConditioningSettings, TransportSourceBuilder, get_transport_model_objective, sampling_source_specs
+from ..transport import (SIGMA_TRAINING_DISTRIBUTIONS, EdmSettings, NoiseConditioningSettings, TransportSourceBuilder, TransportSourceSpec,
+                         edm_loss_weight, get_transport_model_objective, sampling_source_specs)
 from ..utils.config import DotDict, instantiate
 from .encoder_processor_decoder import _PAD64, AnemoiModelEncProcDec, _retarget
 
@@ -180,9 +186,12 @@ class AnemoiTransportModelEncProcDec(AnemoiModelEncProcDec):
         x_latent_proc = self.processor(x=x_latent, batch_size=bse, shard_info=GraphShardInfo(nodes=shard_sizes_hidden, edges=es), edge_attr=ea,
                                        edge_index=ei, model_comm_group=model_comm_group, cond=c_hidden)
         if self.latent_skip:
-            from ..layers.block import _identity_index  # the add as one launch of this library
+            if torch.is_grad_enabled() and (x_latent_proc.requires_grad or x_latent.requires_grad):
+                x_latent_proc = x_latent_proc + x_latent  # training: the differentiable add (the ensemble model's route)
+            else:
+                from ..layers.block import _identity_index  # inference: the add as one launch of this library
 
-            x_latent_proc = ops.gather_add_rows(x_latent_proc, x_latent, _identity_index(x_latent))
+                x_latent_proc = ops.gather_add_rows(x_latent_proc, x_latent, _identity_index(x_latent))
         out = {}
         for ds in names:
             ea, ei, es = self.decoder_graph_provider[ds].get_edges(batch_size=bse, model_comm_group=model_comm_group)
@@ -190,6 +199,31 @@ class AnemoiTransportModelEncProcDec(AnemoiModelEncProcDec):
             out[ds] = self.decoder[ds]((x_latent_proc, data_latents[ds]), batch_size=bse, shard_info=info, edge_attr=ea, edge_index=ei,
                                        model_comm_group=model_comm_group, keep_x_dst_sharded=False, cond=(c_hidden, c_data[ds]))
         return out
+
+    # -- training ---------------------------------------------------------------------------------------------------------
+    def prepare_edm_training(self, target: dict, source: Optional[dict] = None, sigma: Optional[dict] = None) -> tuple:
+        """What one EDM training step feeds the model and its loss - the reference's EDMDiffusionTransportObjective.prepare
+        (training/train/methods/edm_diffusion.py:28-51): (y_noised, sigma, weights), each {name: tensor}, from the clean ``target``
+        {name: [batch, n_step_output, ensemble, grid, output vars]}.  sigma [batch, 1, ensemble, 1, 1]: one draw per sample and member from the
+        distribution ``training_condition`` names, shared by the datasets; source: ``transport_source`` (Gaussian by default);
+        y_noised = target + source sigma; weights = edm_loss_weight(sigma, sigma_data).  ``source`` / ``sigma`` given: used as they are.
+        Torch operations on the device of ``target``; the loss, mean(weights (model(x, y_noised, sigma) - target)^2), stays with the caller."""
+        if sigma is None:
+            config = dict(self.training_condition)
+            try:
+                name = config.pop("distribution")
+            except KeyError as exc:
+                raise ValueError("EDM training_condition must define 'distribution'.") from exc
+            if name not in SIGMA_TRAINING_DISTRIBUTIONS:
+                raise ValueError(f"Unknown EDM training condition distribution: {name}")
+            sigma = SIGMA_TRAINING_DISTRIBUTIONS[name](**config).sample({ds: tuple(t.shape) for ds, t in target.items()},
+                                                                      device=next(iter(target.values())).device)
+        weights = {ds: edm_loss_weight(s, self.edm.sigma_data) for ds, s in sigma.items()}
+        if source is None:
+            specs = {ds: TransportSourceSpec(shape=tuple(t.shape), device=t.device, dtype=t.dtype) for ds, t in target.items()}
+            source = self.transport_source.build(specs, default_kind="gaussian", error_context="training")
+        y_noised = {ds: target[ds] + source[ds] * sigma[ds] for ds in target}
+        return y_noised, sigma, weights
 
     # -- sampling ---------------------------------------------------------------------------------------------------------
     def build_sampling_source(self, x: dict, model_comm_group=None, grid_shard_sizes: Optional[dict] = None, default_kind: str = "gaussian") -> dict:

@@ -2262,10 +2262,20 @@ def noise_cond(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: 
     """The conditioning rows of one denoiser call, one launch (anemoi_noise_cond_fwd): values [G] (fp32 / fp64, cast to fp32), optionally
     log(v) / 4 (the EDM c_noise), the sin | cos embedding over ``frequencies`` [C / 2] fp32 (times 2 pi[0] when ``pi`` is given), the
     two Linear maps with SiLU between them, and the result [G, cond_dim] repeated ``rows[k]`` times per group into up to two outputs
-    [G rows[k], cond_dim] in ``out_dtype`` (default: the weights').  Returns one tensor per entry of ``rows`` (None for a 0 entry)."""
+    [G rows[k], cond_dim] in ``out_dtype`` (default: the weights').  Returns one tensor per entry of ``rows`` (None for a 0 entry).
+    Differentiable in the four parameters (``autograd.NoiseCondFunction``: anemoi_noise_cond_bwd); not in ``values``."""
     _dev(values, frequencies, w1, b1, w2, b2, pi)
-    if _needs_grad(values, w1, b1, w2, b2):
-        raise NotImplementedError("noise_cond: training the noise conditioning (a backward kernel) is not built; call it under torch.no_grad()")
+    if _needs_grad(values):
+        raise NotImplementedError("noise_cond: a gradient with respect to values (the noise level) is not built; detach it")
+    if _needs_grad(w1, b1, w2, b2):
+        from .autograd import NoiseCondFunction
+
+        return NoiseCondFunction.apply(values, frequencies, pi, log_quarter, tuple(rows), out_dtype, w1, b1, w2, b2)
+    return _noise_cond_fwd(values, frequencies, w1, b1, w2, b2, pi=pi, log_quarter=log_quarter, rows=rows, out_dtype=out_dtype)
+
+
+def _noise_cond_operands(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, pi: Optional[Tensor]) -> tuple:
+    """The checked, contiguous operands of the noise-conditioning kernels and (C, cond_dim, G)."""
     C, cond_dim, G = w1.shape[0], w2.shape[0], values.numel()
     if tuple(w1.shape) != (C, C) or tuple(w2.shape) != (cond_dim, C) or b1.numel() != C or b2.numel() != cond_dim or frequencies.numel() * 2 != C:
         raise ValueError(f"noise_cond: w1 [C, C], b1 [C], w2 [cond, C], b2 [cond], frequencies [C / 2]; got {tuple(w1.shape)}, {tuple(b1.shape)}, "
@@ -2274,10 +2284,14 @@ def noise_cond(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: 
         raise ValueError("noise_cond: frequencies and pi are fp32")
     if not (w1.dtype == b1.dtype == w2.dtype == b2.dtype):
         raise ValueError("noise_cond: the four parameters share one dtype")
+    return (values.reshape(-1).contiguous(), frequencies.contiguous(), w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()), (C, cond_dim, G)
+
+
+def _noise_cond_fwd(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, *, pi: Optional[Tensor] = None,
+                    log_quarter: bool = False, rows: tuple = (1,), out_dtype=None) -> tuple:
+    (values, frequencies, w1, b1, w2, b2), (C, cond_dim, G) = _noise_cond_operands(values, frequencies, w1, b1, w2, b2, pi)
     if not 1 <= len(rows) <= 2:
         raise ValueError("noise_cond: one or two destinations")
-    values, frequencies = values.reshape(-1).contiguous(), frequencies.contiguous()
-    w1, b1, w2, b2 = w1.contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()
     out_dtype = out_dtype or w1.dtype
     outs = [None if r == 0 else torch.empty((G * r, cond_dim), dtype=out_dtype, device=values.device) for r in rows]
     dst = [(0, 0, 0) if o is None else (o.data_ptr(), r, cond_dim) for o, r in zip(outs, rows)] + [(0, 0, 0)] * (2 - len(rows))
@@ -2288,15 +2302,61 @@ def noise_cond(values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: 
     return tuple(outs)
 
 
+def noise_cond_backward(d_outs: tuple, rows: tuple, values: Tensor, frequencies: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, *,
+                        pi: Optional[Tensor] = None, log_quarter: bool = False) -> tuple:
+    """(d_w1, d_b1, d_w2, d_b2) in fp32 from the gradients ``d_outs[k]`` [G rows[k], cond_dim] (row-major, any leading dimension; None: absent)
+    of ``noise_cond``'s outputs, two launches (anemoi_noise_cond_bwd): deterministic - fixed-order fp32 sums, no atomics."""
+    _dev(values, frequencies, w1, b1, w2, b2, pi, *d_outs)
+    (values, frequencies, w1, b1, w2, b2), (C, cond_dim, G) = _noise_cond_operands(values, frequencies, w1, b1, w2, b2, pi)
+    if not 1 <= len(d_outs) <= 2 or len(d_outs) != len(rows):
+        raise ValueError("noise_cond_backward: one gradient (or None) per destination, one or two destinations")
+    present = [d for d in d_outs if d is not None]
+    dtype = present[0].dtype if present else w1.dtype
+    src = []
+    for d, r in zip(d_outs, rows):
+        if d is None or r == 0 or G == 0:
+            src.append((0, 0, 0))
+            continue
+        if d.dim() != 2 or tuple(d.shape) != (G * r, cond_dim) or (cond_dim > 1 and d.stride(1) != 1) or d.dtype != dtype or (
+                d.shape[0] > 1 and d.stride(0) < cond_dim):
+            raise ValueError(f"noise_cond_backward: gradient [{G * r}, {cond_dim}] row-major in {dtype}, got {tuple(d.shape)} strides {d.stride()} {d.dtype}")
+        src.append((d.data_ptr(), r, d.stride(0) if d.shape[0] > 1 else cond_dim))
+    src += [(0, 0, 0)] * (2 - len(src))
+    lib = _lib.load()
+    ws_bytes = lib.anemoi_noise_cond_bwd_workspace_bytes(src[0][1], src[1][1], G, cond_dim)
+    ws = torch.empty((max(ws_bytes // 4, 1),), dtype=torch.float32, device=values.device)
+    grads = torch.empty((C * C + C + cond_dim * C + cond_dim,), dtype=torch.float32, device=values.device)
+    d_w1, d_b1, d_w2, d_b2 = grads[:C * C].view(C, C), grads[C * C:C * C + C], grads[C * C + C:C * C + C + cond_dim * C].view(cond_dim, C), grads[C * C + C + cond_dim * C:]
+    rc = lib.anemoi_noise_cond_bwd(*src[0], *src[1], _DT[dtype], values.data_ptr(), _real(values, "noise_cond: values"), 1 if log_quarter else 0,
+                                   frequencies.data_ptr(), 0 if pi is None else pi.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                   _dt(w1), d_w1.data_ptr(), d_b1.data_ptr(), d_w2.data_ptr(), d_b2.data_ptr(), ws.data_ptr(), ws.numel() * 4, G, C, cond_dim,
+                                   _stream())
+    _lib.check(rc, "noise_cond_bwd")
+    return d_w1, d_b1, d_w2, d_b2
+
+
 def transport_assemble_input(x: Tensor, y: Tensor, attrs: Optional[Tensor], width: int, *, sigma: Optional[Tensor] = None, sigma_data: float = 1.0,
                              out_dtype=None, out: Optional[Tensor] = None) -> Tensor:
     """The denoiser network's input rows, one launch (anemoi_transport_assemble_input):
     out[(b e n), :] = [x[b, t, e, n, :] | c_in[b, e] float(y[b, t, e, n, :]) | attrs[n, :] | zeros up to ``width``], c_in = 1 / sqrt(sigma_data^2
     + sigma^2) in fp32 from the device ``sigma`` [B E] (None: no scale).  x fp32 and y fp32 / fp64 are read in place through their strides.
-    ``out``: a [B E N, >= width] row-major tensor to write into (its columns beyond ``width`` stay untouched)."""
+    ``out``: a [B E N, >= width] row-major tensor to write into (its columns beyond ``width`` stay untouched).
+    Differentiable in ``attrs`` (``autograd.TransportAssembleInputFunction``: anemoi_transport_assemble_input_bwd); not in x, y or sigma."""
     _dev(x, y, attrs, sigma, out)
-    if _needs_grad(x, y, attrs, sigma):
-        raise NotImplementedError("transport_assemble_input: training (a backward kernel) is not built; call it under torch.no_grad()")
+    for name, t in (("x", x), ("y", y), ("sigma", sigma)):
+        if _needs_grad(t):
+            raise NotImplementedError(f"transport_assemble_input: a gradient with respect to {name} is not built; detach it")
+    if _needs_grad(attrs):
+        if out is not None:
+            raise ValueError("transport_assemble_input: out= is an inference-only argument")
+        from .autograd import TransportAssembleInputFunction
+
+        return TransportAssembleInputFunction.apply(x, y, attrs, width, sigma, float(sigma_data), out_dtype)
+    return _transport_assemble_input_fwd(x, y, attrs, width, sigma=sigma, sigma_data=sigma_data, out_dtype=out_dtype, out=out)
+
+
+def _transport_assemble_input_fwd(x: Tensor, y: Tensor, attrs: Optional[Tensor], width: int, *, sigma: Optional[Tensor] = None, sigma_data: float = 1.0,
+                                  out_dtype=None, out: Optional[Tensor] = None) -> Tensor:
     if x.dtype != torch.float32:
         raise NotImplementedError(f"transport_assemble_input: the data dtype is float32, got {x.dtype}")
     xs, ys = _state5(x, "transport_assemble_input: x"), _state5(y, "transport_assemble_input: y")
@@ -2325,15 +2385,42 @@ def transport_assemble_input(x: Tensor, y: Tensor, attrs: Optional[Tensor], widt
     return out
 
 
+def transport_assemble_input_backward(d_rows: Tensor, col0: int, n_nodes: int, n_attrs: int) -> Tensor:
+    """d_attrs [N, A] (d_rows' dtype) = the sum over the groups of columns col0 .. col0 + A - 1 of d_rows [G N, >= col0 + A], one launch
+    (anemoi_transport_assemble_input_bwd): groups in order, fp32 accumulation."""
+    _dev(d_rows)
+    if d_rows.dim() != 2 or n_nodes <= 0 or d_rows.shape[0] % n_nodes or d_rows.shape[1] < col0 + n_attrs or (d_rows.shape[1] > 1 and d_rows.stride(1) != 1):
+        raise ValueError(f"transport_assemble_input_backward: d_rows [G {n_nodes}, >= {col0 + n_attrs}] row-major, got {tuple(d_rows.shape)}")
+    G = d_rows.shape[0] // n_nodes
+    d_attrs = torch.empty((n_nodes, n_attrs), dtype=d_rows.dtype, device=d_rows.device)
+    rc = _lib.load().anemoi_transport_assemble_input_bwd(d_rows.data_ptr(), d_rows.stride(0) if d_rows.shape[0] > 1 else d_rows.shape[1], col0,
+                                                         d_attrs.data_ptr(), n_attrs, G, n_nodes, n_attrs, _dt(d_rows), _stream())
+    _lib.check(rc, "transport_assemble_input_bwd")
+    return d_attrs
+
+
 def edm_output(pred: Tensor, y: Optional[Tensor], sigma: Optional[Tensor], shape: tuple, *, sigma_data: float = 1.0, out_dtype=torch.float32,
                out: Optional[Tensor] = None) -> Tensor:
     """The denoised state from the network's output rows, one launch (anemoi_edm_output): with ``shape`` = (B, T_out, E, N, V_out),
     out[b, t, e, n, v] = c_skip float(y[b, t, e, n, v]) + c_out pred[(b e n), t V_out + v] with the fp32 EDM coefficients of the device
     ``sigma`` [B E]; y and sigma None: "(batch ensemble grid) (time vars) -> batch time ensemble grid vars" and the cast alone.  The result
-    is float32 or float64 (``out_dtype``, or the contiguous ``out``)."""
+    is float32 or float64 (``out_dtype``, or the contiguous ``out``).
+    Differentiable in ``pred`` (``autograd.EdmOutputFunction``: anemoi_edm_output_bwd); not in y or sigma."""
     _dev(pred, y, sigma, out)
-    if _needs_grad(pred, y, sigma):
-        raise NotImplementedError("edm_output: training (a backward kernel) is not built; call it under torch.no_grad()")
+    for name, t in (("y", y), ("sigma", sigma)):
+        if _needs_grad(t):
+            raise NotImplementedError(f"edm_output: a gradient with respect to {name} is not built; detach it")
+    if _needs_grad(pred):
+        if out is not None:
+            raise ValueError("edm_output: out= is an inference-only argument")
+        from .autograd import EdmOutputFunction
+
+        return EdmOutputFunction.apply(pred, y, sigma, tuple(shape), float(sigma_data), out_dtype)
+    return _edm_output_fwd(pred, y, sigma, shape, sigma_data=sigma_data, out_dtype=out_dtype, out=out)
+
+
+def _edm_output_fwd(pred: Tensor, y: Optional[Tensor], sigma: Optional[Tensor], shape: tuple, *, sigma_data: float = 1.0, out_dtype=torch.float32,
+                    out: Optional[Tensor] = None) -> Tensor:
     B, T_out, E, N, V_out = shape
     if pred.dim() != 2 or pred.shape[0] != B * E * N or pred.shape[1] < T_out * V_out or pred.stride(1) != 1:
         raise ValueError(f"edm_output: pred [{B * E * N}, >= {T_out * V_out}] row-major, got {tuple(pred.shape)}")
@@ -2355,6 +2442,36 @@ def edm_output(pred: Tensor, y: Optional[Tensor], sigma: Optional[Tensor], shape
                                        _stream())
     _lib.check(rc, "edm_output")
     return out
+
+
+def edm_output_backward(d_out: Tensor, sigma: Optional[Tensor], pred_shape: tuple, pred_dtype, *, sigma_data: float = 1.0,
+                        out: Optional[Tensor] = None) -> Tensor:
+    """d_pred [B E N, P] in ``pred_dtype`` from d_out [B, T_out, E, N, V_out] (fp32 / fp64, read in place through its five strides - an
+    expanded gradient has zeros among them), one launch (anemoi_edm_output_bwd): c_out d_out in the first T_out V_out columns (``sigma``
+    None: d_out itself), zeros in the rest.  ``out``: a row-major [B E N, P] tensor in ``pred_dtype`` to write into."""
+    _dev(d_out, sigma, out)
+    if d_out.dim() != 5 or any(st < 0 for st in d_out.stride()):
+        raise ValueError(f"edm_output_backward: d_out [batch, time, ensemble, grid, vars], got {tuple(d_out.shape)} strides {d_out.stride()}")
+    B, T_out, E, N, V_out = d_out.shape
+    rows, P = pred_shape
+    if rows != B * E * N or P < T_out * V_out:
+        raise ValueError(f"edm_output_backward: pred [{B * E * N}, >= {T_out * V_out}], got {tuple(pred_shape)}")
+    if sigma is not None:
+        if sigma.numel() != B * E:
+            raise ValueError(f"edm_output_backward: sigma has {sigma.numel()} values for {B * E} groups")
+        sigma = sigma.reshape(-1).contiguous()
+    if out is None:
+        out = torch.empty((rows, P), dtype=pred_dtype, device=d_out.device)
+    elif tuple(out.shape) != (rows, P) or out.dtype != pred_dtype or (P > 1 and out.stride(1) != 1) or (rows > 1 and out.stride(0) < P):
+        raise ValueError(f"edm_output_backward: out is row-major [{rows}, {P}] in {pred_dtype}, got {tuple(out.shape)} {out.dtype}")
+    d_pred = out
+    rc = _lib.load().anemoi_edm_output_bwd(d_out.data_ptr(), _real(d_out, "edm_output_backward: d_out"), *d_out.stride(),
+                                           0 if sigma is None else sigma.data_ptr(), 0 if sigma is None else _real(sigma, "edm_output: sigma"),
+                                           float(sigma_data), 0 if sigma is None else 1, d_pred.data_ptr(), d_pred.stride(0) if rows > 1 else P, P, _DT[pred_dtype],
+                                           B, E, N, T_out, V_out,
+                                           _stream())
+    _lib.check(rc, "edm_output_bwd")
+    return d_pred
 
 
 def edm_update_(mode: int, params: Tensor, y: Tensor, D: Tensor, aux1: Optional[Tensor] = None, aux2: Optional[Tensor] = None) -> Tensor:

@@ -1,5 +1,5 @@
-"""Sigma schedules of the EDM samplers - mirror of the reference's ``anemoi.models.transport.schedules`` (KarrasSigmaSchedule,
-LinearSigmaSchedule, CosineSigmaSchedule, ExponentialSigmaSchedule, SIGMA_SCHEDULES) with its validation and the exact final zero.
+"""Sigma schedules of the EDM samplers and the sigma distributions EDM training draws from - mirror of the reference's ``anemoi.models.transport.schedules`` (KarrasSigmaSchedule,
+LinearSigmaSchedule, CosineSigmaSchedule, ExponentialSigmaSchedule, SIGMA_SCHEDULES; SIGMA_TRAINING_DISTRIBUTIONS and the ``*_sigma_from_unit_time`` maps) with its validation and the exact final zero.
 
 A schedule is a handful of numbers: ``get_host_schedule`` computes it in float64 on the HOST, ``get_schedule(device)`` is that tensor
 uploaded.  The samplers take their control flow (``sigma_next == 0``, the churn window) and their per-step coefficients from the host
@@ -11,6 +11,8 @@ import math
 
 import torch
 from torch import Tensor
+
+from .paths import karras_sigma_from_unit_time
 
 DEFAULT_FINAL_SIGMA_EPS = 1e-10  # tolerance for a schedule that provides its final value itself
 
@@ -121,3 +123,84 @@ class ExponentialSigmaSchedule(SigmaSchedule):
 
 SIGMA_SCHEDULES = {"karras": KarrasSigmaSchedule, "linear": LinearSigmaSchedule, "cosine": CosineSigmaSchedule,
                    "exponential": ExponentialSigmaSchedule}
+
+
+# ---------------------------------------------------------------------------------------------- training: one sigma per sample and member
+def exponential_sigma_from_unit_time(unit_time: Tensor, *, sigma_max: float, sigma_min: float) -> Tensor:
+    """Unit time -> sigma, linear in log sigma."""
+    hi, lo = math.log(sigma_max), math.log(sigma_min)
+    return torch.exp(hi + unit_time * (lo - hi))
+
+
+def cosine_sigma_from_unit_time(unit_time: Tensor, *, sigma_max: float, sigma_min: float, s: float = 0.008) -> Tensor:
+    """Unit time -> sigma along the cosine alpha-bar path."""
+    t_max = (2 * math.atan(sigma_max) / math.pi) * (1 + s) - s
+    t_min = (2 * math.atan(sigma_min) / math.pi) * (1 + s) - s
+    t = t_max + unit_time * (t_min - t_max)
+    alpha_bar = torch.cos((t + s) / (1 + s) * torch.pi / 2) ** 2
+    return torch.sqrt((1 - alpha_bar) / alpha_bar)
+
+
+def _validate_condition_shape(shape: dict) -> tuple:
+    names = list(shape)
+    if not names:
+        raise ValueError("Condition distribution requires at least one dataset shape.")
+    ref = shape[names[0]]
+    if len(ref) != 5:
+        raise ValueError("Expected 5D tensor shape (batch, time, ensemble, grid, vars) for transport conditions.")
+    for name, sh in shape.items():
+        if len(sh) != 5:
+            raise ValueError(f"Expected 5D tensor shape for dataset '{name}'.")
+        if sh[0] != ref[0] or sh[2] != ref[2]:
+            raise ValueError("Batch or ensemble dimension mismatch across datasets when sampling conditions.")
+    return ref[0], ref[2]
+
+
+class SigmaTrainingDistribution:
+    """One sigma per sample and ensemble member: ``sample`` draws one ``torch.rand((batch, ensemble))`` and maps it through
+    ``_sigma_from_unit_time``; the datasets share the one resulting tensor [batch, 1, ensemble, 1, 1]."""
+
+    def __init__(self, sigma_max: float, sigma_min: float) -> None:
+        SigmaSchedule._validate_sigma_parameters(sigma_max=sigma_max, sigma_min=sigma_min)
+        self.sigma_max, self.sigma_min = float(sigma_max), float(sigma_min)
+
+    def _sigma_from_unit_time(self, unit_time: Tensor) -> Tensor:
+        raise NotImplementedError
+
+    def sample(self, shape: dict, *, device, dtype=None) -> dict:
+        batch_size, ensemble_size = _validate_condition_shape(shape)
+        unit_time = torch.rand((batch_size, ensemble_size), device=device, dtype=dtype)
+        base = self._sigma_from_unit_time(unit_time)[:, None, :, None, None]
+        return {name: base for name in shape}
+
+
+class KarrasSigmaTrainingDistribution(SigmaTrainingDistribution):
+    def __init__(self, sigma_max: float, sigma_min: float, rho: float = 7.0) -> None:
+        super().__init__(sigma_max=sigma_max, sigma_min=sigma_min)
+        self.rho = float(rho)
+
+    def _sigma_from_unit_time(self, unit_time: Tensor) -> Tensor:
+        return karras_sigma_from_unit_time(unit_time, sigma_max=self.sigma_max, sigma_min=self.sigma_min, rho=self.rho)
+
+
+class LinearSigmaTrainingDistribution(SigmaTrainingDistribution):
+    def _sigma_from_unit_time(self, unit_time: Tensor) -> Tensor:
+        return self.sigma_max + unit_time * (self.sigma_min - self.sigma_max)
+
+
+class ExponentialSigmaTrainingDistribution(SigmaTrainingDistribution):
+    def _sigma_from_unit_time(self, unit_time: Tensor) -> Tensor:
+        return exponential_sigma_from_unit_time(unit_time, sigma_max=self.sigma_max, sigma_min=self.sigma_min)
+
+
+class CosineSigmaTrainingDistribution(SigmaTrainingDistribution):
+    def __init__(self, sigma_max: float, sigma_min: float, s: float = 0.008) -> None:
+        super().__init__(sigma_max=sigma_max, sigma_min=sigma_min)
+        self.s = float(s)
+
+    def _sigma_from_unit_time(self, unit_time: Tensor) -> Tensor:
+        return cosine_sigma_from_unit_time(unit_time, sigma_max=self.sigma_max, sigma_min=self.sigma_min, s=self.s)
+
+
+SIGMA_TRAINING_DISTRIBUTIONS = {"karras": KarrasSigmaTrainingDistribution, "linear": LinearSigmaTrainingDistribution,
+                                "cosine": CosineSigmaTrainingDistribution, "exponential": ExponentialSigmaTrainingDistribution}

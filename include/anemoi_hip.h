@@ -30,7 +30,8 @@ extern "C" {
 #endif
 
 /* (The EDM diffusion entries - anemoi_noise_cond_fwd, anemoi_transport_assemble_input, anemoi_edm_output, anemoi_edm_update - were added at
- * 25 without a bump: they only add entry points, every earlier signature keeps its meaning.) */
+ * 25 without a bump: they only add entry points, every earlier signature keeps its meaning.  The same holds for their backward entries -
+ * anemoi_noise_cond_bwd (+ _workspace_bytes), anemoi_transport_assemble_input_bwd, anemoi_edm_output_bwd - added at 26.) */
 #define ANEMOI_HIP_ABI_VERSION 26
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
@@ -871,6 +872,42 @@ int anemoi_edm_output(const void* pred, int64_t ldp, anemoi_dtype_t pred_dtype, 
  *   mode 5 DPMPP_FINAL:  y = D */
 int anemoi_edm_update(int32_t mode, const double* params, void* y, const void* D, void* aux1, void* aux2, int64_t n, int32_t solver_f64,
                       void* stream);
+
+/* ---- Backward of the three launches around the denoiser network (csrc/transport_bwd.hip): what torch autograd derives for the reference's
+ * tensor expressions named above.  fp32 accumulation in a fixed order, plain stores with one owner per element, no atomics, no host
+ * synchronisation, every per-call scalar read from DEVICE memory: a captured training step replays bit-equal.  The conditioning vector
+ * and the EDM coefficients are the forward's own (csrc/transport_core.h). ---- */
+
+/* Bytes of fp32 workspace anemoi_noise_cond_bwd needs: one partial per (group, 512-row tile of destination 0 then 1, column). */
+int64_t anemoi_noise_cond_bwd_workspace_bytes(int64_t rows0, int64_t rows1, int32_t G, int32_t cond_dim);
+
+/* Gradients of the noise MLP's parameters from the gradients of the conditioning rows (anemoi_noise_cond_fwd's outputs).
+ *   s_g = sum_k sum_r d_out_k[(g rows_k + r), 0:cond_dim]     stage 1: one partial per (group, tile), then summed in tile order
+ *   e, p = W1 e + b1, h = silu(p) recomputed as the forward computes them;  over the groups in order:
+ *   d_b2 = sum_g s_g;  d_w2 = sum_g s_g h_g^T;  dh = W2^T s_g;  dp = dh sigmoid(p) (1 + p (1 - sigmoid(p)));  d_b1 = sum_g dp;
+ *   d_w1 = sum_g dp e_g^T.
+ * d_out_k in dtype with leading dimension ld_k (NULL or rows_k = 0: absent); rows are read with 16-byte loads when cond_dim, ld_k and the
+ * base address allow.  d_w1 [C, C], d_b1 [C], d_w2 [cond_dim, C], d_b2 [cond_dim]: fp32, every element written.  There is no gradient
+ * to values, frequencies or pi.  Two launches. */
+int anemoi_noise_cond_bwd(const void* d_out0, int64_t rows0, int64_t ld0, const void* d_out1, int64_t rows1, int64_t ld1, anemoi_dtype_t dtype,
+                          const void* values, int32_t values_f64, int32_t transform, const float* frequencies, const float* pi, const void* w1,
+                          const void* b1, const void* w2, const void* b2, anemoi_dtype_t w_dtype, float* d_w1, float* d_b1, float* d_w2,
+                          float* d_b2, void* workspace, int64_t workspace_bytes, int32_t G, int32_t C, int32_t cond_dim, void* stream);
+
+/* Gradient of the node attributes anemoi_transport_assemble_input concatenates (its only differentiable operand: the trainable columns are
+ * a Parameter):  d_attrs[n, a] = sum_g float(d_rows[(g N + n), col0 + a]), groups in order, fp32 accumulation, written in dtype.
+ * col0 = T_in V_in + T_out V_out; the alignment columns past the attributes are not read. */
+int anemoi_transport_assemble_input_bwd(const void* d_rows, int64_t ldr, int32_t col0, void* d_attrs, int64_t lda, int32_t G, int32_t N, int32_t A,
+                                        anemoi_dtype_t dtype, void* stream);
+
+/* Gradient of the network's output rows from the gradient of anemoi_edm_output's result:
+ *   d_pred[(g N + n), t V_out + v] = round(c_out[g] float(d_out[b, t, e, n, v]))  (precondition = 0: c_out = 1), c_out as in the forward;
+ *   d_pred[(g N + n), T_out V_out .. P - 1] = 0: the whole row of P columns is written (the decoder's backward reads all of it).
+ * d_out: fp32 or fp64, read in place through its five element strides, each >= 0 (0: an expanded gradient).  There is no gradient to y or
+ * sigma. */
+int anemoi_edm_output_bwd(const void* d_out, int32_t d_out_f64, int64_t gs_b, int64_t gs_t, int64_t gs_e, int64_t gs_n, int64_t gs_v,
+                          const void* sigma, int32_t sigma_f64, double sigma_data, int32_t precondition, void* d_pred, int64_t ldp, int32_t P,
+                          anemoi_dtype_t pred_dtype, int32_t B, int32_t E, int32_t N, int32_t T_out, int32_t V_out, void* stream);
 
 #ifdef __cplusplus
 }
