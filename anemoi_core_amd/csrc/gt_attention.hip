@@ -15,10 +15,10 @@
 // fe_pad fp32 edge features (wave-uniform -> scalar loads) and at the end apply W' to the weighted feature
 // sum.  HBM traffic per layer drops from 2(4ND + MD) to 2*4ND + 4*M*fe_pad bytes.
 //
-// This file: the fused-edge forward kernel.  In front of it gt_attention_core.h (build-time knobs, the packed dot product), behind
-// it gt_attention_fwd_host.h (the materialised-E, generic and pack kernels, the launches, the C entry points); which kernel a call
-// runs is decided by plan_attention (gt_attention_plan.h).  csrc/experiments/gt_attention_r05_variants.hip is built the same way
-// around its own kernel.
+// This file: the fused-edge forward kernel.  In front of it gt_attention_core.h (build-time knobs, the packed dot product, the small
+// helpers the wave kernels share), behind it gt_attention_fwd_host.h (the materialised-E, generic and pack kernels, the launches, the
+// C entry points); which kernel a call runs is decided by plan_attention (gt_attention_plan.h).
+// csrc/experiments/gt_attention_r05_variants.hip is built the same way around its own kernel.
 #include "gt_attention_core.h"
 
 namespace anemoi {
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt
       const int idx = threadIdx.x + it * 64 * kWavesPerBlock;
       if (idx < kTotal) {
         const int c = idx / kQ, qq = idx % kQ;  // channel c, features 4 qq .. 4 qq + 3 -> chunk layout [feature][channel]
-        float* dst = w_lds + (c / VEC) * L::kChunk + (qq * 4) * VEC + (c % VEC);
+        float* dst = w_lds + (c / VEC) * L::kChunk + (qq * 4) * VEC + (c % VEC);  // L::at(c, 4 qq), in this kernel's own pointer steps
         dst[0] = tmp[it].x;
         dst[VEC] = tmp[it].y;
         dst[2 * VEC] = tmp[it].z;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt
     asm volatile("" ::: "memory");
     h_d = n_d, h_beg = n_beg, h_end = n_end;
     h_q = *reinterpret_cast<const Raw*>(q + (int64_t)h_d * ldq + c0);
-    h_src = (lane < h_end - h_beg) ? row[h_beg + lane] : 0;
+    h_src = chunk_ids(row, h_beg, h_end - h_beg, lane);
     if (i + waves_in_xcd < d_hi) load_scalars(i + waves_in_xcd, n_d, n_beg, n_end);
     const int d = h_d, beg = h_beg, end = h_end;
     const Raw q_raw = h_q;
@@ -121,9 +121,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt
       acc[j] = 0.f;
     }
     // Scores are kept in units of 1/scale (s' = <q, k + e>, the softmax argument is scale * s'): the scale rides in the
-    // exponent's multiplier (one multiply per edge less).
-    // Edge loop in chunks of 64: the source ids of a chunk are fetched with ONE coalesced load (lane j holds
-    // row[chunk + j]) and broadcast with v_readlane, so row loads never wait on a dependent scalar load.
+    // exponent's multiplier (one multiply per edge less).  The edge loop runs in chunks of 64 (chunk_ids).
     int chunk = beg, n = min(64, end - beg), my_src = h_src;  // the first chunk's ids came with the header
     Raw kb[PF], vb[PF];
     float fb[PF][FE_PAD];
@@ -172,7 +170,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, ANEMOI_ATTN_MIN_WAVES) void gt
     for (; chunk < end; chunk += 64) {
       if (chunk != beg) {
         n = min(64, end - chunk);
-        my_src = (lane < n) ? row[chunk + lane] : 0;
+        my_src = chunk_ids(row, chunk, n, lane);
       }
 #pragma unroll
       for (int st = 0; st < PF; ++st) fetch(st, kb[st], vb[st], fb[st]);

@@ -18,9 +18,8 @@
 // src pass 2(2 N_src D) + gathers of q/dO + 8 M H.
 //
 // Which kernels a call runs, on which lane layout and grids, is decided by plan_attention (gt_attention_plan.h); the launch
-// functions at the end of each half of this file launch what the plan names.
-#include "common.h"
-#include "gt_attention_plan.h"
+// functions at the end of each half of this file launch what the plan names; the shared device helpers are gt_attention_core.h's.
+#include "gt_attention_core.h"
 
 namespace anemoi {
 
@@ -64,30 +63,38 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_kernel(
     load_vec<T, VEC>(d_out + (int64_t)d * lddo + c0, gv);
     load_vec<T, VEC>(out + (int64_t)d * ldo + c0, ov);
     const float m = lse[(int64_t)d * H + h];
-    float Dj;
+    // One edge, for the D pre-pass and the main pass alike: p_e; pc = c_e p_e, the value-side weight (dE's second term, dv in the source
+    // pass; with dropout o_d = sum_e c_e p_e (v + E), c_e = 0 or 1 / (1 - p)); the head's <dO, v + E>; the k + E slice.
+    struct Edge { float p, pc, da, ke[VEC]; };
+    auto edge = [&](int ei) {
+      const int s = row[ei];
+      Edge r;
+      float vv[VEC], ev[VEC];
+      load_vec<T, VEC>(k + (int64_t)s * ldk + c0, r.ke);
+      load_vec<T, VEC>(v + (int64_t)s * ldv + c0, vv);
+      load_vec<T, VEC>(e + (int64_t)ei * lde + c0, ev);
+      float dot = 0.f, da = 0.f;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        r.ke[i] += ev[i];
+        dot = fmaf(qv[i], r.ke[i], dot);
+        da = fmaf(gv[i], vv[i] + ev[i], da);
+      }
+      r.p = __expf(group_sum<LPH>(dot) * scale - m);
+      r.pc = dropout_weight(r.p, drop_seed, ei, h, drop_p, inv_keep);
+      r.da = group_sum<LPH>(da);
+      return r;
+    };
+    float Dj = 0.f;
     if constexpr (sizeof(T) == 2) {
       // A 16-bit `out` carries its rounding (2^-9 |o|) into D = <dO, o>.  When one edge dominates the softmax, <dO, v + E> - D of
       // that edge cancels and the rounding of `out` is what is left of its dS: dq / dk off by up to 1.3x the suite's 16-bit bound
       // (tests/test_attention_shapes_gpu.py).  So D = sum_e c_e p_e <dO, v_s + E_e> in fp32 from a pass of its own over the edges
       // (the rows are gathered again below, from the caches), and `out` is not read.
-      float dsum = 0.f;
       for (int ei = beg; ei < end; ++ei) {
-        const int s = row[ei];
-        float kv[VEC], vv[VEC], ev[VEC];
-        load_vec<T, VEC>(k + (int64_t)s * ldk + c0, kv);
-        load_vec<T, VEC>(v + (int64_t)s * ldv + c0, vv);
-        load_vec<T, VEC>(e + (int64_t)ei * lde + c0, ev);
-        float dot = 0.f, da = 0.f;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
-          dot = fmaf(qv[i], kv[i] + ev[i], dot);
-          da = fmaf(gv[i], vv[i] + ev[i], da);
-        }
-        const float p = __expf(group_sum<LPH>(dot) * scale - m);
-        const float pc = drop_p > 0.f ? p * attn_dropout_scale(drop_seed, ei, h, drop_p, inv_keep) : p;
-        dsum = fmaf(pc, group_sum<LPH>(da), dsum);
+        const Edge w = edge(ei);
+        Dj = fmaf(w.pc, w.da, Dj);
       }
-      Dj = dsum;
     } else {
       float dd = 0.f;
 #pragma unroll
@@ -95,32 +102,17 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_kernel(
       Dj = group_sum<LPH>(dd);
     }
     for (int ei = beg; ei < end; ++ei) {
-      const int s = row[ei];
-      float kv[VEC], vv[VEC], ev[VEC];
-      load_vec<T, VEC>(k + (int64_t)s * ldk + c0, kv);
-      load_vec<T, VEC>(v + (int64_t)s * ldv + c0, vv);
-      load_vec<T, VEC>(e + (int64_t)ei * lde + c0, ev);
-      float dot = 0.f, da = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        kv[i] += ev[i];
-        dot = fmaf(qv[i], kv[i], dot);
-        da = fmaf(gv[i], vv[i] + ev[i], da);
-      }
-      const float p = __expf(group_sum<LPH>(dot) * scale - m);
-      // with dropout o_d = sum_e c_e p_e (v + E) (c_e = 0 or 1 / (1 - p)): d p_e = c_e <dO, v + E>, D_d = <dO, o_d> as before, and
-      // the value-side weight (dE's second term, dv in the source pass) is c_e p_e
-      const float pc = drop_p > 0.f ? p * attn_dropout_scale(drop_seed, ei, h, drop_p, inv_keep) : p;
-      const float ds = (pc * group_sum<LPH>(da) - p * Dj) * scale;  // dS_e / sqrt(C)
+      const Edge w = edge(ei);
+      const float ds = (w.pc * w.da - w.p * Dj) * scale;  // dS_e / sqrt(C)
       float dev[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) {
-        acc[i] = fmaf(ds, kv[i], acc[i]);
-        dev[i] = fmaf(ds, qv[i], pc * gv[i]);
+        acc[i] = fmaf(ds, w.ke[i], acc[i]);
+        dev[i] = fmaf(ds, qv[i], w.pc * gv[i]);
       }
       store_vec<T, VEC>(de + (int64_t)ei * ldde + c0, dev);
       if ((lane % LPH) == 0) {
-        p_ws[(int64_t)ei * H + h] = pc;
+        p_ws[(int64_t)ei * H + h] = w.pc;
         ds_ws[(int64_t)ei * H + h] = ds;
       }
     }
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_src_kernel(
   constexpr int PF = 2;
   for (int chunk = beg; chunk < end; chunk += 64) {
     const int n = min(64, end - chunk);
-    const int my_e = (lane < n) ? edge_ids[chunk + lane] : 0;
+    const int my_e = chunk_ids(edge_ids, chunk, n, lane);
     const int my_d = (lane < n) ? edge_dst[my_e] : 0;
     Raw qb[PF], gb[PF];
     float pb[PF], sb[PF];
@@ -268,13 +260,18 @@ int launch_src_pass(const BwdArgs& a, const AttnPlan& p) {
   return check_launch("gt_attn_bwd_src_kernel");
 }
 
+// the plan of a backward call; `own`: the row operands only this op has, next to the eight both have
+template <typename T>
+AttnPlan plan_of(AttnOp op, const BwdArgs& a, int fe_pad, std::initializer_list<RowOperand> own) {
+  const bool aligned = rows_aligned({{a.q, a.ldq}, {a.k, a.ldk}, {a.v, a.ldv}, {a.out, a.ldo}, {a.d_out, a.lddo}, {a.dq, a.lddq},
+                                     {a.dk, a.lddk}, {a.dv, a.lddv}}, align_elems(op, sizeof(T))) && rows_aligned(own, align_elems(op, sizeof(T)));
+  return plan_attention(op, a.H, a.C, fe_pad, a.n_dst, a.n_src, aligned, false, 0);
+}
+
 template <typename T>
 int launch(const BwdArgs& a) {
   const float scale = 1.0f / sqrtf((float)a.C);
-  const bool aligned = rows_aligned({{a.q, a.ldq}, {a.k, a.ldk}, {a.v, a.ldv}, {a.e, a.lde}, {a.out, a.ldo}, {a.d_out, a.lddo},
-                                     {a.dq, a.lddq}, {a.dk, a.lddk}, {a.dv, a.lddv}, {a.de, a.ldde}},
-                                    align_elems(AttnOp::Bwd, sizeof(T)));
-  const AttnPlan p = plan_attention(AttnOp::Bwd, a.H, a.C, 0, a.n_dst, a.n_src, aligned, false, 0);
+  const AttnPlan p = plan_of<T>(AttnOp::Bwd, a, 0, {{a.e, a.lde}, {a.de, a.ldde}});
   if (p.route == AttnRoute::Wave)
     return with_lane_layout(p, [&](auto vec_c, auto lph_c) {
       constexpr int VEC = decltype(vec_c)::value, LPH = decltype(lph_c)::value;
@@ -332,7 +329,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_fused_kernel(
   const int h = lane / LPH;
   for (int idx = threadIdx.x; idx < 64 * VEC * FE_PAD; idx += 64 * kBwdWaves) {
     const int c = idx / FE_PAD, f = idx % FE_PAD;
-    w_lds[(c / VEC) * L::kChunk + f * VEC + (c % VEC)] = w_packed[idx];
+    w_lds[L::at(c, f)] = w_packed[idx];
   }
   __syncthreads();
   const float* wl = w_lds + lane * L::kChunk;
@@ -380,7 +377,7 @@ __global__ __launch_bounds__(64 * kBwdWaves) void gt_attn_bwd_dst_fused_kernel(
     constexpr int PF = 2;
     for (int chunk = beg; chunk < end; chunk += 64) {
       const int n = min(64, end - chunk);
-      const int my_src = (lane < n) ? row[chunk + lane] : 0;
+      const int my_src = chunk_ids(row, chunk, n, lane);
       Raw kb[PF], vb[PF];
       float fb[PF][FE_PAD];
       auto fetch = [&](int j, Raw& kr, Raw& vr, float (&fr)[FE_PAD]) {
@@ -615,10 +612,7 @@ template <typename T>
 int launch_fused(const FusedBwdArgs& f) {
   const BwdArgs& a = f.b;
   const float scale = 1.0f / sqrtf((float)a.C);
-  const bool aligned = rows_aligned({{a.q, a.ldq}, {a.k, a.ldk}, {a.v, a.ldv}, {a.out, a.ldo}, {a.d_out, a.lddo}, {a.dq, a.lddq},
-                                     {a.dk, a.lddk}, {a.dv, a.lddv}, {f.addend, f.ldadd}, {f.d_addend, f.lddadd}},
-                                    align_elems(AttnOp::BwdFusedEdge, sizeof(T)));
-  const AttnPlan p = plan_attention(AttnOp::BwdFusedEdge, a.H, a.C, f.fe_pad, a.n_dst, a.n_src, aligned, false, 0);
+  const AttnPlan p = plan_of<T>(AttnOp::BwdFusedEdge, a, f.fe_pad, {{f.addend, f.ldadd}, {f.d_addend, f.lddadd}});
   if (p.route != AttnRoute::Wave) {
     set_error("gt_attention_fused_edge_bwd: shape H=%d C=%d fe_pad=%d is not covered by the fused backward", a.H, a.C, f.fe_pad);
     return ANEMOI_E_UNSUPPORTED;

@@ -1,7 +1,7 @@
-// Edge attention, forward: what stands in front of the fused-edge forward kernel - build-time knobs, the packed dot product, the
-// deferred-max threshold.  gt_attention.hip and csrc/experiments/gt_attention_r05_variants.hip each include this, define THEIR
-// gt_attn_fused_edge_fwd_kernel<T, VEC, LPH, FE_PAD, KVADJ>, and then include gt_attention_fwd_host.h (every other kernel of the
-// forward, the launches and the C entry points).  WLayout, kWavesPerBlock and the launch plan come from gt_attention_plan.h.
+// Edge attention: build-time knobs, the packed dot product, the deferred-max threshold, chunk_ids and dropout_weight (the two small
+// phases more than one wave kernel shares).  gt_attention.hip and csrc/experiments/gt_attention_r05_variants.hip each include this, define
+// THEIR gt_attn_fused_edge_fwd_kernel<T, VEC, LPH, FE_PAD, KVADJ>, and then include gt_attention_fwd_host.h (every other kernel of the
+// forward, the launches, the C entry points); gt_attention_bwd.hip includes it too.  WLayout and the plan: gt_attention_plan.h.
 #pragma once
 #include <type_traits>
 
@@ -44,5 +44,13 @@ __device__ __forceinline__ float dot_rows(const Vec<T, VEC>& a, const Vec<T, VEC
 // exceeds its running max by more than this; otherwise p = exp(s - m_old) <= e^8 is accumulated directly (fp32
 // accumulators; the value after the final division is the same).
 constexpr float kDeferThr = 8.0f;
+
+// The ids of a chunk of up to 64 edges: ONE coalesced load (lane j holds ids[chunk + j]), broadcast later with v_readlane, so that
+// row loads never wait on a dependent scalar load.  (No __restrict__ on helper parameters: the kernels' own carry it.)
+__device__ __forceinline__ int chunk_ids(const int32_t* ids, int chunk, int n, int lane) { return (lane < n) ? ids[chunk + lane] : 0; }
+// Dropout acts on the NORMALISED weight: the denominator sums every edge, the numerator the kept ones (scaled by 1 / (1 - p)).
+__device__ __forceinline__ float dropout_weight(float p, uint64_t seed, int edge, int head, float drop_p, float inv_keep) {
+  return drop_p > 0.f ? p * attn_dropout_scale(seed, edge, head, drop_p, inv_keep) : p;
+}
 
 }  // namespace anemoi

@@ -63,8 +63,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void gt_attn_fwd_kernel(
     const float corr = __expf(m - m_new);  // first edge: exp(-inf) = 0
     const float p = __expf(dot - m_new);
     l = fmaf(l, corr, p);
-    // dropout acts on the NORMALISED weight: the denominator sums every edge, the numerator the kept ones (scaled by 1 / (1 - p))
-    const float pv = drop_p > 0.f ? p * attn_dropout_scale(drop_seed, ei, lane / LPH, drop_p, inv_keep) : p;
+    const float pv = dropout_weight(p, drop_seed, ei, lane / LPH, drop_p, inv_keep);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[j] = fmaf(acc[j], corr, pv * cur.v[j]);
     m = m_new;

@@ -37,12 +37,13 @@ struct AttnPlan {
 };
 
 // LDS image of W' = [W_e | b_e | 0] of the fused-edge kernels: per lane a chunk of VEC*FE_PAD floats (+4 floats of padding so that
-// 16 consecutive lanes' ds_read_b128 hit 16 distinct 16-byte bank slots).
+// 16 consecutive lanes' ds_read_b128 hit 16 distinct 16-byte bank slots), laid out [feature][channel]; at(c, f) = W'[c][f].
 constexpr int w_image_chunk(int vec, int fe_pad) { return vec * fe_pad + 4; }
 template <int VEC, int FE_PAD>
 struct WLayout {
   static constexpr int kChunk = w_image_chunk(VEC, FE_PAD);
   static constexpr int kFloats = 64 * kChunk;
+  static constexpr int at(int c, int f) { return (c / VEC) * kChunk + f * VEC + (c % VEC); }
 };
 constexpr int64_t w_image_bytes(int vec, int fe_pad) { return 64 * (int64_t)w_image_chunk(vec, fe_pad) * (int64_t)sizeof(float); }
 constexpr int64_t kMaxDynamicLds = 64 * 1024;  // the default dynamic-LDS limit: no kernel of the family raises it

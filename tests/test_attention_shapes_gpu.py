@@ -316,6 +316,54 @@ def test_degree_ladder_forward(ops, H, C, dtype, hot):
             assert float(sep[1][empty].abs().max()) == 0.0 and (aa is not None or float(sep[0][empty].abs().max()) == 0.0)
 
 
+_WT_CHILD = """
+import sys
+sys.path.insert(0, {repo!r})
+import torch
+from tests import test_attention_shapes_gpu as t
+from anemoi_core_amd import ops
+c = t._dst_ladder(8, 64, t.BF16, {hot!r}, 11)
+csc = ops.build_csc(c["ei"].to(t.DEV), (c["n_src"], c["n_dst"]))
+q, k, v, add = t._dev(c["q"], c["k"], c["v"], c["add"])
+feat, wp = ops.pack_edge_features(c["ea"].to(t.DEV)), ops.pack_edge_weights(c["w"].to(t.DEV), c["b"].to(t.DEV))
+res = [x.cpu() for aa in (None, add) for x in ops.gt_attention_fused_edge(q, k, v, feat, wp, csc, 8, addend=aa, return_lse=True)]
+torch.save(res, {path!r})
+"""
+
+
+@pytest.mark.parametrize("hot", ["first", "last"])
+def test_degree_ladder_forward_write_through_stores(ops, tmp_path, hot):
+    """ANEMOI_ATTN_OUT_WT=1 (write-through output rows of the fused-edge forward; read once per process, so a child runs it): the
+    (8, 64) bf16 ladder, with and without addend, against the float64 restatement at the 16-bit bound, and the bits of the default
+    stores."""
+    import os
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = str(tmp_path / "wt.pt")
+    r = subprocess.run([sys.executable, "-c", _WT_CHILD.format(repo=repo, hot=hot, path=path)], cwd=repo, env={**os.environ, "ANEMOI_ATTN_OUT_WT": "1"},
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = torch.load(path)
+    H, C, dtype = 8, 64, BF16
+    tag = f"ladder-fwd write-through H{H} C{C} {NAME[dtype]} hot={hot}"
+    c = _dst_ladder(H, C, dtype, hot, 11)
+    feat64, wp64 = _pack(c["ea"], c["w"], c["b"])
+    want, want_lse = _attention(c["q"].double(), c["k"].double(), c["v"].double(), feat64 @ wp64.t(), c["ei"], c["n_dst"], H)
+    csc = ops.build_csc(c["ei"].to(DEV), (c["n_src"], c["n_dst"]))
+    qd, kd, vd, addd = _dev(c["q"], c["k"], c["v"], c["add"])
+    feat, wp = ops.pack_edge_features(c["ea"].to(DEV)), ops.pack_edge_weights(c["w"].to(DEV), c["b"].to(DEV))
+    assert ops.gt_attention_plan("forward_fused_edge", H, C, fe_pad=12, n_dst=c["n_dst"], n_src=c["n_src"], dtype=dtype).vec == 8  # 16-byte rows
+    for i, (name, aa, aa64) in enumerate((("fused", None, None), ("fused+addend", addd, c["add"].double()))):
+        out, lse = got[2 * i], got[2 * i + 1]
+        assert out.dtype == dtype and lse.dtype == F32
+        _close(tag, out, want if aa64 is None else want + aa64, dtype, f"{name} out")
+        _close(tag, lse, want_lse, F32, f"{name} lse")
+        plain = ops.gt_attention_fused_edge(qd, kd, vd, feat, wp, csc, H, addend=aa, return_lse=True)
+        assert torch.equal(out, plain[0].cpu()) and torch.equal(lse, plain[1].cpu()), f"{tag} {name}: the store kind changes the bits"
+
+
 # ------------------------------------------------------------------------------------------------- 2. degree ladder, backward
 def _check_backward(ops, tag, c, H, dtype, zero_dst=None, zero_src=None, print_fp32_reference=False):
     """gt_attention_backward and gt_attention_fused_edge_backward (need_feat_grad) of one case dict against float64 autograd; the
