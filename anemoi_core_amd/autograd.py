@@ -491,3 +491,21 @@ class EdmOutputFunction(torch.autograd.Function):
     def backward(ctx, d_out):
         (sigma,) = ctx.saved_tensors
         return ops.edm_output_backward(d_out, sigma, ctx.pred_shape, ctx.pred_dtype, sigma_data=ctx.sigma_data), None, None, None, None, None
+
+
+class KernelCrpsFunction(torch.autograd.Function):
+    """``ops.kernel_crps`` with its HIP backward: pred, target and the weights are kept (no gradient tensor is), the ranks are recomputed.
+    The target and the weights carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, w_grid, w_var, w_time, alpha, ignore_nans, squash, squash_mode):
+        ctx.options = dict(alpha=alpha, ignore_nans=ignore_nans, squash=squash, squash_mode=squash_mode)
+        ctx.save_for_backward(pred, target, w_grid, w_var, w_time)
+        args, dims, mode = ops._crps_operands(pred, target, w_grid, w_var, w_time, alpha, squash, squash_mode)
+        return ops._kernel_crps_fwd(args, dims, mode, ignore_nans, pred.device)
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        pred, target, w_grid, w_var, w_time = ctx.saved_tensors
+        d_pred = ops.kernel_crps_backward(d_loss, pred, target, w_grid, w_var=w_var, w_time=w_time, **ctx.options)
+        return d_pred, None, None, None, None, None, None, None, None

@@ -2490,3 +2490,85 @@ def edm_update_(mode: int, params: Tensor, y: Tensor, D: Tensor, aux1: Optional[
                                        0 if aux2 is None else aux2.data_ptr(), y.numel(), _real(y, "edm_update_: y"), _stream())
     _lib.check(rc, "edm_update")
     return y
+
+
+# ---------------------------------------------------------------------------------------------- the ensemble loss (csrc/crps.hip)
+CRPS_MAX_ENSEMBLE, CRPS_MAX_VARS = 16, 4096  # what anemoi_crps_fwd / _bwd are built for
+_SQUASH = {"avg": 1, "sum": 2}
+
+
+def _crps_operands(pred: Tensor, target: Tensor, w_grid: Tensor, w_var: Optional[Tensor], w_time: Optional[Tensor], alpha: float, squash: bool,
+                   squash_mode: str) -> tuple:
+    """The checked operands of the CRPS kernels, in the order both entry points take them, and (B, T, E, N, V)."""
+    if pred.dim() != 5:
+        raise ValueError(f"kernel_crps: pred [batch, time, ensemble, grid, vars], got {tuple(pred.shape)}")
+    B, T, E, N, V = pred.shape
+    if E == 1:
+        raise ValueError("kernel_crps: Ensemble size must be greater than 1.")
+    if E > CRPS_MAX_ENSEMBLE:
+        raise NotImplementedError(f"kernel_crps: ensemble size {E} beyond the built limit {CRPS_MAX_ENSEMBLE}")
+    if V > CRPS_MAX_VARS:
+        raise NotImplementedError(f"kernel_crps: {V} variables beyond the built limit {CRPS_MAX_VARS}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"kernel_crps: alpha must be in the range [0, 1], got {alpha}")
+    if squash and squash_mode not in _SQUASH:
+        raise ValueError(f"kernel_crps: invalid squash_mode '{squash_mode}'; supported modes are 'avg', 'sum'")
+    _dev(pred, target, w_grid, w_var, w_time)
+    if target.dim() == 4:
+        target = target.unsqueeze(2)
+    if tuple(target.shape) != (B, T, 1, N, V):
+        raise ValueError(f"kernel_crps: target [{B}, {T}, 1, {N}, {V}] or [{B}, {T}, {N}, {V}], got {tuple(target.shape)}")
+    if pred.dtype not in (torch.float32, torch.bfloat16) or target.dtype not in (torch.float32, pred.dtype):
+        raise NotImplementedError(f"kernel_crps: pred float32 or bfloat16 and target float32 or pred's dtype, got {pred.dtype}, {target.dtype}")
+    ps, ts = _state5(pred, "kernel_crps: pred"), _state5(target, "kernel_crps: target")
+    if min(pred.stride()) < 0 or min(target.stride()) < 0:
+        raise ValueError("kernel_crps: negative strides")
+    args = (pred.data_ptr(), *ps, _dt(pred), target.data_ptr(), ts[0], ts[1], ts[3], _dt(target), _vec(w_grid, "kernel_crps: w_grid", N, torch.float32),
+            _vec(w_var, "kernel_crps: w_var", V, torch.float32), _vec(w_time, "kernel_crps: w_time", T, torch.float32), float(alpha))
+    return args, (B, T, E, N, V), (_SQUASH[squash_mode] if squash else 0)
+
+
+def kernel_crps(pred: Tensor, target: Tensor, w_grid: Tensor, *, alpha: float = 0.95, w_var: Optional[Tensor] = None, w_time: Optional[Tensor] = None,
+                ignore_nans: bool = False, squash: bool = True, squash_mode: str = "avg") -> Tensor:
+    """The weighted almost-fair kernel CRPS of an ensemble, two launches (anemoi_crps_fwd): pred [B, T, E, N, V] (fp32 / bf16) and target
+    [B, T, 1, N, V] or [B, T, N, V] (fp32 or pred's dtype) are read in place through their strides (contiguous variables), the column
+    weight is w_time[t] w_grid[n] w_var[v] (contiguous fp32 vectors; None: 1), all arithmetic is fp32.  Returns the fp32 loss reduced as
+    the reference reduces it: summed over time and grid, averaged over the batch; a scalar under ``squash`` (the mean, or with "sum" the
+    sum, over the variables), [V] without.  ``ignore_nans``: columns with a NaN in the target or a member count 0.  Deterministic.
+    Differentiable in ``pred`` (``autograd.KernelCrpsFunction``: anemoi_crps_bwd); not in the target or the weights."""
+    args, dims, mode = _crps_operands(pred, target, w_grid, w_var, w_time, alpha, squash, squash_mode)
+    for name, t in (("target", target), ("w_grid", w_grid), ("w_var", w_var), ("w_time", w_time)):
+        if _needs_grad(t):
+            raise NotImplementedError(f"kernel_crps: a gradient with respect to {name} is not built; detach it")
+    if _needs_grad(pred):
+        from .autograd import KernelCrpsFunction
+
+        return KernelCrpsFunction.apply(pred, target, w_grid, w_var, w_time, float(alpha), bool(ignore_nans), bool(squash), squash_mode)
+    return _kernel_crps_fwd(args, dims, mode, bool(ignore_nans), pred.device)
+
+
+def _kernel_crps_fwd(args: tuple, dims: tuple, mode: int, ignore_nans: bool, device) -> Tensor:
+    B, T, E, N, V = dims
+    lib = _lib.load()
+    ws = torch.empty((max(lib.anemoi_crps_workspace_bytes(B, T, N, V) // 4, 1),), dtype=torch.float32, device=device)
+    loss = torch.empty((V,) if mode == 0 else (), dtype=torch.float32, device=device)
+    rc = lib.anemoi_crps_fwd(*args, 1 if ignore_nans else 0, mode, loss.data_ptr(), ws.data_ptr(), ws.numel() * 4, B, T, E, N, V, _stream())
+    _lib.check(rc, "crps_fwd")
+    return loss
+
+
+def kernel_crps_backward(upstream: Tensor, pred: Tensor, target: Tensor, w_grid: Tensor, *, alpha: float = 0.95, w_var: Optional[Tensor] = None,
+                         w_time: Optional[Tensor] = None, ignore_nans: bool = False, squash: bool = True, squash_mode: str = "avg") -> Tensor:
+    """d_pred, contiguous [B, T, E, N, V] in pred's dtype, from the gradient ``upstream`` of ``kernel_crps``'s result (fp32 on the device: a
+    scalar under ``squash``, [V] without - an expanded one is read in place), one launch (anemoi_crps_bwd): the ranks are recomputed from
+    pred and target, nothing of the forward is kept."""
+    args, dims, mode = _crps_operands(pred, target, w_grid, w_var, w_time, alpha, squash, squash_mode)
+    B, T, E, N, V = dims
+    _dev(pred, upstream)
+    if upstream.dtype != torch.float32 or upstream.numel() != (V if mode == 0 else 1) or upstream.dim() > 1:
+        raise ValueError(f"kernel_crps_backward: upstream is float32 with {V if mode == 0 else 1} value(s), got {upstream.dtype} {tuple(upstream.shape)}")
+    us = upstream.stride(0) if (mode == 0 and V > 1) else (1 if mode == 0 else 0)
+    d_pred = torch.empty((B, T, E, N, V), dtype=pred.dtype, device=pred.device)
+    rc = _lib.load().anemoi_crps_bwd(*args, 1 if ignore_nans else 0, mode, upstream.data_ptr(), us, d_pred.data_ptr(), B, T, E, N, V, _stream())
+    _lib.check(rc, "crps_bwd")
+    return d_pred

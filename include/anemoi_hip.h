@@ -31,7 +31,8 @@ extern "C" {
 
 /* (The EDM diffusion entries - anemoi_noise_cond_fwd, anemoi_transport_assemble_input, anemoi_edm_output, anemoi_edm_update - were added at
  * 25 without a bump: they only add entry points, every earlier signature keeps its meaning.  The same holds for their backward entries -
- * anemoi_noise_cond_bwd (+ _workspace_bytes), anemoi_transport_assemble_input_bwd, anemoi_edm_output_bwd - added at 26.) */
+ * anemoi_noise_cond_bwd (+ _workspace_bytes), anemoi_transport_assemble_input_bwd, anemoi_edm_output_bwd - added at 26, and for the
+ * ensemble loss - anemoi_crps_workspace_bytes, anemoi_crps_fwd, anemoi_crps_bwd - added at 26 as well.) */
 #define ANEMOI_HIP_ABI_VERSION 26
 
 typedef enum { ANEMOI_F32 = 0, ANEMOI_BF16 = 1, ANEMOI_F16 = 2 } anemoi_dtype_t;
@@ -908,6 +909,38 @@ int anemoi_transport_assemble_input_bwd(const void* d_rows, int64_t ldr, int32_t
 int anemoi_edm_output_bwd(const void* d_out, int32_t d_out_f64, int64_t gs_b, int64_t gs_t, int64_t gs_e, int64_t gs_n, int64_t gs_v,
                           const void* sigma, int32_t sigma_f64, double sigma_data, int32_t precondition, void* d_pred, int64_t ldp, int32_t P,
                           anemoi_dtype_t pred_dtype, int32_t B, int32_t E, int32_t N, int32_t T_out, int32_t V_out, void* stream);
+
+/* ---- The ensemble loss (csrc/crps.hip): the almost-fair kernel CRPS, weighted and reduced, and its gradient.
+ * Replaces: CRPS.forward = mask_nans + _kernel_crps (either backend) + BaseLoss.scale + BaseLoss.reduce
+ * (training/src/anemoi/training/losses/kcrps.py:77-191, losses/base.py:94-149, 180-251) and what torch autograd derives from them.
+ *   per column (b, t, n, v), members x_1..x_E = pred[b, t, :, n, v], y = target[b, t, n, v], all arithmetic fp32:
+ *     s_m = sum_j sign(x_m - x_j);  crps = (1/E) sum_m |x_m - y| + coef sum_m (x_m - y) s_m,
+ *     coef = -(alpha / (E (E - 1)) + (1 - alpha) / E^2)   (the value of both reference backends; sum_m s_m = 0)
+ *     column weight w = w_time[t] w_grid[n] w_var[v]      (w_time, w_var NULL: 1)
+ *   loss[v] = (1/B) sum_{b, t, n} w crps   (squash 0: V values);  squash 1: their mean over v, squash 2: their sum (one value).
+ *   ignore_nans != 0: a column with a NaN in y or in any member counts 0 and has gradient 0.
+ * pred: [B, T, E, N, V] in pred_dtype (fp32 or bf16) read through its element strides ps_*, target: [B, T, N, V] in target_dtype (fp32 or
+ * pred_dtype) through ts_*; the variable axis of both is contiguous.  2 <= E <= 16, V <= 4096, N V < 2^31, B T <= 65535.
+ * Deterministic: per-workgroup fp32 partial rows in the workspace, summed by one workgroup in a fixed order with fp64 accumulators; no
+ * atomics.  Two launches forward, one backward. ---- */
+
+/* Bytes of fp32 workspace anemoi_crps_fwd needs: one row of V partials per stage-one workgroup. */
+int64_t anemoi_crps_workspace_bytes(int32_t B, int32_t T, int32_t N, int32_t V);
+
+/* loss: fp32, V values (squash 0) or one. */
+int anemoi_crps_fwd(const void* pred, int64_t ps_b, int64_t ps_t, int64_t ps_e, int64_t ps_n, anemoi_dtype_t pred_dtype, const void* target,
+                    int64_t ts_b, int64_t ts_t, int64_t ts_n, anemoi_dtype_t target_dtype, const float* w_grid, const float* w_var,
+                    const float* w_time, double alpha, int32_t ignore_nans, int32_t squash, float* loss, void* workspace, int64_t workspace_bytes,
+                    int32_t B, int32_t T, int32_t E, int32_t N, int32_t V, void* stream);
+
+/* d_pred[b, t, m, n, v] = upstream[v us] w (1/B) (sign(x_m - y) / E + coef s_m)  (/ V under squash 1), s_m recomputed from pred and target:
+ * nothing is saved by the forward.  upstream: fp32 on the device, one value (squash 1, 2: us = 0) or V values with element stride us = 1
+ * (0: an expanded gradient).  d_pred: contiguous [B, T, E, N, V] in pred_dtype, every element written.  There is no gradient to the
+ * target or the weights. */
+int anemoi_crps_bwd(const void* pred, int64_t ps_b, int64_t ps_t, int64_t ps_e, int64_t ps_n, anemoi_dtype_t pred_dtype, const void* target,
+                    int64_t ts_b, int64_t ts_t, int64_t ts_n, anemoi_dtype_t target_dtype, const float* w_grid, const float* w_var,
+                    const float* w_time, double alpha, int32_t ignore_nans, int32_t squash, const float* upstream, int64_t us, void* d_pred,
+                    int32_t B, int32_t T, int32_t E, int32_t N, int32_t V, void* stream);
 
 #ifdef __cplusplus
 }
